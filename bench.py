@@ -61,7 +61,13 @@ def parse():
     ap.add_argument("--layers-out", default=None, help="write the per-launch table as JSON to this path")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / aggregation only (gloo, no GPU work): what the CPU test of the N>1 entry runs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result dicts of the last timed step (rank 0) as DIR/<name>.npy "
+                         "(float32 / float64): same arguments, same inputs, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -358,6 +364,8 @@ def main():
     stamps.append(time.perf_counter())
     barrier()
     elapsed = time.perf_counter() - t0
+    # what the caller received for the last timed step (the sustained leg below overwrites `last`)
+    timed_last = last.get("results" if args.workload == "full" else "detections")
     if os.environ.get("VTD_BENCH_STAMPS") == "1" and rank == 0:
         print("per-step host times (ms): " + " ".join(f"{1e3 * (b - a):.2f}" for a, b in zip([t0] + stamps, stamps)) +
               f" | barrier {1e3 * (t0 + elapsed - stamps[-1]):.2f}", file=sys.stderr)
@@ -379,6 +387,8 @@ def main():
         if texts and not any(texts):
             print("bench.py: every recognised text of the last batch is empty; no number is reported", file=sys.stderr)
             raise SystemExit(3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_last)
 
     roofline = None
     layer_rows = []
@@ -553,6 +563,42 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, per_frame):
+    """The last timed step's results as float arrays, one row per detection in frame order: `frame` (index in the batch), `bbox` [N,4],
+    `polygon` [N,4,2], `detection_confidence`, and for the full workload `text` [N,L] (Unicode code points, 0-padded) and
+    `recognition_confidence`; `detections_per_frame` [B].  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the rows is kept."""
+    import numpy as np
+    if per_frame is None:
+        raise SystemExit("bench.py: --dump-outputs: the timed steps returned no results")
+    full = bool(per_frame) and isinstance(per_frame[0], dict)   # pipeline result dicts; the detector workload returns detection lists
+    per_frame = [r["detections"] if full else r for r in per_frame]
+    dets = [(i, d) for i, r in enumerate(per_frame) for d in r]
+    rows = {"frame": np.array([i for i, _ in dets], np.float64),
+            "bbox": np.array([d["bbox"] for _, d in dets], np.float64).reshape(-1, 4),
+            "polygon": np.array([d["polygon"] for _, d in dets], np.float64).reshape(-1, 4, 2),
+            "detection_confidence": np.array([d["detection_confidence" if full else "confidence"] for _, d in dets], np.float64)}
+    if full:
+        width = max([len(d["text"]) for _, d in dets] + [1])
+        text = np.zeros((len(dets), width), np.float32)
+        for k, (_, d) in enumerate(dets):
+            text[k, :len(d["text"])] = [ord(c) for c in d["text"]]
+        rows["text"] = text
+        rows["recognition_confidence"] = np.array([d["recognition_confidence"] for _, d in dets], np.float64)
+    counts = np.array([len(r) for r in per_frame], np.float64)
+    per_row = sum(a[:1].nbytes for a in rows.values())
+    budget = DUMP_LIMIT_BYTES - counts.nbytes - 4096 * (len(rows) + 1)   # (an .npy header is at most a few hundred bytes)
+    if per_row and len(dets) * per_row > budget:
+        keep = np.sort(np.random.default_rng(0).choice(len(dets), budget // per_row, replace=False))
+        rows = {k: a[keep] for k, a in rows.items()}
+    rows["detections_per_frame"] = counts
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in rows.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def read_sclk_mhz():

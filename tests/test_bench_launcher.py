@@ -73,3 +73,40 @@ def test_roofline_traffic_lookup_for_the_transformer_line():
         rows = detail["live_rows_of_that_launch"]
         assert rows >= 256
         assert 0.95 <= traffic / detail["algorithmic_bytes_of_that_launch"] <= 1.10, (launch, rows, traffic, detail)
+
+
+def test_dump_outputs_writes_the_result_dicts_as_float_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: one row per detection in frame order, float32 / float64 only, texts as code points; above the size limit a
+    seeded sample of rows that is the same from run to run."""
+    import numpy as np
+    import bench
+    det = lambda k: {"bbox": [k, k + 1, k + 9, k + 5], "polygon": [[k, k + 1], [k + 9, k + 1], [k + 9, k + 5], [k, k + 5]],
+                     "detection_confidence": 0.5 + k / 100, "text": "ab" * k, "recognition_confidence": 0.25 + k / 200}
+    results = [{"frame_number": 0, "timestamp": 0.0, "detections": [det(1), det(2)]},
+               {"frame_number": 1, "timestamp": 0.1, "detections": []},
+               {"frame_number": 2, "timestamp": 0.2, "detections": [det(3)]}]
+    bench.dump_outputs(str(tmp_path / "full"), results)
+    got = {p.stem: np.load(p) for p in (tmp_path / "full").iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["frame"].tolist() == [0, 0, 2] and got["detections_per_frame"].tolist() == [2, 0, 1]
+    assert got["bbox"].tolist() == [d["bbox"] for d in (det(1), det(2), det(3))] and got["polygon"].shape == (3, 4, 2)
+    assert got["detection_confidence"].tolist() == [0.51, 0.52, 0.53] and got["recognition_confidence"].tolist() == [0.255, 0.26, 0.265]
+    assert ["".join(chr(int(c)) for c in row if c) for row in got["text"]] == ["ab", "abab", "ababab"]
+    # the detector workload: per-frame lists of detection dicts, no recogniser fields
+    bench.dump_outputs(str(tmp_path / "det"), [[{"bbox": [1, 2, 3, 4], "polygon": [[1, 2]] * 4, "confidence": 0.75}], []])
+    assert sorted(p.stem for p in (tmp_path / "det").iterdir()) == ["bbox", "detection_confidence", "detections_per_frame", "frame", "polygon"]
+    # a large output is cut to a seeded sample under the limit, identical on every call
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    many = [{"detections": [det(k % 7) for k in range(300)]} for _ in range(4)]
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), many)
+    size = sum(p.stat().st_size for p in (tmp_path / "s1").iterdir())
+    assert size <= 64 << 10
+    assert 0 < len(np.load(tmp_path / "s1" / "frame.npy")) < 1200
+    for p in (tmp_path / "s1").iterdir():
+        assert np.array_equal(np.load(p), np.load(tmp_path / "s2" / p.name))
+
+
+def test_steps_below_one_is_an_error():
+    r = _run("--dry-run", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
