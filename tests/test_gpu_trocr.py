@@ -258,15 +258,13 @@ def test_queued_tickets_share_one_pass_and_equal_the_synchronous_calls(base, mon
             assert np.array_equal(g, w)
 
 
-def test_encoder_pass_beside_the_previous_decode_equals_the_synchronous_calls(base, monkeypatch):
-    """Overlap mode (VTD_TROCR_OVERLAP=1; measured slower than back to back, kept as an option): passes of two tickets, the encoder pass
-    of pass k+1 on a stream confined to one part of every die while the decode of pass k runs on a stream confined to the rest
-    (vtd_stream_create_masked).  Driven the way _pipeline_push drives it -- `pipeline_lag` tickets in flight behind the one asked for --
-    every ticket's ids must equal generate_crops on its own boxes, the second pass must already be encoded when the first is decoded,
-    and the default engine (back to back on the caller's stream; also with passes of four tickets) must give the same ids."""
+def test_pipelined_passes_equal_the_synchronous_calls(base, monkeypatch):
+    """Passes of queued tickets, each encoder pass with its decode right behind it on the caller's stream, while another stream keeps
+    the machine busy.  Driven the way _pipeline_push drives it -- `pipeline_lag` tickets in flight behind the one asked for -- every
+    ticket's ids must equal generate_crops on its own boxes, with passes of two tickets (the default) and of four."""
     from vtd_amd.engine import DeviceFrames, TrOCREngine
     eng, sd = base
-    assert not eng.overlap and eng.pipeline_lag == 1
+    assert eng.pipeline_lag == 1
     batches = []
     for gi, n in enumerate((4, 6, 3, 5, 7, 2, 4)):
         frames, boxes = _crops_in_frames([synth.glyph_crop(1100 + 10 * gi + i) for i in range(n)])
@@ -278,38 +276,26 @@ def test_encoder_pass_beside_the_previous_decode_equals_the_synchronous_calls(ba
     def drive(engine):
         tickets, got = [], []
         for k, (fr, bx) in enumerate(batches):
-            with torch.cuda.stream(side):          # something else keeps the unmasked part of the machine busy
+            with torch.cuda.stream(side):          # something else keeps the machine busy
                 for _ in range(4):
                     noise.mul_(1.0001)
             tickets.append(engine.submit_crops(fr, bx))
             if k >= engine.pipeline_lag:
-                first = k == engine.pipeline_lag
                 got.append(engine.finish(tickets[k - engine.pipeline_lag]).numpy())
-                if first and engine.overlap:
-                    # the first finish cut the four queued tickets into two passes and enqueued BOTH encoder passes before it decoded the first
-                    assert all(t["parts"] is not None for t in tickets[:4])
-                    assert tickets[2]["parts"][0][0] is tickets[3]["parts"][0][0] and not tickets[2]["parts"][0][0]["decoded"]
         for t in tickets[len(got):]:
             got.append(engine.finish(t).numpy())
         return got
 
     for g, w in zip(drive(eng), want):
         assert np.array_equal(g, w)
-    for env in ({"VTD_TROCR_OVERLAP": "1", "VTD_TROCR_DEC_CUS": "96"}, {"VTD_TROCR_PASS_TICKETS": "4"}):
-        for k in ("VTD_TROCR_OVERLAP", "VTD_TROCR_DEC_CUS", "VTD_TROCR_PASS_TICKETS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        other = TrOCREngine(BASE_PRINTED, sd, max_crops=32)
-        try:
-            if "VTD_TROCR_OVERLAP" in env:
-                assert other.overlap and other.pipeline_lag == 3 and other.dec_cus == 96 and other.enc_cus == 160, "CU-masked streams were not created on this box"
-            else:
-                assert not other.overlap and other.pipeline_lag == 3
-            for g, w in zip(drive(other), want):
-                assert np.array_equal(g, w)
-        finally:
-            other.close()
+    monkeypatch.setenv("VTD_TROCR_PASS_TICKETS", "4")
+    other = TrOCREngine(BASE_PRINTED, sd, max_crops=32)
+    try:
+        assert other.pipeline_lag == 3
+        for g, w in zip(drive(other), want):
+            assert np.array_equal(g, w)
+    finally:
+        other.close()
     side.synchronize()
 
 
@@ -430,6 +416,7 @@ def test_passes_on_the_worker_thread_equal_the_synchronous_calls(base, monkeypat
     submitting thread carries on; finish() of such a ticket waits for the worker, finish() of a ticket still in the queue flushes it in
     the calling thread.  Five tickets -> two passes on the worker + one leftover: every ticket's ids equal generate_crops on its own boxes;
     discard_queue drops what the worker has not started."""
+    from vtd_amd._native import NativeError
     from vtd_amd.engine import DeviceFrames, TrOCREngine
     eng, sd = base
     monkeypatch.setenv("VTD_TROCR_ASYNC", "1")
@@ -459,6 +446,8 @@ def test_passes_on_the_worker_thread_equal_the_synchronous_calls(base, monkeypat
         assert np.array_equal(a.finish(t).numpy(), want[0]) and np.array_equal(a.finish(t2).numpy(), want[1])
     finally:
         a.close()
+    with pytest.raises(NativeError):   # a closed engine takes no more tickets
+        a.submit_crops(*batches[0])
 
 
 def test_panel_major_gemm_inputs_change_no_bit(base, monkeypatch):

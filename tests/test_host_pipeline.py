@@ -300,10 +300,11 @@ def test_swallowed_errors_are_counted(pipe):
     assert pipe.error_counts == {"detection": 1, "collection": 1}
 
 
-def test_host_frames_enter_the_detector_one_interval_after_their_copy(pipe, monkeypatch):
+def test_host_frames_enter_the_detector_one_interval_after_their_copy_and_return_to_the_pool_behind_it(pipe, monkeypatch):
     """Host frames are staged (pinned buffer + copy on the upload stream) when pushed and enter the detector when the NEXT job is
     pushed, so the detector never waits for its own batch's copy; every stage advances one job per push, results stay whole and in
-    order, the drain flushes a batch that never got its interval, and VTD_STAGE_AHEAD=0 restores detect-at-push.  Host logic only."""
+    order, the drain flushes a batch that never got its interval, every staging buffer goes back to the pool with its own upload
+    event, and VTD_STAGE_AHEAD=0 restores detect-at-push.  Host logic only."""
     from vtd_amd import engine
 
     class _Eng:
@@ -316,8 +317,8 @@ def test_host_frames_enter_the_detector_one_interval_after_their_copy(pipe, monk
     class _Pinned:
         released = []
 
-        def release(self, h):
-            self.released.append(h)
+        def release(self, h, event):
+            self.released.append((h, event))
 
     pinned = _Pinned()
     monkeypatch.setattr(engine, "PINNED", pinned)
@@ -326,10 +327,15 @@ def test_host_frames_enter_the_detector_one_interval_after_their_copy(pipe, monk
     pipe._upload = object()
     pipe._bind_device = lambda: None
 
+    class _Batch(list):
+        ready = None   # DeviceFrames.ready: the upload event
+
     def stage(chunk):
         k = int(chunk[0][0, 0, 0])
         log.append(("stage", k))
-        return list(chunk), f"pinned{k}"
+        batch = _Batch(chunk)
+        batch.ready = f"upload{k}"
+        return batch, f"pinned{k}"
 
     def detect(batch):
         log.append(("detect", int(batch[0][0, 0, 0])))
@@ -353,7 +359,7 @@ def test_host_frames_enter_the_detector_one_interval_after_their_copy(pipe, monk
     rest = pipe._pipeline_drain()
     assert [r["frame_number"] for o in outs for r in o] + [r["frame_number"] for r in rest] == list(range(10))
     assert ("detect", 4) in log and log.index(("detect", 4)) > log.index(("collect", 1))   # the drain enqueues the batch still staged
-    assert sorted(pinned.released) == [f"pinned{k}" for k in range(5)]
+    assert sorted(pinned.released) == [(f"pinned{k}", f"upload{k}") for k in range(5)]
 
     log.clear()
     monkeypatch.setenv("VTD_STAGE_AHEAD", "0")

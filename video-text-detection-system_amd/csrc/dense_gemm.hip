@@ -386,7 +386,7 @@ int vtd_launch_dense_gemm_ex(const half_t* A, int lda, int64_t a_prows, const ha
     static const int grid_env = [] { const char* e = std::getenv("VTD_DGM_GRID"); return e ? std::max(8, std::atoi(e) / 8 * 8) : 0; }();
     if (grid_env) grid = grid_env;
     else {
-        // a stream confined to part of the chip (vtd_stream_create_masked: the encoder pass beside a decode): one workgroup per CU it may
+        // a stream confined to part of the chip (a host's hipExtStreamCreateWithCUMask): one workgroup per CU it may
         // use -- a 256-workgroup grid on 176 CUs would run as one full round and a 45 % round behind it
         uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (hipExtStreamGetCUMask(stream, 8, mask) == hipSuccess) {

@@ -355,6 +355,7 @@ static int autotune_conv(const ConvOp& c, int n, hipStream_t s, int* best_cfg) {
     if (!rc && halo_enabled() && vtd_conv_halo_supported(p, &hbn, &htw)) {
         const char* force = std::getenv("VTD_FORCE_HALO");  // tests: 1 = take the halo kernel wherever it applies,
         if (force && (force[0] == '1' || force[0] == '2' || force[0] == '3')) best = 1e30f;  // 2 = and its persistent 64->64 variant, 3 = the hand-pipelined 64-channel kernel
+        bool pinned = false;  // the variant VTD_FORCE_HALO=2 / 3 names was taken: no later variant may win on time
         for (int variant = 0; variant < 3 && !rc; ++variant) {
             if (variant == 1 && !vtd_conv_halo_c64_supported(p, htw)) continue;
             const int bn = variant == 1 ? 1 : variant == 2 ? 2 : hbn;
@@ -366,7 +367,8 @@ static int autotune_conv(const ConvOp& c, int n, hipStream_t s, int* best_cfg) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, e0, e1);
             const int vid = variant == 1 ? kHaloC64Cfg : variant == 2 ? kHalo64Cfg : kHaloCfg;
-            if (!rc && (ms < best || (variant == 1 && force && force[0] == '2') || (variant == 2 && force && force[0] == '3'))) { best = ms; best_id = vid; }
+            const bool pin = (variant == 1 && force && force[0] == '2') || (variant == 2 && force && force[0] == '3');
+            if (!rc && !pinned && (ms < best || pin)) { best = ms; best_id = vid; pinned = pin; }
         }
     }
     (void)hipEventDestroy(e0);
@@ -1383,25 +1385,6 @@ const char* vtd_strerror(int code) {
     }
     if (code < 0) return hipGetErrorString((hipError_t)(-code));
     return "unknown";
-}
-
-// A stream whose kernels run on a subset of the CUs (hipExtStreamCreateWithCUMask): the Transformer recogniser's encoder pass and its
-// decode each get one, so that the decode's thousands of small dependent launches always find free CUs beside the encoder's wide ones.
-int vtd_stream_create_masked(const uint32_t* cu_mask, int words, vtd_stream* out) {
-    if (!cu_mask || words <= 0 || words > 32 || !out) return ERR_ARG;
-    bool any = false;
-    for (int i = 0; i < words; ++i) any = any || cu_mask[i] != 0;
-    if (!any) return ERR_ARG;
-    hipStream_t s = nullptr;
-    VTD_HIP_CHECK(hipExtStreamCreateWithCUMask(&s, (uint32_t)words, cu_mask));
-    *out = (vtd_stream)s;
-    return 0;
-}
-
-int vtd_stream_destroy(vtd_stream stream) {
-    if (!stream) return ERR_ARG;
-    VTD_HIP_CHECK(hipStreamDestroy((hipStream_t)stream));
-    return 0;
 }
 
 // ---- training loss, forward (app/ml/training/trainer.py:48-56 / :66-71: BCELoss + BCELoss + DiceLoss on the detector's two maps)

@@ -90,8 +90,6 @@ SIGNATURES = {
     "vtd_dbloss_workspace_bytes": (C.c_int64, []),
     "vtd_dbloss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
-    "vtd_stream_create_masked": (C.c_int, [C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_void_p)]),
-    "vtd_stream_destroy": (C.c_int, [C.c_void_p]),
     "vtd_trocr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vtd_trocr_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "vtd_trocr_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),

@@ -150,8 +150,8 @@ class TextDetector:
             logger.warning(f"{int((cnt > ticket['max_out']).sum())} frame(s) exceed max_detections={ticket['max_out']} "
                            f"(up to {int(cnt.max())} components); extra detections dropped -- raise TextDetector.max_detections")
         out = [records_to_dicts(rec[i, :min(int(cnt[i]), ticket["max_out"])]) for i in range(len(cnt))]
-        PINNED.release(ticket["rec"])
-        PINNED.release(ticket["cnt"])
+        PINNED.release(ticket["rec"], ticket["event"])
+        PINNED.release(ticket["cnt"], ticket["event"])
         return out
 
     def detect_batch(self, frames, confidence_threshold: float = 0.5):

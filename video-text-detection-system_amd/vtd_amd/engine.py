@@ -5,6 +5,7 @@ FLOP is issued by libvtd_hip.so.
 import ctypes as C
 import logging
 import os
+import queue
 import sys
 import threading
 
@@ -69,7 +70,8 @@ def _stream_ptr():
 
 class PinnedPool:
     """Recycles pinned host staging buffers (hipHostMalloc costs far more than the copies they serve).  A buffer is
-    handed out again only after `release`, which callers do once the event guarding its last copy has completed."""
+    handed out again only after `release(buf, event)`, which waits for `event` first: the event recorded after the buffer's
+    last GPU use (copy_to_pinned writes through a mapped pointer, so torch cannot know the buffer is busy)."""
 
     def __init__(self):
         self._free = {}
@@ -83,7 +85,10 @@ class PinnedPool:
                 return lst.pop()
         return torch.empty(shape, dtype=dtype).pin_memory()
 
-    def release(self, t):
+    def release(self, t, event):
+        """`event`: None only for a buffer no GPU work ever touched."""
+        if event is not None:
+            event.synchronize()
         with self._lock:
             self._free.setdefault((tuple(t.shape), t.dtype), []).append(t)
 
@@ -418,8 +423,8 @@ class RecognizerEngine(_Tunable):
     def finish_decode(ticket):
         ticket["event"].synchronize()
         out = decode_records_to_text(ticket["host"].numpy())
-        PINNED.release(ticket["host"])
-        PINNED.release(ticket["keep"][0])
+        PINNED.release(ticket["host"], ticket["event"])
+        PINNED.release(ticket["keep"][0], ticket["event"])
         return out
 
     def read_tap(self, name, n):
@@ -453,43 +458,26 @@ def decode_records_to_text(host):
     return [("".join(map(chr, rows[i][:lens[i]])), conf[i]) for i in range(len(lens))]
 
 
-_MASKED_STREAMS = {}   # (device, total CUs, decode CUs) -> (encoder stream, decode stream): process-wide, like torch's own stream pool
-_MASKED_LOCK = threading.Lock()
-
-
-def _masked_stream_pair(lib, device, total, dec_cus):
-    """Two HIP streams with disjoint CU masks (include/vtd.h: vtd_stream_create_masked), wrapped for torch.
-
-    What a mask bit means on this part was measured, not assumed (tools/cumask_map.py on an MI355X, ROCm 7.2): bit i enables CU
-    i // 8 of XCC (die) i % 8, and a die whose bits are ALL zero is not masked at all -- every one of its CUs stays enabled.  So a
-    partition must leave every die some CUs on both sides: the decode gets CUs 0 .. dec_cus / 8 - 1 of every die, the encoder pass the
-    other ones (an evenly 'strided' mask, the first thing tried, emptied whole dies on one side and partitioned nothing).  Equal
-    shares per die also keep the persistent dense GEMM's one-workgroup-per-CU grid balanced (dense_gemm.hip sizes its grid by the
-    stream's mask).  The pair is created once per process and shared by every engine on the device: torch's allocators remember the
-    streams a block was used on (a pinned buffer's free records an event on each of them), so a stream handed to torch must outlive
-    every tensor that met it -- these are never destroyed (tools/cumask_probe.py: a process exits cleanly with them alive)."""
-    dies = 8
-    if total % dies:
-        raise _native.NativeError(f"{total} CUs do not split over {dies} dies")
-    per_die = total // dies
-    dc = min(max(1, dec_cus // dies), per_die - 1)
-    key = (device, total, dc)
-    with _MASKED_LOCK:
-        if key not in _MASKED_STREAMS:
-            words = (total + 31) // 32
-            streams = []
-            for want_dec in (False, True):
-                m = (C.c_uint32 * words)()
-                for die in range(dies):
-                    for cu in range(per_die):
-                        if (cu < dc) == want_dec:
-                            bit = cu * dies + die
-                            m[bit // 32] |= 1 << (bit % 32)
-                h = C.c_void_p()
-                _native.check(lib.vtd_stream_create_masked(m, words, C.byref(h)), "vtd_stream_create_masked")
-                streams.append(torch.cuda.ExternalStream(h.value))
-            _MASKED_STREAMS[key] = tuple(streams)
-        return _MASKED_STREAMS[key] + (dc * dies,)
+def plan_passes(rows, pass_tickets, max_crops):
+    """The recogniser passes of queued tickets with `rows[i]` crops each: groups of `pass_tickets` consecutive tickets, every group cut
+    into passes of at most `max_crops` rows.  A pass is a list of runs (ticket index, first row, rows, offset in the pass), one per
+    stretch of consecutive rows of one ticket -- one staging launch each."""
+    passes = []
+    for g in range(0, len(rows), pass_tickets):
+        runs, used = [], 0
+        for i in range(g, min(g + pass_tickets, len(rows))):
+            first = 0
+            while first < rows[i]:
+                if used == max_crops:
+                    passes.append(runs)
+                    runs, used = [], 0
+                n = min(rows[i] - first, max_crops - used)
+                runs.append((i, first, n, used))
+                first += n
+                used += n
+        if runs:
+            passes.append(runs)
+    return passes
 
 
 class TrOCREngine(_Tunable):
@@ -513,9 +501,8 @@ class TrOCREngine(_Tunable):
         _native.check(self.lib.vtd_trocr_create(C.byref(cfg), self.max_crops, C.byref(h)), "vtd_trocr_create")
         self.handle = h
         try:
-            # one encoder-output slot unless the overlapped order (two passes in flight) or a caller asks for the second one
-            want_slots = slots or (2 if os.environ.get("VTD_TROCR_OVERLAP", "0") == "1" else 1)
-            _native.check(self.lib.vtd_trocr_set_option(h, b"slots", int(want_slots)), "vtd_trocr_set_option(slots)")
+            # one encoder-output slot unless a caller asks for the second one
+            _native.check(self.lib.vtd_trocr_set_option(h, b"slots", int(slots or 1)), "vtd_trocr_set_option(slots)")
             # decoder cross-attention on the raw encoder states (csrc/trocr_xattn.hip; include/vtd.h option "xattn") unless asked for the
             # reference's per-layer key / value projections: xattn=False, or VTD_TROCR_XATTN=0
             want_xattn = (os.environ.get("VTD_TROCR_XATTN", "1") != "0") if xattn is None else bool(xattn)
@@ -535,24 +522,35 @@ class TrOCREngine(_Tunable):
         _native.check(self.lib.vtd_trocr_get_option(h, b"xattn", C.byref(form)), "vtd_trocr_get_option(xattn)")
         self.xattn = bool(form.value)   # the form that runs (a geometry the kernel does not cover keeps the key / value form)
         self._next_slot = 0
-        self._queue = []          # tickets whose crops are not staged yet (submit_crops / finish)
-        self._qlock = threading.Lock()
-        self._passes = []         # encoded passes that wait for their decode, oldest first
-        self._setup_overlap()
+        self._setup_passes()
 
     def close(self):
-        if getattr(self, "_worker", None) is not None and self._worker.is_alive() and not sys.is_finalizing():
-            self._generation = getattr(self, "_generation", 0) + 1
-            self._jobs.put(None)
-            self._worker.join(timeout=60)
+        """Stops the worker thread, then destroys the handle -- unless the worker is still inside a pass: the handle is then left
+        alive (leaked) rather than destroyed under it."""
+        worker = None
+        if getattr(self, "_qlock", None) is not None:
+            with self._qlock:   # submit_crops raises from here on; jobs the worker has not started are dropped
+                self._closed = True
+                self._generation += 1
+                worker = self._worker
+                if worker is not None:
+                    self._jobs.put(None)
+        if worker is not None and worker.is_alive():
+            if sys.is_finalizing():   # (a daemon thread may be frozen anywhere at exit)
+                return
+            worker.join(timeout=60)
+            if worker.is_alive():
+                logger.error("TrOCREngine.close: the recogniser worker is still inside a pass after 60 s; its handle is left alive")
+                return
         if getattr(self, "handle", None):
-            if not sys.is_finalizing():   # work may still be queued on the shared encoder / decode streams
-                try:
-                    torch.cuda.synchronize()
-                except Exception:
-                    pass
-            self.lib.vtd_trocr_destroy(self.handle)
-            self.handle = None
+            with self.lock:
+                if not sys.is_finalizing():   # passes may still run on the streams their tickets came from
+                    try:
+                        torch.cuda.synchronize()
+                    except Exception:
+                        pass
+                self.lib.vtd_trocr_destroy(self.handle)
+                self.handle = None
 
     def __del__(self):
         try:
@@ -632,43 +630,27 @@ class TrOCREngine(_Tunable):
     # ---- pipelined use: recogniser batches are decoupled from detector batches ---------------------------------------------------
     # A decode step costs about the same whether 30 or 300 rows are live (~136 dependent launches), so crops are worth collecting:
     # submit_crops only QUEUES a ticket; the GPU work starts when some ticket's result is asked for (finish) or the queue would
-    # overflow the workspace.  Queued tickets are then cut into PASSES of `pass_tickets` tickets (VTD_TROCR_PASS_TICKETS, default 2);
-    # every pass is ONE encoder pass into an encoder-output slot and ONE decode.
+    # overflow the workspace.  Queued tickets are then cut into PASSES (plan_passes) of `pass_tickets` tickets (VTD_TROCR_PASS_TICKETS,
+    # default 2); every pass is ONE encoder pass into an encoder-output slot and ONE decode right behind it, on the same stream.
     #
     # A caller keeps `pipeline_lag` = pass_tickets - 1 tickets in flight behind the one it asks for (VideoTextPipeline._pipeline_push and
     # bench.py do), so that a whole pass is queued when its first ticket is finished; with fewer in flight the passes are simply smaller.
     #
-    # Overlap (VTD_TROCR_OVERLAP=1, off by default): the handle has two slots, and the encoder pass of pass k+1 can run BESIDE the
-    # decode of pass k -- each on a stream of its own whose kernels are confined to a disjoint part of the chip (include/vtd.h:
-    # vtd_stream_create_masked; VTD_TROCR_DEC_CUS of the 256 CUs for the decode, the rest for the encoder pass; pipeline_lag is then
-    # 2 pass_tickets - 1).  Measured twice, lost twice: on plain streams (round 3) the decoder's ~6.7 k small
-    # dependent launches queued for CU slots behind the encoder's wide ones (10 -> 50 us each) and the encoder pass doubled; with the
-    # chip really partitioned (round 4: 32 / 64 / 96 / 128 CUs for the decode) every decode launch finds its CUs free, but the decode's
-    # kernels are sized to finish in ONE round on 256 CUs -- on a quarter of the chip each takes several -- and the encoder pass loses
-    # the same share: 135 - 238 frames/s against 279 back to back on the ResNet-18 line.  The mode stays as a tested option.
-    def _setup_overlap(self):
+    # Asynchronous passes (VTD_TROCR_ASYNC=1): a full pass (pass_tickets tickets) goes to a worker thread, which stages, encodes and
+    # decodes it while the submitting thread keeps feeding the detector -- a pass blocks its host thread for its whole (host-paced)
+    # decode, during which the caller's thread otherwise submits nothing: the detector's launches of the next pass's batches then fall
+    # into the decode's launch-bound tail instead of running while the recogniser's streams sit idle.  The caller keeps two passes of
+    # tickets in flight (pipeline_lag = 2 pass_tickets - 1).
+    def _setup_passes(self):
         self.pass_tickets = max(1, int(os.environ.get("VTD_TROCR_PASS_TICKETS", "2")))
-        self.overlap = False
-        self._enc_stream = self._dec_stream = None
-        if os.environ.get("VTD_TROCR_OVERLAP", "0") == "1" and self.slots >= 2:
-            try:
-                total = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-                dec_cus = min(max(8, int(os.environ.get("VTD_TROCR_DEC_CUS", "80"))), total - 8)
-                self._enc_stream, self._dec_stream, dec_cus = _masked_stream_pair(self.lib, torch.cuda.current_device(), total, dec_cus)
-                self.overlap = True
-                self.dec_cus, self.enc_cus = dec_cus, total - dec_cus
-            except Exception as e:   # no CU masks on this stack: the back-to-back order
-                logger.warning(f"TrOCREngine: CU-masked streams unavailable ({e}); encoder pass and decode run back to back")
-                self._enc_stream = self._dec_stream = None
-        # Asynchronous passes (VTD_TROCR_ASYNC=1): a full pass (pass_tickets tickets) goes to a worker thread, which stages, encodes and
-        # decodes it while the submitting thread keeps feeding the detector -- a pass blocks its host thread for its whole (host-paced)
-        # decode, during which the caller's thread otherwise submits nothing: the detector's launches of the next pass's batches then fall
-        # into the decode's launch-bound tail instead of running while the recogniser's streams sit idle.  The caller keeps two passes of
-        # tickets in flight (pipeline_lag = 2 pass_tickets - 1).
-        self.async_passes = os.environ.get("VTD_TROCR_ASYNC", "0") == "1" and not self.overlap
-        self._jobs = self._worker = None
-        self._generation = 0
-        self.pipeline_lag = 2 * self.pass_tickets - 1 if (self.overlap or self.async_passes) else max(1, self.pass_tickets - 1)
+        self.async_passes = os.environ.get("VTD_TROCR_ASYNC", "0") == "1"
+        self.pipeline_lag = 2 * self.pass_tickets - 1 if self.async_passes else max(1, self.pass_tickets - 1)
+        self._queue = []          # tickets whose crops are not staged yet (submit_crops / finish)
+        self._qlock = threading.Lock()   # the queue, the worker and the generation: submitting never waits for a pass
+        self._jobs = queue.Queue()
+        self._worker = None
+        self._generation = 0      # bumped by discard_queue / close: jobs of an older generation are dropped by the worker
+        self._closed = False
 
     def submit_crops(self, frames, boxes):
         """Queue the crops `boxes` ([(frame, x1, y1, x2, y2), ...]) of a resident frame batch; returns a ticket for ``finish``.  Nothing
@@ -676,49 +658,45 @@ class TrOCREngine(_Tunable):
         at once)."""
         b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 5))
         ticket = {"boxes": b, "frames": frames, "stream": torch.cuda.current_stream(), "parts": None}
-        if self.async_passes and os.environ.get("VTD_TROCR_MERGE", "1") != "0":
-            # (the engine lock is the worker's for the whole of a pass: the queue has a lock of its own, so submitting never waits for one)
-            job = None
+        merge = os.environ.get("VTD_TROCR_MERGE", "1") != "0"
+        if self.async_passes and merge:
             with self._qlock:
+                self._check_open()
                 self._queue.append(ticket)
                 if len(self._queue) >= self.pass_tickets:
                     group, self._queue = self._queue[:self.pass_tickets], self._queue[self.pass_tickets:]
                     for t in group:
                         t["ready"] = threading.Event()
-                    job = (self._generation, group, torch.cuda.current_device())
-            if job is not None:
-                self._start_worker()
-                self._jobs.put(job)
+                    if self._worker is None:
+                        self._worker = threading.Thread(target=self._worker_loop, name="vtd-trocr-pass", daemon=True)
+                        self._worker.start()
+                    self._jobs.put((self._generation, group, torch.cuda.current_device()))
             return ticket
         with self.lock:
-            room = self.max_crops * (self.slots if self.overlap else 1)
-            if sum(len(t["boxes"]) for t in self._queue) + len(b) > room:
+            self._check_open()
+            if sum(len(t["boxes"]) for t in self._queue) + len(b) > self.max_crops:
                 self._flush()
             with self._qlock:
                 self._queue.append(ticket)
-            if os.environ.get("VTD_TROCR_MERGE", "1") == "0":
+            if not merge:
                 self._flush()
         return ticket
 
-    def _start_worker(self):
-        if self._worker is None or not self._worker.is_alive():
-            import queue as _queue
-            self._jobs = _queue.Queue()
-            self._worker = threading.Thread(target=self._worker_loop, name="vtd-trocr-pass", daemon=True)
-            self._worker.start()
+    def _check_open(self):
+        if self._closed:
+            raise _native.NativeError("TrOCREngine is closed")
 
     def _worker_loop(self):
-        jobs = self._jobs
         while True:
-            job = jobs.get()
+            job = self._jobs.get()
             if job is None:
                 return
             generation, group, device = job
             try:
                 torch.cuda.set_device(device)
                 with self.lock:
-                    if generation == self._generation and getattr(self, "handle", None):   # (discard_queue / close bump the generation)
-                        self._run_groups([group], group)
+                    if generation == self._generation:
+                        self._run_tickets(group, len(group))
             except Exception as e:   # finish() reports it per ticket (parts stay None), as for a synchronous pass that raised
                 logger.error(f"TrOCREngine: recogniser pass failed: {e}")
             finally:
@@ -726,148 +704,91 @@ class TrOCREngine(_Tunable):
                     t["ready"].set()
 
     def _flush(self):
-        """Everything queued is cut into passes and their encoder passes are enqueued (lock held).  Back-to-back mode decodes every pass
-        at once; overlap mode leaves the decodes to ``finish`` (and runs the oldest ones only when the slots run out).  Tickets larger
-        than the workspace are cut into passes of max_crops rows; every ticket ends up with a list of (pass, spans)."""
+        """Everything queued runs now, in passes (lock held)."""
         with self._qlock:
-            queue, self._queue = self._queue, []
-        if not queue:
-            return
-        merge = os.environ.get("VTD_TROCR_MERGE", "1") != "0"
-        groups, k = [], (self.pass_tickets if merge else 1)
-        for i in range(0, len(queue), k):
-            groups.append(queue[i:i + k])
-        self._run_groups(groups, queue)
+            tickets, self._queue = self._queue, []
+        self._run_tickets(tickets, self.pass_tickets if os.environ.get("VTD_TROCR_MERGE", "1") != "0" else 1)
 
-    def _run_groups(self, groups, queue):
-        """Stage + encode (+ decode, back to back) the ticket groups, one or more passes each (lock held)."""
-        if getattr(self, "_passes", None) is None:
-            self._passes = []
-        parts = {id(t): [] for t in queue}
-        for group in groups:
-            rows = [(t, i) for t in group for i in range(len(t["boxes"]))]
-            caller = group[-1]["stream"]
-            for start in range(0, len(rows), self.max_crops):
-                chunk = rows[start:start + self.max_crops]
-                while len(self._passes) >= self.slots:       # both slots hold passes that wait for their decode: run the oldest
-                    self._decode_pass(self._passes[0])
-                slot = self._next_slot
-                self._next_slot = (slot + 1) % self.slots
-                enc = self._enc_stream if self.overlap else caller
-                if self.overlap:
-                    enc.wait_stream(caller)                  # the frames the crops come out of (detector / upload order)
-                spans = {}
-                with torch.cuda.stream(enc):
-                    # runs of consecutive rows of one ticket are staged with one processor launch each
-                    off, kk = 0, 0
-                    while kk < len(chunk):
-                        t, i0 = chunk[kk]
-                        k2 = kk
-                        while k2 < len(chunk) and chunk[k2][0] is t:
-                            k2 += 1
-                        n = k2 - kk
-                        fr = t["frames"]
-                        fr.wait_ready()
-                        bb = np.ascontiguousarray(t["boxes"][i0:i0 + n])
-                        _native.check(self.lib.vtd_trocr_stage_crops_slot(self.handle, slot, C.c_void_p(fr.tensor.data_ptr()), fr.n, fr.height, fr.width,
-                                                                          bb.ctypes.data, n, off, _stream_ptr()), "vtd_trocr_stage_crops")
-                        spans.setdefault(id(t), []).append((off, i0, n))
-                        off += n
-                        kk = k2
-                    _native.check(self.lib.vtd_trocr_encode_staged_slot(self.handle, slot, off, _stream_ptr()), "vtd_trocr_encode_staged")
-                pas = {"slot": slot, "rows": off, "caller": caller, "host": None, "event": None, "ids": None, "users": 0, "decoded": False}
-                for t in group:
-                    if id(t) in spans:
-                        parts[id(t)].append((pas, spans[id(t)]))
-                        pas["users"] += 1
-                self._passes.append(pas)
-                if not self.overlap:
-                    self._decode_pass(pas)
-        for t in queue:             # only now are the tickets marked as run: an exception above leaves them unmarked
-            t["parts"] = parts[id(t)]   # (a ticket keeps its frames until it is finished: the processor launches read them asynchronously)
-
-    def _decode_pass(self, pas):
-        """Greedy decode of one encoded pass (lock held): host-paced, returns when all but the last two steps have run."""
-        if pas["decoded"]:
-            return
-        stream = self._dec_stream if self.overlap else self.decode_stream(pas["caller"])
-        host = None
+    def _run_tickets(self, tickets, pass_tickets):
+        """Every pass of `tickets` (lock held).  Only once all of them were enqueued do the tickets get their `parts`, a list of
+        (pass, first row, rows, offset in the pass): an exception leaves every ticket without parts (finish reports the failure)."""
+        done = []
         try:
-            with torch.cuda.stream(stream):
-                ids, _ = self._enqueue_generate(pas["rows"], pas["slot"])
-                host = PINNED.take(tuple(ids.shape))
-                copy_to_pinned(host, ids)
-                ev = torch.cuda.Event()
-                ev.record()
-            pas.update(host=host, event=ev, ids=ids)
+            for runs in plan_passes([len(t["boxes"]) for t in tickets], pass_tickets, self.max_crops):
+                done.append((self._run_pass(tickets, runs), runs))
         except Exception:
-            if host is not None:
-                PINNED.release(host)
-            pas["failed"] = True
+            for pas, _ in done:
+                PINNED.release(pas["host"], pas["event"])
             raise
-        finally:
-            pas["decoded"] = True
-            if pas in self._passes:
-                self._passes.remove(pas)
+        for t in tickets:
+            t["parts"] = []   # (a ticket keeps its frames until it is finished: the staging launches read them asynchronously)
+        for pas, runs in done:
+            pas["users"] = len(runs)
+            for i, first, n, off in runs:
+                tickets[i]["parts"].append((pas, first, n, off))
 
-    def decode_stream(self, stream=None):
-        """Back-to-back mode: the stream a pass's decode runs on is the one its encoder pass was enqueued on.  (VTD_TROCR_DEC_STREAM=1:
-        a plain high-priority stream of its own -- the round-3 experiment that lost, kept for A/B runs.)"""
-        if os.environ.get("VTD_TROCR_DEC_STREAM", "0") != "1":
-            return stream if stream is not None else torch.cuda.current_stream()
-        if self._dec_stream is None:
-            self._dec_stream = torch.cuda.Stream(priority=-1)
-        return self._dec_stream
+    def _run_pass(self, tickets, runs):
+        """One planned pass (lock held), on the stream its last ticket was submitted from: stage every run into the next slot, encode,
+        decode (host-paced: returns when all but the last two decoder steps have run), copy the ids to a pinned buffer and record the
+        event that guards it.  Returns the pass {"host", "event"}."""
+        slot = self._next_slot
+        self._next_slot = (slot + 1) % self.slots
+        with torch.cuda.stream(tickets[runs[-1][0]]["stream"]):
+            for i, first, n, off in runs:
+                fr = tickets[i]["frames"]
+                fr.wait_ready()
+                bb = np.ascontiguousarray(tickets[i]["boxes"][first:first + n])
+                _native.check(self.lib.vtd_trocr_stage_crops_slot(self.handle, slot, C.c_void_p(fr.tensor.data_ptr()), fr.n, fr.height, fr.width,
+                                                                  bb.ctypes.data, n, off, _stream_ptr()), "vtd_trocr_stage_crops")
+            rows = runs[-1][3] + runs[-1][2]
+            _native.check(self.lib.vtd_trocr_encode_staged_slot(self.handle, slot, rows, _stream_ptr()), "vtd_trocr_encode_staged")
+            ids, _ = self._enqueue_generate(rows, slot)
+            host, event = PINNED.take(tuple(ids.shape)), torch.cuda.Event()
+            try:
+                copy_to_pinned(host, ids)
+                event.record()
+            except Exception:
+                event.record()   # behind whatever of the copy was enqueued
+                PINNED.release(host, event)
+                raise
+        return {"host": host, "event": event}
 
     def finish(self, ticket):
         """ids [n, max_length] int32 (cpu) of a ticket, rows in the order of its boxes.  Flushes the queue when the ticket is still in
-        it (every ticket queued by then gets its encoder pass enqueued: the passes behind this ticket's run beside its decode).
-        Host-blocking: returns when this ticket's decode has finished."""
-        ready = ticket.get("ready")
-        if ready is not None:
-            ready.wait()               # its pass runs (or ran) on the worker thread: encoded and decoded when the event is set
-        else:
+        it.  Host-blocking: returns when this ticket's decodes have finished."""
+        if ticket["parts"] is None and "ready" not in ticket:
             with self.lock:
                 if ticket["parts"] is None:
                     self._flush()
-                if ticket["parts"] is not None:
-                    for pas, _ in ticket["parts"]:
-                        while not pas["decoded"]:          # passes decode in the order they were encoded
-                            self._decode_pass(self._passes[0])
+        if "ready" in ticket:
+            ticket["ready"].wait()     # its pass runs (or ran) on the worker thread
         if ticket["parts"] is None:    # its pass raised half way (the exception went to whoever triggered the flush)
             raise _native.NativeError("the recogniser pass this ticket was queued for failed")
-        n = len(ticket["boxes"])
-        out = torch.empty((n, self.spec.max_length), dtype=torch.int32)
+        out = torch.empty((len(ticket["boxes"]), self.spec.max_length), dtype=torch.int32)
         try:
-            for pas, spans in ticket["parts"]:
-                if pas.get("failed") or pas["event"] is None:
-                    raise _native.NativeError("the recogniser pass this ticket was queued for failed")
+            for pas, first, n, off in ticket["parts"]:
                 pas["event"].synchronize()
-                for off, i0, cnt in spans:
-                    out[i0:i0 + cnt] = pas["host"][off:off + cnt]
+                out[first:first + n] = pas["host"][off:off + n]
         finally:
-            for pas, _ in ticket["parts"]:
+            for pas, *_ in ticket["parts"]:
                 pas["users"] -= 1
-                if pas["users"] == 0 and pas["host"] is not None:
-                    PINNED.release(pas["host"])
-                    pas["host"] = pas["ids"] = None
+                if pas["users"] == 0:
+                    PINNED.release(pas.pop("host"), pas["event"])
             ticket["parts"] = []
             ticket["frames"] = None
         return out
 
     def discard_queue(self):
-        """Drop every ticket that has not been finished (an abandoned video): queued tickets release their frame batches, encoded
-        passes are forgotten (their slots are reused in order; the handle's events keep the GPU side consistent)."""
+        """Drop every ticket that has not been finished (an abandoned video): queued tickets release their frame batches, jobs the worker
+        has not started are dropped, and the device is synchronised so that no pass still writes a pinned buffer once its tickets go."""
         with self.lock:
-            self._generation = getattr(self, "_generation", 0) + 1   # passes still waiting for the worker are dropped when it gets to them
             with self._qlock:
+                self._generation += 1
                 for t in self._queue:
                     t["frames"] = None
                     t["parts"] = None
                 self._queue = []
-            for pas in getattr(self, "_passes", None) or []:
-                pas["decoded"] = pas["failed"] = True
-            self._passes = []
+            torch.cuda.synchronize()
 
     def set_profiling(self, mode):
         _native.check(self.lib.vtd_trocr_set_profiling(self.handle, int(mode)), "vtd_trocr_set_profiling")
@@ -875,9 +796,8 @@ class TrOCREngine(_Tunable):
     def profile(self):
         """(total ms, launches, summed row counts) of the bracketed cross-attention launches since the last call."""
         ms, calls, rows = C.c_double(), C.c_int64(), C.c_int64()
-        stream = self._dec_stream if self._dec_stream is not None else torch.cuda.current_stream()   # get_profile waits for it
         torch.cuda.synchronize()
-        _native.check(self.lib.vtd_trocr_get_profile(self.handle, C.byref(ms), C.byref(calls), C.byref(rows), C.c_void_p(stream.cuda_stream)),
+        _native.check(self.lib.vtd_trocr_get_profile(self.handle, C.byref(ms), C.byref(calls), C.byref(rows), _stream_ptr()),
                       "vtd_trocr_get_profile")
         return ms.value, calls.value, rows.value
 

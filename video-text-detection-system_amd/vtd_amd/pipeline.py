@@ -248,9 +248,11 @@ class VideoTextPipeline:
         token = {"left": len(jobs), "parts": []}
         for idx in jobs:
             tick = self.__dict__["_tick"] = self.__dict__.get("_tick", 0) + 1
-            job = {"info": [frame_info[i] for i in idx], "host": None, "token": token, "pos": idx}
+            job = {"info": [frame_info[i] for i in idx], "host": None, "upload": None, "token": token, "pos": idx}
             try:
                 batch, job["host"] = self._stage([frames[i] for i in idx])
+                if job["host"] is not None:
+                    job["upload"] = batch.ready   # the staging buffer goes back to the pool only behind its upload
                 if ahead and job["host"] is not None:
                     job["staged"] = batch
                 else:
@@ -271,8 +273,7 @@ class VideoTextPipeline:
                     self._try_recognition(older)
                     older["rec_tick"] = tick
             # a job retires `lag` pushes after its recogniser was submitted: 1 for the CRNN; the Transformer recogniser asks for more
-            # (engine.TrOCREngine.pipeline_lag) so that the pass BEHIND the one being decoded is already queued and its encoder pass
-            # runs beside that decode
+            # (engine.TrOCREngine.pipeline_lag) so that a whole recogniser pass is queued by the time its first ticket is asked for
             lag = self._recognizer_lag()
             while self._inflight and (self._inflight[0].get("failed") or self._inflight[0].get("rec_tick", tick) + lag <= tick):
                 out += self._retire(self._inflight.pop(0))
@@ -332,7 +333,7 @@ class VideoTextPipeline:
         if res is None:
             res = [{"frame_number": num, "timestamp": ts, "detections": []} for num, ts in job["info"]]
         if job.get("host") is not None:
-            PINNED.release(job["host"])
+            PINNED.release(job["host"], job["upload"])
         token = job["token"]
         token["parts"] += zip(job["pos"], res)
         token["left"] -= 1
