@@ -117,17 +117,36 @@ int vtd_postproc_run(vtd_postproc* pp, const float* prob_dev, int n, const int32
  * was seen to do once per drained pipeline.  Order the host behind it with an event on `stream`.  Fails (HIP error) for pageable memory. */
 int vtd_copy_to_pinned_host(const void* src_dev, void* dst_pinned_host, int64_t bytes, vtd_stream stream);
 
-/* ---- training loss, forward only (app/ml/training/trainer.py:48-56 training_step, :66-71 validation_step, :130-142 DiceLoss) --
+/* ---- training loss, forward and backward (app/ml/training/trainer.py:48-56 training_step, :66-71 validation_step, :130-142 DiceLoss) --
  * total = nn.BCELoss()(probability, probability_map) + nn.BCELoss()(threshold, threshold_map) + DiceLoss()(probability,
  * probability_map) over `numel` float32 elements per map (any shape; 16-byte aligned device pointers), in ONE pass that reads every
  * element once.  out4_dev = {probability BCE, threshold BCE, dice loss, total} as float32 (the reference's scalar tensors);
  * sums5_dev (optional) = the five float64 sums behind them (BCE numerators, sum p*t, sum p, sum t).  thresh_dev / thresh_target_dev
  * may both be null (DiceLoss alone, or a detector run without its threshold branch): that term is then 0.  smooth = DiceLoss.smooth
  * (1e-5).  workspace_dev: vtd_dbloss_workspace_bytes() bytes, caller-owned, one per concurrent call.  fp64 accumulation in a fixed
- * order: bitwise repeatable.  Backward, AdamW and the plateau scheduler (trainer.py:107-128) are not part of this library yet. */
+ * order: bitwise repeatable.  AdamW and the plateau scheduler (trainer.py:107-128) are torch's, as in the reference. */
 int64_t vtd_dbloss_workspace_bytes(void);
 int vtd_dbloss_forward(const float* prob_dev, const float* thresh_dev, const float* prob_target_dev, const float* thresh_target_dev, int64_t numel,
                        float smooth, void* workspace_dev, float* out4_dev, double* sums5_dev, vtd_stream stream);
+/* Backward of the four scalars above (what torch autograd forms on trainer.py:52-56 with DiceLoss :135-142), one element-wise pass.
+ * sums5_dev: the sums vtd_dbloss_forward returned for the same maps (nothing is recomputed); grad_out4_dev: the upstream gradients of
+ * {probability BCE, threshold BCE, dice loss, total}, read on the device (no host wait).  With g_p = g[0] + g[3], g_th = g[1] + g[3],
+ * g_d = g[2] + g[3], n = numel, den = P + T + smooth and num = 2 I + smooth formed in fp32 from the fp32-rounded sums as the forward forms them:
+ *   grad_prob[i]   = ((g_p (p - t)) / max((1 - p) p, 1e-12)) / n  +  (t (2 (-g_d / den)) + g_d ((num / den) / den))
+ *   grad_thresh[i] = ((g_th (th - th_t)) / max((1 - th) th, 1e-12)) / n
+ * (aten binary_cross_entropy_backward with its 1e-12 clamp: p in {0, 1} against the other label gives +-1e12 g / n).  Either gradient
+ * pointer may be null (that map is then neither read nor written); grad_thresh needs thresh_dev / thresh_target_dev.  Same 16-byte
+ * alignment rule as the forward, for the gradients too.  Element-wise: bitwise repeatable.  Errors -2711 (argument), -2712 (alignment). */
+int vtd_dbloss_backward(const float* prob_dev, const float* thresh_dev, const float* prob_target_dev, const float* thresh_target_dev, int64_t numel,
+                        float smooth, const double* sums5_dev, const float* grad_out4_dev, float* grad_prob_dev, float* grad_thresh_dev,
+                        vtd_stream stream);
+/* ---- validation metrics (app/ml/training/trainer.py:83-103 on_validation_epoch_end: precision_recall_fscore_support(average='binary',
+ * zero_division=0) of `probability > 0.5` against probability_map) -- the counts behind them, never the maps.  ADDS {TP, FP, FN, number of
+ * targets not in {0, 1}} of `pred > threshold` (strict) into the caller-owned int64[4] counts4_dev (8-byte aligned; zero it once per epoch),
+ * so a whole epoch runs without a host sync.  NaN predictions count as negative, NaN targets as "not in {0, 1}".  pred_dev / target_dev:
+ * numel float32 each, 16-byte aligned.  Integer sums: the same counts on every run.  Errors -2721 (argument), -2722 (alignment). */
+int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev, int64_t numel, float threshold, int64_t* counts4_dev,
+                                 vtd_stream stream);
 
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */

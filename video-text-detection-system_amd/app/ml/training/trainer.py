@@ -1,2 +1,4 @@
-"""app.ml.training.trainer (reference: app/ml/training/trainer.py) -> MI355X implementation, first slice: the loss (forward)."""
-from vtd_amd.training import DiceLoss, detection_loss  # noqa: F401
+"""app.ml.training.trainer (reference: app/ml/training/trainer.py) -> MI355X implementation: the loss (forward and analytic backward),
+the validation metrics and the trainer surface (TextDetectionLightningModule as a plain nn.Module; ModelTrainer is a stub)."""
+from vtd_amd.training import (BinaryMetricCounts, DiceLoss, ModelTrainer, TextDetectionDataset, TextDetectionLightningModule,  # noqa: F401
+                              detection_loss, precision_recall_f1)

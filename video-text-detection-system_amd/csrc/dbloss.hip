@@ -1,4 +1,4 @@
-// DB training loss, forward (first slice): the scalar the reference's training / validation step computes,
+// DB training loss, forward; its analytic backward and the validation counts follow below.  The forward:
 //     total = BCELoss(probability, probability_map) + BCELoss(threshold, threshold_map) + DiceLoss(probability, probability_map)
 // (app/ml/training/trainer.py:48-56 training_step, :66-71 validation_step; DiceLoss :130-142; nn.BCELoss = mean over all elements of
 // -(t * max(log p, -100) + (1 - t) * max(log1p(-p), -100)), torch's clamp), as ONE pass over the four fp32 maps.
@@ -103,6 +103,132 @@ __global__ __launch_bounds__(64) void dbloss_finish_kernel(const double* partial
         for (int k = 0; k < 5; ++k) sums[k] = s[k];
 }
 
+// ---- backward (analytic): d{prob BCE, thresh BCE, dice, total} / d{probability, threshold} -------------------------------------------
+// Element-wise, one streaming pass: reads p, t (and theta, theta_t when the threshold gradient is wanted), writes the gradient maps
+// (24 B per pixel position with both maps).  The scalars it needs -- the forward's five fp64 sums and the four upstream gradients --
+// are read from device memory, so backward never waits for the host.  Per element it forms exactly what torch autograd forms on the
+// reference's graph (trainer.py:52-56, DiceLoss :135-142), in the same fp32 operation order:
+//   aten binary_cross_entropy_backward, mean:  ((g * (p - t)) / max((1 - p) * p, 1e-12)) / n
+//   DiceLoss, num = 2I + s, den = P + T + s:   t * (2 * (-g_d / den)) + g_d * ((num / den) / den)
+//   probability gradient = BCE path + Dice path (the two uses of `pred` inside DiceLoss are summed first, as autograd does)
+// with num / den formed from the fp32-rounded sums exactly as dbloss_finish_kernel forms them.  The _rn intrinsics keep the compiler
+// from fusing a multiply into the following add (torch rounds both).
+
+struct DbLossGradParams {
+    const float* prob;
+    const float* thresh;     // read only when grad_thresh is written
+    const float* prob_t;
+    const float* thresh_t;
+    const double* sums;      // [5] the forward's sums
+    const float* grad_out;   // [4] upstream gradients of {prob BCE, thresh BCE, dice, total}
+    float* grad_prob;        // [n] (may be null)
+    float* grad_thresh;      // [n] (may be null)
+    int64_t n;
+    float smooth;
+};
+
+struct DbLossGradScalars {
+    float gp, gt, gd;        // upstream gradients of the prob BCE, the thresh BCE and the dice loss (total's added to each)
+    float dice_a, dice_q;    // 2 * (-g_d / den), g_d * ((num / den) / den)
+    float n;
+};
+
+__device__ __forceinline__ float bce_grad(float g, float p, float t, float n) {
+    // aten: grad * (input - target) / max((1 - input) * input, EPSILON), then grad_input.div_(numel) for the mean
+    return __fdiv_rn(__fdiv_rn(__fmul_rn(g, __fsub_rn(p, t)), fmaxf(__fmul_rn(__fsub_rn(1.0f, p), p), 1e-12f)), n);
+}
+
+__device__ __forceinline__ float prob_grad(const DbLossGradScalars& s, float p, float t) {
+    const float dice = __fadd_rn(__fmul_rn(t, s.dice_a), s.dice_q);
+    return __fadd_rn(bce_grad(s.gp, p, t, s.n), dice);
+}
+
+__global__ __launch_bounds__(DBL_THREADS) void dbloss_backward_kernel(const DbLossGradParams p) {
+    DbLossGradScalars s;
+    {
+        const float g3 = p.grad_out[3];
+        s.gp = p.grad_out[0] + g3;
+        s.gt = p.grad_out[1] + g3;
+        s.gd = p.grad_out[2] + g3;
+        const float inter = (float)p.sums[2], sp = (float)p.sums[3], st = (float)p.sums[4];   // as dbloss_finish_kernel
+        const float num = 2.0f * inter + p.smooth;
+        const float den = sp + st + p.smooth;
+        s.dice_a = 2.0f * __fdiv_rn(-s.gd, den);
+        s.dice_q = __fmul_rn(s.gd, __fdiv_rn(__fdiv_rn(num, den), den));
+        s.n = (float)p.n;
+    }
+    const int64_t n4 = p.n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * DBL_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * DBL_THREADS + threadIdx.x; i < n4; i += stride) {
+        if (p.grad_prob) {
+            const floatx4 a = *(const floatx4*)(p.prob + 4 * i), b = *(const floatx4*)(p.prob_t + 4 * i);
+            floatx4 r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = prob_grad(s, a[e], b[e]);
+            *(floatx4*)(p.grad_prob + 4 * i) = r;
+        }
+        if (p.grad_thresh) {
+            const floatx4 c = *(const floatx4*)(p.thresh + 4 * i), d = *(const floatx4*)(p.thresh_t + 4 * i);
+            floatx4 r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = bce_grad(s.gt, c[e], d[e], s.n);
+            *(floatx4*)(p.grad_thresh + 4 * i) = r;
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < (p.n & 3)) {   // tail: n not a multiple of 4
+        const int64_t i = (n4 << 2) + threadIdx.x;
+        if (p.grad_prob) p.grad_prob[i] = prob_grad(s, p.prob[i], p.prob_t[i]);
+        if (p.grad_thresh) p.grad_thresh[i] = bce_grad(s.gt, p.thresh[i], p.thresh_t[i], s.n);
+    }
+}
+
+// ---- validation counts: {TP, FP, FN, targets not in {0, 1}} of `pred > threshold` against a {0, 1} target, ADDED into int64[4] -------
+// One pass, 8 B per position.  NaN predictions compare false (negative); a NaN target is "not in {0, 1}".  Integer sums: per-lane
+// counters, a shuffle tree per wave, one 64-bit atomic add per counter per workgroup -- order-independent, the same on every run.
+__global__ __launch_bounds__(DBL_THREADS) void binary_counts_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
+                                                                    float threshold, unsigned long long* counts) {
+    unsigned long long c[4] = {0, 0, 0, 0};
+    auto count = [&](float x, float t) {
+        const bool pos = x > threshold;
+        const bool one = t == 1.0f, zero = t == 0.0f;
+        c[0] += (pos && one) ? 1 : 0;
+        c[1] += (pos && zero) ? 1 : 0;
+        c[2] += (!pos && one) ? 1 : 0;
+        c[3] += (one || zero) ? 0 : 1;
+    };
+    const int64_t n4 = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * DBL_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * DBL_THREADS + threadIdx.x; i < n4; i += stride) {
+        const floatx4 a = *(const floatx4*)(pred + 4 * i), b = *(const floatx4*)(target + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) count(a[e], b[e]);
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < (n & 3)) {
+        const int64_t i = (n4 << 2) + threadIdx.x;
+        count(pred[i], target[i]);
+    }
+    __shared__ unsigned long long wsum[DBL_THREADS / 64][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) c[k] += __shfl_down(c[k], off, 64);
+        if (lane == 0) wsum[w][k] = c[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        unsigned long long t = 0;
+        for (int i = 0; i < DBL_THREADS / 64; ++i) t += wsum[i][threadIdx.x];
+        if (t) atomicAdd(counts + threadIdx.x, t);
+    }
+}
+
+// element-wise grid: a function of n only, one workgroup per 4096 positions up to DBL_MAX_BLOCKS (grid-stride beyond)
+int64_t streaming_blocks(int64_t n) {
+    int64_t blocks = (n / 4 + DBL_THREADS * 4 - 1) / (DBL_THREADS * 4);
+    return blocks < 1 ? 1 : (blocks > DBL_MAX_BLOCKS ? DBL_MAX_BLOCKS : blocks);
+}
+
 }  // namespace
 
 int vtd_dbloss_ws_bytes() { return DBL_MAX_BLOCKS * 5 * (int)sizeof(double); }
@@ -119,5 +245,25 @@ int vtd_launch_dbloss(const float* prob, const float* thresh, const float* prob_
     DbLossParams p{prob, thresh, prob_t, thresh_t, workspace, n};
     hipLaunchKernelGGL(dbloss_partial_kernel, dim3((unsigned)blocks), dim3(DBL_THREADS), 0, stream, p);
     hipLaunchKernelGGL(dbloss_finish_kernel, dim3(1), dim3(64), 0, stream, (const double*)workspace, (int)blocks, n, smooth, thresh ? 1 : 0, out4, sums5);
+    return -(int)hipGetLastError();
+}
+
+int vtd_launch_dbloss_backward(const float* prob, const float* thresh, const float* prob_t, const float* thresh_t, int64_t n, float smooth,
+                               const double* sums5, const float* grad_out4, float* grad_prob, float* grad_thresh, hipStream_t stream) {
+    if (!prob || !prob_t || !sums5 || !grad_out4 || n <= 0 || (!grad_prob && !grad_thresh)) return -2711;
+    if ((thresh == nullptr) != (thresh_t == nullptr) || (grad_thresh && !thresh)) return -2711;
+    if (((uintptr_t)prob | (uintptr_t)prob_t | (uintptr_t)thresh | (uintptr_t)thresh_t | (uintptr_t)grad_prob | (uintptr_t)grad_thresh) & 15)
+        return -2712;   // 16-byte loads and stores
+    DbLossGradParams p{prob, thresh, prob_t, thresh_t, sums5, grad_out4, grad_prob, grad_thresh, n, smooth};
+    hipLaunchKernelGGL(dbloss_backward_kernel, dim3((unsigned)streaming_blocks(n)), dim3(DBL_THREADS), 0, stream, p);
+    return -(int)hipGetLastError();
+}
+
+int vtd_launch_binary_counts(const float* pred, const float* target, int64_t n, float threshold, int64_t* counts4, hipStream_t stream) {
+    if (!pred || !target || !counts4 || n <= 0) return -2721;
+    if (((uintptr_t)pred | (uintptr_t)target) & 15) return -2722;
+    if ((uintptr_t)counts4 & 7) return -2722;   // 64-bit atomics
+    hipLaunchKernelGGL(binary_counts_kernel, dim3((unsigned)streaming_blocks(n)), dim3(DBL_THREADS), 0, stream, pred, target, n, threshold,
+                       (unsigned long long*)counts4);
     return -(int)hipGetLastError();
 }

@@ -54,6 +54,9 @@ int vtd_launch_compact_rows(const float* in, float* out, int64_t rows, int V, in
 int vtd_dbloss_ws_bytes();
 int vtd_launch_dbloss(const float* prob, const float* thresh, const float* prob_t, const float* thresh_t, int64_t n, float smooth, double* workspace,
                       float* out4, double* sums5, hipStream_t stream);
+int vtd_launch_dbloss_backward(const float* prob, const float* thresh, const float* prob_t, const float* thresh_t, int64_t n, float smooth,
+                               const double* sums5, const float* grad_out4, float* grad_prob, float* grad_thresh, hipStream_t stream);
+int vtd_launch_binary_counts(const float* pred, const float* target, int64_t n, float threshold, int64_t* counts4, hipStream_t stream);
 
 namespace vtd {
 
@@ -1396,6 +1399,19 @@ int vtd_dbloss_forward(const float* prob_dev, const float* thresh_dev, const flo
     if ((thresh_dev == nullptr) != (thresh_target_dev == nullptr)) return ERR_ARG;
     return vtd_launch_dbloss(prob_dev, thresh_dev, prob_target_dev, thresh_target_dev, numel, smooth, (double*)workspace_dev, out4_dev, sums5_dev,
                              (hipStream_t)stream);
+}
+
+int vtd_dbloss_backward(const float* prob_dev, const float* thresh_dev, const float* prob_target_dev, const float* thresh_target_dev, int64_t numel,
+                        float smooth, const double* sums5_dev, const float* grad_out4_dev, float* grad_prob_dev, float* grad_thresh_dev,
+                        vtd_stream stream) {
+    return vtd_launch_dbloss_backward(prob_dev, thresh_dev, prob_target_dev, thresh_target_dev, numel, smooth, sums5_dev, grad_out4_dev,
+                                      grad_prob_dev, grad_thresh_dev, (hipStream_t)stream);
+}
+
+// ---- validation metrics (trainer.py:83-98): the three integer counts behind sklearn's binary precision / recall / F1
+int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev, int64_t numel, float threshold, int64_t* counts4_dev,
+                                 vtd_stream stream) {
+    return vtd_launch_binary_counts(pred_dev, target_dev, numel, threshold, counts4_dev, (hipStream_t)stream);
 }
 
 int vtd_device_count(void) {
