@@ -617,6 +617,15 @@ struct Fold {
     std::vector<double> scale, shift;  // y = conv*scale + shift
 };
 
+// fp16 weight of a folded double product: rounded to float, then to half, as the fused stem+pool packing (which goes
+// through a float array) and the test references do.  The float is materialised on purpose: written as one expression,
+// the x86 backend may fold the two conversions into a single double -> half rounding, which differs from the two-step
+// one whenever the float lands exactly halfway between two fp16 values (one stem weight of a calibrated checkpoint did).
+static inline half_t half_of(double v) {
+    volatile float f = (float)v;
+    return (half_t)f;
+}
+
 // BatchNorm (eval) folded with an optional conv bias: y = (conv + b - mean) * g/sqrt(var+eps) + beta
 static int fold_bn(const ModelBase* d, const std::string& bn, const std::string& bias_key, int cout, Fold& f) {
     f.scale.assign(cout, 1.0);
@@ -672,7 +681,7 @@ static int build_conv(ModelBase* d, ConvOp& op, const TensorDesc& in, TensorDesc
             for (int r = 0; r < kh; ++r)
                 for (int s = 0; s < kw; ++s)
                     wp[(size_t)co * K + (size_t)(r * kw + s) * cin + c] =
-                        (half_t)(float)((double)(*w)[(((size_t)co * cin + c) * kh + r) * kw + s] * f.scale[co]);
+                        half_of((double)(*w)[(((size_t)co * cin + c) * kh + r) * kw + s] * f.scale[co]);
     std::vector<float> bias(cout_pad, 0.f);
     for (int co = 0; co < cout; ++co) bias[co] = (float)f.shift[co];
     // cin % 64 == 0: a K-step never straddles two taps
@@ -735,7 +744,7 @@ static int build_stem(ModelBase* d, ConvOp& op, const TensorDesc& in, TensorDesc
         for (int c = 0; c < 3; ++c)
             for (int r = 0; r < 7; ++r)
                 for (int s = 0; s < 7; ++s)
-                    wp[(size_t)co * K + r * 32 + s * 4 + c] = (half_t)(float)((double)(*w)[(((size_t)co * 3 + c) * 7 + r) * 7 + s] * f.scale[co]);
+                    wp[(size_t)co * K + r * 32 + s * 4 + c] = half_of((double)(*w)[(((size_t)co * 3 + c) * 7 + r) * 7 + s] * f.scale[co]);
     std::vector<float> bias(64);
     for (int co = 0; co < 64; ++co) bias[co] = (float)f.shift[co];
     // one K-step = two kernel rows of 32 elements (8 taps x 4 ch): chunks 4-7 sit one input row below chunks 0-3
@@ -764,7 +773,7 @@ static int build_convt(ModelBase* d, ConvOp& op, const TensorDesc& in, TensorDes
             const int nrow = blk * cout + co;
             bias[nrow] = (float)f.shift[co];
             for (int ci = 0; ci < cin; ++ci)
-                wp[(size_t)nrow * K + ci] = (half_t)(float)((double)(*w)[((size_t)ci * cout + co) * 4 + blk] * f.scale[co]);
+                wp[(size_t)nrow * K + ci] = half_of((double)(*w)[((size_t)ci * cout + co) * 4 + blk] * f.scale[co]);
         }
     op.cin_steps = K / 64; op.kw = 1; op.s_step = 0; op.r_step = 0; op.k_hi_step = 32;
     int rc;
@@ -887,7 +896,7 @@ static int compose_head_entry(const ModelBase* d, const std::string& hp, int c2c
                         const double sc = f.scale[o];
                         for (int u = 0; u < 25; ++u)
                             for (int k = 0; k < c2ch; ++k)
-                                dst[(size_t)o * K + (size_t)u * c2ch + k] = (half_t)(float)(sc * wc2[((size_t)u * 64 + o) * c2ch + k]);
+                                dst[(size_t)o * K + (size_t)u * c2ch + k] = half_of(sc * wc2[((size_t)u * 64 + o) * c2ch + k]);
                         // L3 part: window offset uy lands on L3 row floor((a+uy)/2) (relative to y>>1), likewise columns
                         std::vector<double> acc((size_t)9 * 256, 0.0);
                         for (int uy = -2; uy <= 2; ++uy)
@@ -899,7 +908,7 @@ static int compose_head_entry(const ModelBase* d, const std::string& hp, int c2c
                             }
                         for (int ij = 0; ij < 9; ++ij)
                             for (int c = 0; c < 256; ++c)
-                                dst[(size_t)o * K + (size_t)25 * c2ch + (size_t)ij * 256 + c] = (half_t)(float)(sc * acc[(size_t)ij * 256 + c]);
+                                dst[(size_t)o * K + (size_t)25 * c2ch + (size_t)ij * 256 + c] = half_of(sc * acc[(size_t)ij * 256 + c]);
                     }
                 }
         }
@@ -1664,7 +1673,7 @@ static int build_recognizer_graph(vtd_recognizer* r) {
             for (int c = 0; c < 3; ++c)
                 for (int rr = 0; rr < 3; ++rr)
                     for (int ss = 0; ss < 3; ++ss)
-                        wp[co * 32 + (rr * 3 + ss) * 3 + c] = (half_t)(float)((double)(*w)[((co * 3 + c) * 3 + rr) * 3 + ss] * f.scale[co]);
+                        wp[co * 32 + (rr * 3 + ss) * 3 + c] = half_of((double)(*w)[((co * 3 + c) * 3 + rr) * 3 + ss] * f.scale[co]);
         }
         if ((rc = upload(r->arena, wp.data(), wp.size() * sizeof(half_t), (void**)&r->w1))) return rc;
         if ((rc = upload(r->arena, bp.data(), bp.size() * 4, (void**)&r->b1))) return rc;

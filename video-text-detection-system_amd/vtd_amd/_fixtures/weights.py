@@ -17,6 +17,7 @@
 """
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from .. import nets
@@ -133,6 +134,76 @@ def margin_detector_state_dict(backbone="resnet18", seed=0, gain=16.0):
         sd[head + "6.bias"][0] = -gain / 2.0
     return sd
 
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Detector stress weights.  seeded_state_dict leaves BN betas at 0 and means near 0, so the probability map of a
+# default-init DBNet sits in [0.45, 0.56] everywhere and a bias-path or channel-order bug moves it by less than the
+# fp16 noise of the probability test.  ``stress_detector_state_dict`` keeps torch's default conv init, then walks the
+# network on seeded text frames and sets every BatchNorm the way _crnn_calibrate does (running statistics = the batch
+# statistics of its input), spread per channel: means shifted by N(0, 0.3) standard deviations, variances scaled by
+# [0.7, 1.4], gamma log-uniform in [0.5, 2], beta ~ N(0, 0.5).  FPN and head conv biases are drawn at the size of the
+# conv's output (N(0, 1) x its per-channel standard deviation), and the last ConvT is scaled so that the logits have a
+# standard deviation of `logit_std` around 0.  Activations stay O(1) (well inside fp16) and the logits span [-4, 4].
+
+def _stress_batch(seed, n=4, size=192):
+    from . import synth
+    frames = [synth.text_frame(9100 + 17 * seed + i, size, size)[0] for i in range(n)]
+    x = torch.from_numpy(np.stack(frames)[..., ::-1].copy()).permute(0, 3, 1, 2).float() / 255.0
+    return (x - torch.tensor(MEAN)[:, None, None]) / torch.tensor(STD)[:, None, None]
+
+
+def stress_detector_state_dict(backbone="resnet18", seed=0, logit_std=3.0):
+    import torch.nn.functional as F
+    sd = nets.seeded_state_dict(lambda: nets.DBNet(backbone), seed)
+    g = torch.Generator().manual_seed(60013 + seed)
+
+    def bn(z, p):
+        c = z.shape[1]
+        mean, std = z.mean((0, 2, 3)), z.std((0, 2, 3)).clamp_min(1e-3)
+        sd[p + ".weight"] = torch.exp(torch.empty(c).uniform_(np.log(0.5), np.log(2.0), generator=g))
+        sd[p + ".bias"] = 0.5 * torch.randn(c, generator=g)
+        sd[p + ".running_mean"] = mean + 0.3 * std * torch.randn(c, generator=g)
+        sd[p + ".running_var"] = std ** 2 * torch.empty(c).uniform_(0.7, 1.4, generator=g)
+        return F.batch_norm(z, sd[p + ".running_mean"], sd[p + ".running_var"], sd[p + ".weight"], sd[p + ".bias"], False, 0.0, 1e-5)
+
+    def bias(z, key):
+        sd[key] = torch.randn(z.shape[1], generator=g) * z.std((0, 2, 3))
+        return z + sd[key][:, None, None]
+
+    r50 = backbone == "resnet50"
+    with torch.no_grad():
+        y = F.relu(bn(F.conv2d(_stress_batch(seed), sd["backbone.0.weight"], None, 2, 3), "backbone.1"))
+        y = F.max_pool2d(y, 3, 2, 1)
+        taps = []
+        for st, n in enumerate((3, 4, 6, 3) if r50 else (2, 2, 2, 2)):
+            for b in range(n):
+                p, stride = f"backbone.{4 + st}.{b}", (2 if b == 0 and st > 0 else 1)
+                idt = y
+                if p + ".downsample.0.weight" in sd:
+                    idt = bn(F.conv2d(y, sd[p + ".downsample.0.weight"], None, stride), p + ".downsample.1")
+                if r50:
+                    t = F.relu(bn(F.conv2d(y, sd[p + ".conv1.weight"]), p + ".bn1"))
+                    t = F.relu(bn(F.conv2d(t, sd[p + ".conv2.weight"], None, stride, 1), p + ".bn2"))
+                    t = bn(F.conv2d(t, sd[p + ".conv3.weight"]), p + ".bn3")
+                else:
+                    t = F.relu(bn(F.conv2d(y, sd[p + ".conv1.weight"], None, stride, 1), p + ".bn1"))
+                    t = bn(F.conv2d(t, sd[p + ".conv2.weight"], None, 1, 1), p + ".bn2")
+                y = F.relu(t + idt)
+            taps.append(y)
+        last = None
+        for i, feat in enumerate(taps[::-1]):
+            lat = bias(F.conv2d(feat, sd[f"fpn.inner_blocks.{i}.weight"]), f"fpn.inner_blocks.{i}.bias")
+            last = lat if last is None else lat + F.interpolate(last, scale_factor=2, mode="nearest")
+        p2 = bias(F.conv2d(last, sd["fpn.layer_blocks.3.weight"], None, 1, 1), "fpn.layer_blocks.3.bias")
+        for head in ("head.probability_head.", "head.threshold_head."):
+            h = F.relu(bn(bias(F.conv2d(p2, sd[head + "0.weight"], None, 1, 1), head + "0.bias"), head + "1"))
+            h = F.relu(bn(bias(F.conv_transpose2d(h, sd[head + "3.weight"], None, 2), head + "3.bias"), head + "4"))
+            logit = F.conv_transpose2d(h, sd[head + "6.weight"], None, 2)
+            k = logit_std / float(logit.std().clamp_min(1e-6))
+            sd[head + "6.weight"] = sd[head + "6.weight"] * k
+            sd[head + "6.bias"] = torch.tensor([-float(logit.mean()) * k])
+    return sd
 
 # ---------------------------------------------------------------------------------------------------------------
 # CRNN fixtures.  With torch's default init the CRNN ignores its input: every conv shrinks the signal while the
