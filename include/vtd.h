@@ -148,6 +148,49 @@ int vtd_dbloss_backward(const float* prob_dev, const float* thresh_dev, const fl
 int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev, int64_t numel, float threshold, int64_t* counts4_dev,
                                  vtd_stream stream);
 
+/* ---- DB head training, forward and backward (text_detector.py:58-86 DBHead, both branches, BatchNorm in train or eval mode) ---------
+ * Fine-tunes the probability and threshold heads over a frozen trunk and FPN: the features are P2 (fpn.layer_blocks.3's output, 256
+ * channels at H x W = 160 x 160 for 640^2 input) in the layout the kernels read, "padded features": ring-padded NHWC fp16
+ * [n][H+2][W+2][256] whose one-pixel ring is zero.  M1 = n H W positions at the head input, M2 = 4 M1 at 2H x 2W.
+ *
+ * vtd_detector_forward_features: trunk + FPN of the current input (vtd_detector_set_input_nchw / _preprocess) up to P2, copied into the
+ * caller-owned padded buffer feats_dev (16-byte aligned) -- a later forward on the handle never touches it, so autograd may keep it.
+ * Needs a handle finalized with "fuse_fpn_head" = 0 (the composed head entry never forms P2): -2801 otherwise.
+ * vtd_dbhead_pack_features: [n][256][H][W] NCHW float32 (dtype 0) or fp16 (dtype 1) -> padded features, ring included; any H, W >= 1.
+ *
+ * Parameters are torch's own tensors, passed as device pointers in PyTorch layouts, float32, contiguous, per branch (0 = probability_head,
+ * 1 = threshold_head; the Sequential index of each is in brackets): conv_w [0] Conv2d [64][256][3][3], conv_b [64], bn1_w / bn1_b /
+ * bn1_mean / bn1_var [1] [64], ct1_w [3] ConvTranspose2d [64 in][64 out][2][2], ct1_b [64], bn2_* [4] [64], ct2_w [6] [64][1][2][2],
+ * ct2_b [1].  Both branches always run (the training loss reads both maps).
+ *
+ * vtd_dbhead_train_forward: DBHead.forward.  Weights are converted to the kernels' fp16 layouts on the device inside the call, so an
+ * in-place optimizer step is seen by the next call.  training = 1: BatchNorm normalises with the batch statistics (biased variance) and
+ * updates bn*_mean / bn*_var in place as torch does (x = (1 - momentum) x + momentum s, unbiased variance for the running value; the
+ * statistics are combined as (count, mean, M2) partials in a fixed order, fp64); training = 0: the running statistics normalise and
+ * nothing is written to them.  prob_dev / thresh_dev: [n][4H][4W] float32.  stats_dev (optional): [4][2][64] float32 = batch mean and
+ * biased variance of BN1, then of BN2 (training = 1), or the running values used (training = 0).  workspace_dev: saved activations,
+ * vtd_dbhead_train_workspace_bytes(n, H, W, 0) bytes, 256-byte aligned; keep it, the features and the two maps for the backward.
+ * vtd_dbhead_train_backward: gradients of every learnable head parameter, both branches, written (not accumulated) as float32 into the
+ * grads struct's pointers (running-statistic entries ignored), given grad_prob_dev / grad_thresh_dev ([n][4H][4W] float32; either may be
+ * null = zero).  training must equal the forward's.  scratch_dev: vtd_dbhead_train_workspace_bytes(n, H, W, 1) bytes.  No gradient is
+ * formed for the features.  Backward GEMM operands are fp16 with an exact power-of-two scale per branch and tensor, chosen from a bound
+ * on max |.| taken in the preceding reduction pass and undone in the fp32 epilogue.  No atomics, shape-only grids: bitwise repeatable.
+ * Errors: -2801 (handle built with the fused head entry), -2802 (argument / shape), -2803 (alignment). */
+typedef struct vtd_dbhead_branch {
+    float *conv_w, *conv_b, *bn1_w, *bn1_b, *bn1_mean, *bn1_var, *ct1_w, *ct1_b, *bn2_w, *bn2_b, *bn2_mean, *bn2_var, *ct2_w, *ct2_b;
+} vtd_dbhead_branch;
+typedef struct vtd_dbhead_params {
+    vtd_dbhead_branch branch[2];
+} vtd_dbhead_params;
+int vtd_detector_forward_features(vtd_detector* d, int n, void* feats_dev, vtd_stream stream);
+int vtd_dbhead_pack_features(const void* x_dev, int dtype, int n, int height, int width, void* feats_dev, vtd_stream stream);
+int64_t vtd_dbhead_train_workspace_bytes(int n, int height, int width, int backward);
+int vtd_dbhead_train_forward(const void* feats_dev, int n, int height, int width, const vtd_dbhead_params* params, int training, float momentum,
+                             float eps, void* workspace_dev, float* prob_dev, float* thresh_dev, float* stats_dev, vtd_stream stream);
+int vtd_dbhead_train_backward(const void* feats_dev, int n, int height, int width, const vtd_dbhead_params* params, int training,
+                              const void* workspace_dev, const float* prob_dev, const float* thresh_dev, const float* grad_prob_dev,
+                              const float* grad_thresh_dev, const vtd_dbhead_params* grads, void* scratch_dev, vtd_stream stream);
+
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */
 int vtd_recognizer_create(int vocab_size, int max_crops, vtd_recognizer** out);

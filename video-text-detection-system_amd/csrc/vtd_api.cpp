@@ -57,6 +57,13 @@ int vtd_launch_dbloss(const float* prob, const float* thresh, const float* prob_
 int vtd_launch_dbloss_backward(const float* prob, const float* thresh, const float* prob_t, const float* thresh_t, int64_t n, float smooth,
                                const double* sums5, const float* grad_out4, float* grad_prob, float* grad_thresh, hipStream_t stream);
 int vtd_launch_binary_counts(const float* pred, const float* target, int64_t n, float threshold, int64_t* counts4, hipStream_t stream);
+int64_t vtd_dbhead_ws_bytes(int n, int H, int W, int backward);
+int vtd_launch_dbhead_pack(const void* x, int dtype, int n, int H, int W, void* feats, hipStream_t s);
+int vtd_launch_dbhead_forward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, float momentum, float eps,
+                              void* ws, float* prob, float* thresh, float* stats_out, hipStream_t s);
+int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
+                               const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
+                               void* scratch, hipStream_t s);
 
 namespace vtd {
 
@@ -569,6 +576,7 @@ struct vtd_detector : vtd::ModelBase {
     bool fuse_stem_pool = true;  // conv7x7/s2 + BN + ReLU + maxpool3x3/s2 in one kernel (the 320x320x64 map is never written)
     bool fuse_fpn_head = true;  // compose FPN lateral(C2) + top-down add + P2 smooth + head conv into one classed conv
     bool fuse_downsample = true;  // a downsample block's 1x1 projection rides in the block's last conv as extra K-steps (attach_second_segment)
+    size_t p2_ops = 0;  // unfused graph: ops up to and including the one that writes P2 (vtd_detector_forward_features)
     // optional per-op HIP-event timing (bench / roofline accounting)
     bool profiling = false;
     int prof_only = -1;  // >= 0: only this launch slot is bracketed with events
@@ -1227,6 +1235,7 @@ static int build_detector_graph(vtd_detector* d) {
         if ((rc = build_conv(d, c, last, p2, "fpn.layer_blocks.3.weight", f, 256, 256, 3, 3, 1, 1, 0))) return rc;
         push_conv(c);
         d->taps["p2"] = p2;
+        d->p2_ops = d->ops.size();
     } else if (!d->get("fpn.inner_blocks.3.weight", (size_t)256 * tapsC[0].c) || !d->get("fpn.layer_blocks.3.weight", (size_t)256 * 256 * 9)) {
         return ERR_MISSING_KEY;
     }
@@ -1389,6 +1398,9 @@ const char* vtd_strerror(int code) {
         case ERR_BATCH: return "batch exceeds the handle's max_batch";
         case ERR_GEOMETRY: return "layer geometry check failed";
         case ERR_CAPACITY: return "output capacity too small";
+        case -2801: return "feature export needs a detector finalized with fuse_fpn_head=0 (the fused head entry never forms P2)";
+        case -2802: return "DB head training: invalid argument or shape";
+        case -2803: return "DB head training: misaligned buffer";
         default: break;
     }
     if (code <= -1000) {
@@ -1421,6 +1433,26 @@ int vtd_dbloss_backward(const float* prob_dev, const float* thresh_dev, const fl
 int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev, int64_t numel, float threshold, int64_t* counts4_dev,
                                  vtd_stream stream) {
     return vtd_launch_binary_counts(pred_dev, target_dev, numel, threshold, counts4_dev, (hipStream_t)stream);
+}
+
+// ---- DB head training (dbhead_train.hip)
+int vtd_dbhead_pack_features(const void* x_dev, int dtype, int n, int height, int width, void* feats_dev, vtd_stream stream) {
+    return vtd_launch_dbhead_pack(x_dev, dtype, n, height, width, feats_dev, (hipStream_t)stream);
+}
+
+int64_t vtd_dbhead_train_workspace_bytes(int n, int height, int width, int backward) { return vtd_dbhead_ws_bytes(n, height, width, backward); }
+
+int vtd_dbhead_train_forward(const void* feats_dev, int n, int height, int width, const vtd_dbhead_params* params, int training, float momentum,
+                             float eps, void* workspace_dev, float* prob_dev, float* thresh_dev, float* stats_dev, vtd_stream stream) {
+    return vtd_launch_dbhead_forward(feats_dev, n, height, width, params, training, momentum, eps, workspace_dev, prob_dev, thresh_dev, stats_dev,
+                                     (hipStream_t)stream);
+}
+
+int vtd_dbhead_train_backward(const void* feats_dev, int n, int height, int width, const vtd_dbhead_params* params, int training,
+                              const void* workspace_dev, const float* prob_dev, const float* thresh_dev, const float* grad_prob_dev,
+                              const float* grad_thresh_dev, const vtd_dbhead_params* grads, void* scratch_dev, vtd_stream stream) {
+    return vtd_launch_dbhead_backward(feats_dev, n, height, width, params, training, workspace_dev, prob_dev, thresh_dev, grad_prob_dev,
+                                      grad_thresh_dev, grads, scratch_dev, (hipStream_t)stream);
 }
 
 int vtd_device_count(void) {
@@ -1490,11 +1522,8 @@ int vtd_detector_set_input_nchw(vtd_detector* d, const float* x_dev, int n, vtd_
     return vtd_launch_nchw_to_input(x_dev, d->input.ptr, n, (hipStream_t)stream);
 }
 
-int vtd_detector_forward(vtd_detector* d, int n, float* prob_dev, float* thresh_dev, vtd_stream stream) {
-    if (!d || !prob_dev) return ERR_ARG;
-    if (!d->finalized) return ERR_NOT_FINALIZED;
-    if (n <= 0 || n > d->max_batch) return ERR_BATCH;
-    hipStream_t s = (hipStream_t)stream;
+// the graph's launches [0, op_end) for n frames of the current input
+static int run_detector_ops(vtd_detector* d, int n, float* prob_dev, float* thresh_dev, hipStream_t s, size_t op_end) {
     float* outs[2] = {prob_dev, thresh_dev};
     // kernel choice per power-of-two batch bucket (1, 2, 4, ... max_batch), decided at the bucket's own size
     const int bucket = batch_bucket(n, d->max_batch);
@@ -1509,7 +1538,7 @@ int vtd_detector_forward(vtd_detector* d, int n, float* prob_dev, float* thresh_
         tit = d->tuned.emplace(bucket, std::move(cfgs)).first;
     }
     const std::vector<int>& cfgs = tit->second;
-    for (size_t oi = 0; oi < d->ops.size(); ++oi) {
+    for (size_t oi = 0; oi < op_end; ++oi) {
         const Op& o = d->ops[oi];
         int rc = 0;
         if (o.final_slot == 1 && !thresh_dev) continue;
@@ -1540,6 +1569,28 @@ int vtd_detector_forward(vtd_detector* d, int n, float* prob_dev, float* thresh_
             d->prof_macs[oi] += (o.kind != Op::POOL) ? (double)o.conv.macs_per_image * n : 0.0;
         }
     }
+    return 0;
+}
+
+int vtd_detector_forward(vtd_detector* d, int n, float* prob_dev, float* thresh_dev, vtd_stream stream) {
+    if (!d || !prob_dev) return ERR_ARG;
+    if (!d->finalized) return ERR_NOT_FINALIZED;
+    if (n <= 0 || n > d->max_batch) return ERR_BATCH;
+    return run_detector_ops(d, n, prob_dev, thresh_dev, (hipStream_t)stream, d->ops.size());
+}
+
+// trunk + FPN up to P2, then a copy of the n frames' ring-padded P2 into the caller's buffer (same layout: [n][162][162][256] fp16)
+int vtd_detector_forward_features(vtd_detector* d, int n, void* feats_dev, vtd_stream stream) {
+    if (!d || !feats_dev) return ERR_ARG;
+    if (!d->finalized) return ERR_NOT_FINALIZED;
+    if (n <= 0 || n > d->max_batch) return ERR_BATCH;
+    if (d->fuse_fpn_head || !d->p2_ops || !d->taps.count("p2")) return -2801;
+    if ((uintptr_t)feats_dev & 15) return -2803;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_detector_ops(d, n, nullptr, nullptr, s, d->p2_ops);
+    if (rc) return rc;
+    const TensorDesc& p2 = d->taps["p2"];
+    VTD_HIP_CHECK(hipMemcpyAsync(feats_dev, p2.ptr, (size_t)n * p2.hp * p2.wp * p2.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

@@ -33,6 +33,16 @@ class Detection(C.Structure):
                 ("first_x", C.c_int32), ("first_y", C.c_int32)]
 
 
+class DbHeadBranch(C.Structure):
+    """vtd_dbhead_branch of include/vtd.h: device pointers to one DB-head branch's fp32 tensors, PyTorch layouts"""
+    _fields_ = [(k, C.c_void_p) for k in ("conv_w", "conv_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "ct1_w", "ct1_b", "bn2_w", "bn2_b",
+                                          "bn2_mean", "bn2_var", "ct2_w", "ct2_b")]
+
+
+class DbHeadParams(C.Structure):
+    _fields_ = [("branch", DbHeadBranch * 2)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vtd.h
 SIGNATURES = {
     "vtd_version": (C.c_char_p, []),
@@ -92,6 +102,13 @@ SIGNATURES = {
                                      C.c_void_p]),
     "vtd_dbloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "vtd_detector_forward_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_dbhead_pack_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_dbhead_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtd_dbhead_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DbHeadParams), C.c_int, C.c_float, C.c_float,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_dbhead_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DbHeadParams), C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DbHeadParams), C.c_void_p, C.c_void_p]),
     "vtd_binary_counts_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "vtd_trocr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vtd_trocr_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),

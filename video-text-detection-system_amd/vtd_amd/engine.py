@@ -217,6 +217,17 @@ class DetectorEngine(_Tunable):
             del keep
             return {"probability": prob, "threshold": thr}
 
+    def forward_features(self, x):
+        """P2 (fpn.layer_blocks.3's output) of the input as a new padded-features tensor, ring-padded NHWC fp16 [n,162,162,256] (the
+        layout the DB-head training kernels read; include/vtd.h vtd_detector_forward_features).  Needs options fuse_fpn_head=0."""
+        with self.lock:
+            n, keep = self._set_input(x)
+            feats = torch.empty((n, 162, 162, 256), dtype=torch.float16, device="cuda")
+            _native.check(self.lib.vtd_detector_forward_features(self.handle, n, C.c_void_p(feats.data_ptr()), _stream_ptr()),
+                          "vtd_detector_forward_features")
+            del keep
+            return feats
+
     def read_tap(self, name, n):
         shapes = {"input": (3, 640, 640), "stem": (64, 320, 320), "pool": (64, 160, 160), "p2": (256, 160, 160), "head1": (64, 160, 160),
                   "head2": (64, 320, 320)}

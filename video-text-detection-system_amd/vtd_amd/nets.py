@@ -18,6 +18,7 @@ import threading
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 
 def _conv_bn(cin, cout, k, stride, pad):
@@ -103,11 +104,150 @@ def _db_branch(c):
         nn.ConvTranspose2d(q, 1, 2, stride=2), nn.Sigmoid())
 
 
+# per-branch tensors of the HIP training kernels (include/vtd.h vtd_dbhead_branch): (field, Sequential index, attribute)
+_HEAD_FIELDS = (("conv_w", 0, "weight"), ("conv_b", 0, "bias"), ("bn1_w", 1, "weight"), ("bn1_b", 1, "bias"),
+                ("bn1_mean", 1, "running_mean"), ("bn1_var", 1, "running_var"), ("ct1_w", 3, "weight"), ("ct1_b", 3, "bias"),
+                ("bn2_w", 4, "weight"), ("bn2_b", 4, "bias"), ("bn2_mean", 4, "running_mean"), ("bn2_var", 4, "running_var"),
+                ("ct2_w", 6, "weight"), ("ct2_b", 6, "bias"))
+_HEAD_LEARNABLE = tuple(f for f in _HEAD_FIELDS if not f[2].startswith("running"))   # 10 per branch
+_HEAD_BUFFERS = tuple(f for f in _HEAD_FIELDS if f[2].startswith("running"))
+
+
+def _head_struct(tensors):
+    """vtd_dbhead_params over a {(branch, field): tensor} mapping (missing fields stay NULL)."""
+    import ctypes as C
+    from . import _native
+    st = _native.DbHeadParams()
+    for (b, field), t in tensors.items():
+        setattr(st.branch[b], field, C.c_void_p(t.data_ptr()))
+    return st
+
+
+class _DBHeadTrainFn(torch.autograd.Function):
+    """DBHead.forward on the HIP training kernels (csrc/dbhead_train.hip), differentiable w.r.t. the 20 learnable head tensors.  Inputs:
+    padded features (include/vtd.h), (H, W), BatchNorm mode / momentum / eps, the four running-stat buffers per branch (updated in place
+    in training mode), then the learnable tensors branch-major in _HEAD_LEARNABLE order."""
+
+    @staticmethod
+    def forward(ctx, feats, hw, training, momentum, eps, buffers, *params):
+        import ctypes as C
+        from . import _native
+        lib = _native.require()
+        n, (H, W) = feats.shape[0], hw
+        tensors = {}
+        for b in range(2):
+            for i, (field, _, _) in enumerate(_HEAD_LEARNABLE):
+                tensors[(b, field)] = params[b * len(_HEAD_LEARNABLE) + i]
+            for i, (field, _, _) in enumerate(_HEAD_BUFFERS):
+                tensors[(b, field)] = buffers[b * len(_HEAD_BUFFERS) + i]
+        st = _head_struct(tensors)
+        dev = feats.device
+        ws = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 0)), dtype=torch.uint8, device=dev)
+        prob = torch.empty((n, 1, 4 * H, 4 * W), dtype=torch.float32, device=dev)
+        thresh = torch.empty_like(prob)
+        stats = torch.empty((4, 2, 64), dtype=torch.float32, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        _native.check(lib.vtd_dbhead_train_forward(ptr(feats), n, H, W, C.byref(st), 1 if training else 0, float(momentum), float(eps), ptr(ws),
+                                                   ptr(prob), ptr(thresh), ptr(stats), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                      "vtd_dbhead_train_forward")
+        ctx.save_for_backward(feats, prob, thresh, *params)
+        ctx.ws, ctx.hw, ctx.training = ws, (H, W), bool(training)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        import ctypes as C
+        from . import _native
+        lib = _native.require()
+        feats, prob, thresh, *params = ctx.saved_tensors
+        n, (H, W) = feats.shape[0], ctx.hw
+        grads = [torch.empty_like(p) for p in params]
+        tensors, gtensors = {}, {}
+        for b in range(2):
+            for i, (field, _, _) in enumerate(_HEAD_LEARNABLE):
+                tensors[(b, field)] = params[b * len(_HEAD_LEARNABLE) + i]
+                gtensors[(b, field)] = grads[b * len(_HEAD_LEARNABLE) + i]
+        st, gst = _head_struct(tensors), _head_struct(gtensors)
+        scratch = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 1)), dtype=torch.uint8, device=feats.device)
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (grad_prob, grad_thresh)]
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        _native.check(lib.vtd_dbhead_train_backward(ptr(feats), n, H, W, C.byref(st), 1 if ctx.training else 0, ptr(ctx.ws), ptr(prob),
+                                                    ptr(thresh), ptr(g[0]), ptr(g[1]), C.byref(gst), ptr(scratch),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_dbhead_train_backward")
+        return (None, None, None, None, None, None, *grads)
+
+
+def pack_features(features):
+    """[n,256,H,W] float32 / float16 CUDA tensor -> padded features (ring-padded NHWC fp16 [n,H+2,W+2,256]) on the device."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    x = features.detach()
+    if x.dtype not in (torch.float32, torch.float16):
+        x = x.float()
+    x = x.contiguous()
+    n, _, H, W = x.shape
+    out = torch.empty((n, H + 2, W + 2, 256), dtype=torch.float16, device=x.device)
+    _native.check(lib.vtd_dbhead_pack_features(C.c_void_p(x.data_ptr()), 0 if x.dtype == torch.float32 else 1, n, H, W,
+                                               C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "vtd_dbhead_pack_features")
+    return out
+
+
 class DBHead(nn.Module):
+    """DBHead (text_detector.py:58-86).  ``head(features)`` on a CUDA ``[n,256,H,W]`` tensor returns ``{'probability', 'threshold'}``
+    (``[n,1,4H,4W]`` fp32) from the HIP training kernels, with torch's BatchNorm semantics in ``train()`` (batch statistics, running
+    statistics updated, ``num_batches_tracked`` + 1) and ``eval()``, differentiable w.r.t. the head's parameters.  No gradient flows into
+    the features: a ``features`` tensor that requires grad is refused."""
+
     def __init__(self, in_channels):
         super().__init__()
+        self.in_channels = in_channels
         self.probability_head = _db_branch(in_channels)
         self.threshold_head = _db_branch(in_channels)
+
+    def _branches(self):
+        return (self.probability_head, self.threshold_head)
+
+    def forward(self, features):
+        if not torch.is_tensor(features) or features.dim() != 4 or features.shape[1] != self.in_channels:
+            raise ValueError(f"DBHead input must be a [n,{self.in_channels},H,W] tensor")
+        if features.requires_grad:
+            raise RuntimeError("DBHead: the features require grad, but backward into the features (dgrad into P2, i.e. through the "
+                               "FPN / trunk) is not implemented; pass features.detach()")
+        if not features.is_cuda:
+            raise ValueError("DBHead runs on the HIP kernels: features must be a CUDA (HIP) tensor")
+        return self.forward_padded(pack_features(features), features.shape[2], features.shape[3])
+
+    def forward_padded(self, feats, H, W):
+        """The head on padded features (ring-padded NHWC fp16 [n,H+2,W+2,256], e.g. DetectorEngine.forward_features)."""
+        if self.in_channels != 256:
+            raise ValueError("the HIP DB-head kernels are specialised for 256 input channels")
+        H, W = int(H), int(W)
+        # the kernels trust the buffer's extent: a mismatch here would be a device-side out-of-bounds read
+        if (not torch.is_tensor(feats) or not feats.is_cuda or feats.dtype != torch.float16 or not feats.is_contiguous() or feats.dim() != 4
+                or H < 1 or W < 1 or feats.shape[0] < 1 or tuple(feats.shape[1:]) != (H + 2, W + 2, 256)):
+            raise ValueError(f"padded features must be a contiguous float16 CUDA tensor [n,{H + 2},{W + 2},256] (H={H}, W={W}), got "
+                             f"{tuple(feats.shape) if torch.is_tensor(feats) else type(feats).__name__}")
+        bns = [seq[i] for seq in self._branches() for i in (1, 4)]
+        if any(bn.momentum is None or bn.momentum != bns[0].momentum or bn.eps != bns[0].eps or not bn.track_running_stats for bn in bns):
+            raise ValueError("the HIP DB-head kernels need one fixed momentum and eps on all four BatchNorms, with running stats tracked")
+        params, buffers = [], []
+        for seq in self._branches():
+            params += [getattr(seq[i], a) for _, i, a in _HEAD_LEARNABLE]
+            buffers += [getattr(seq[i], a) for _, i, a in _HEAD_BUFFERS]
+        for t in params + buffers:
+            if not t.is_cuda or t.device != feats.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("DBHead parameters and buffers must be contiguous float32 CUDA tensors on the features' device "
+                                 "(call .cuda() on the model)")
+        prob, thresh, _ = _DBHeadTrainFn.apply(feats, (int(H), int(W)), self.training, bns[0].momentum, bns[0].eps, tuple(buffers), *params)
+        if self.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
 
 
 class _EngineOwner:
@@ -163,7 +303,7 @@ class DBNet(_EngineOwner, nn.Module):
     ``{'probability': [B,1,640,640] f32 cuda tensor, 'threshold': same or None}``.
     """
 
-    def __init__(self, backbone="resnet50", pretrained=False, compute_threshold=False):
+    def __init__(self, backbone="resnet50", pretrained=False, compute_threshold=False, trainable=None):
         super().__init__()
         if backbone not in _PLANS:
             raise ValueError(f"unknown backbone {backbone!r}; expected one of {sorted(_PLANS)}")
@@ -175,6 +315,42 @@ class DBNet(_EngineOwner, nn.Module):
         # (text_detector.py:128); off by default, same kernels when switched on
         self.compute_threshold = compute_threshold
         self._init_engine_state()
+        self.trainable = None
+        self.set_trainable(trainable)
+
+    def set_trainable(self, trainable):
+        """None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
+        FPN -- their parameters stop requiring grad, and a forward in train mode runs trunk + FPN on a separate features engine (built
+        with fuse_fpn_head=0, rebuilt only when trunk / FPN weights change) and the head on the HIP training kernels, differentiable
+        w.r.t. the head's parameters.  eval() forwards keep the fused inference engine, rebuilt after head updates."""
+        if trainable not in (None, "head"):
+            raise ValueError(f"trainable must be None or 'head', got {trainable!r}")
+        self.trainable = trainable
+        if trainable == "head":
+            for p in list(self.backbone.parameters()) + list(self.fpn.parameters()):
+                p.requires_grad_(False)
+        self._head_versions = None
+        return self
+
+    def _head_tensor_versions(self):
+        return tuple(t._version for t in list(self.head.parameters()) + list(self.head.buffers()))
+
+    def features_engine(self):
+        """The trunk + FPN engine of the trainable path (options fuse_fpn_head=0, see engine.DetectorEngine.forward_features)."""
+        from . import engine as _e
+        with self._engine_lock:
+            # keyed on the trunk / FPN tensors' versions only (load_state_dict bumps them): head updates never rebuild it
+            version = tuple(t._version for t in list(self.backbone.state_dict().values()) + list(self.fpn.state_dict().values()))
+            fe = self.__dict__.get("_features_engine")
+            if fe is None or self.__dict__.get("_features_version") != version:
+                fe = _e.DetectorEngine(self.backbone_name, self.state_dict(), getattr(self, "_max_batch", None), options={"fuse_fpn_head": 0})
+                self._features_engine, self._features_version = fe, version
+            return fe
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state["_features_engine"] = None
+        return state
 
     def engine(self):
         """The native engine for the current parameters, built once under a lock (detect() is entered from four pool threads,
@@ -193,7 +369,29 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
+        if self.trainable == "head":
+            if self.training:
+                return self._forward_train_head(x)
+            # the inference engine packs the head on the host: rebuild it after an optimizer step (parameter versions) or a
+            # train-mode forward (running statistics, mark_dirty)
+            versions = self._head_tensor_versions()
+            if versions != self._head_versions:
+                self._head_versions = versions
+                self.mark_dirty()
         return self.engine().forward(x, want_threshold=self.compute_threshold)
+
+    def _forward_train_head(self, x):
+        frozen = [n for n, p in list(self.backbone.named_parameters(prefix="backbone")) + list(self.fpn.named_parameters(prefix="fpn"))
+                  if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head'): {frozen[0]} requires grad, but backward through the trunk / FPN is not "
+                               "implemented; only the DB head trains (set requires_grad_(False) on backbone and fpn)")
+        if not next(self.head.parameters()).is_cuda:
+            self.head.cuda()   # the head's own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        feats = self.features_engine().forward_features(x)   # a new tensor per call: autograd may keep it
+        out = self.head.forward_padded(feats, 160, 160)
+        self.mark_dirty()   # the kernels updated the running statistics in place
+        return out
 
 
 class CRNN(_EngineOwner, nn.Module):
