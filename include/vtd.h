@@ -149,7 +149,7 @@ int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev,
                                  vtd_stream stream);
 
 /* ---- DB head training, forward and backward (text_detector.py:58-86 DBHead, both branches, BatchNorm in train or eval mode) ---------
- * Fine-tunes the probability and threshold heads over a frozen trunk and FPN: the features are P2 (fpn.layer_blocks.3's output, 256
+ * Fine-tunes the probability and threshold heads over a frozen trunk and FPN, and forms the gradient of the head's input: the features are P2 (fpn.layer_blocks.3's output, 256
  * channels at H x W = 160 x 160 for 640^2 input) in the layout the kernels read, "padded features": ring-padded NHWC fp16
  * [n][H+2][W+2][256] whose one-pixel ring is zero.  M1 = n H W positions at the head input, M2 = 4 M1 at 2H x 2W.
  *
@@ -172,9 +172,16 @@ int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev,
  * vtd_dbhead_train_workspace_bytes(n, H, W, 0) bytes, 256-byte aligned; keep it, the features and the two maps for the backward.
  * vtd_dbhead_train_backward: gradients of every learnable head parameter, both branches, written (not accumulated) as float32 into the
  * grads struct's pointers (running-statistic entries ignored), given grad_prob_dev / grad_thresh_dev ([n][4H][4W] float32; either may be
- * null = zero).  training must equal the forward's.  scratch_dev: vtd_dbhead_train_workspace_bytes(n, H, W, 1) bytes.  No gradient is
- * formed for the features.  Backward GEMM operands are fp16 with an exact power-of-two scale per branch and tensor, chosen from a bound
+ * null = zero).  training must equal the forward's.  scratch_dev: vtd_dbhead_train_workspace_bytes(n, H, W, 1) bytes, or (n, H, W, 2) when
+ * vtd_dbhead_train_backward_input follows.  This call forms no gradient for the features.  Backward GEMM operands are fp16 with an exact power-of-two scale per branch and tensor, chosen from a bound
  * on max |.| taken in the preceding reduction pass and undone in the fp32 epilogue.  No atomics, shape-only grids: bitwise repeatable.
+ * vtd_dbhead_train_backward_input: the gradient of the features (dgrad into P2), dP2 = conv3x3^T(dy1) summed over both branches as one
+ * implicit GEMM (K = 9 x 128, N = 256).  Call it after vtd_dbhead_train_backward on the same stream with the same n, H, W and the same
+ * scratch_dev, which must then hold vtd_dbhead_train_workspace_bytes(n, H, W, 2) bytes (mode 2 = mode 1 plus this call's buffers; the
+ * backward's results and bits do not depend on which of the two sizes it was given).  params: only the two conv_w are read.  dfeats_dev:
+ * [n][H][W][256] float32 (NHWC, 16-byte aligned) = dP2 times dscale_dev[0]; dscale_dev: float32[2] (8-byte aligned) = {scale, 1 / scale},
+ * an exact power of two: the smaller of the two branches' dy1 scales (the other branch's ratio is folded into its packed weights).
+ * vtd_dbhead_unpack_input_grad: dfeats_dev / dscale_dev -> the gradient in torch's layout, [n][256][H][W] float32, scale undone.
  * Errors: -2801 (handle built with the fused head entry), -2802 (argument / shape), -2803 (alignment). */
 typedef struct vtd_dbhead_branch {
     float *conv_w, *conv_b, *bn1_w, *bn1_b, *bn1_mean, *bn1_var, *ct1_w, *ct1_b, *bn2_w, *bn2_b, *bn2_mean, *bn2_var, *ct2_w, *ct2_b;
@@ -190,6 +197,10 @@ int vtd_dbhead_train_forward(const void* feats_dev, int n, int height, int width
 int vtd_dbhead_train_backward(const void* feats_dev, int n, int height, int width, const vtd_dbhead_params* params, int training,
                               const void* workspace_dev, const float* prob_dev, const float* thresh_dev, const float* grad_prob_dev,
                               const float* grad_thresh_dev, const vtd_dbhead_params* grads, void* scratch_dev, vtd_stream stream);
+int vtd_dbhead_train_backward_input(int n, int height, int width, const vtd_dbhead_params* params, void* scratch_dev, float* dfeats_dev,
+                                    float* dscale_dev, vtd_stream stream);
+int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_dev, int n, int height, int width, float* grad_nchw_dev,
+                                 vtd_stream stream);
 
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */

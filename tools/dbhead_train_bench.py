@@ -2,9 +2,10 @@
 kernels (csrc/dbhead_train.hip through vtd_amd.nets.DBHead) against torch eager autograd of the same head on the same GPU, in fp32 and
 under torch.autocast(float16).  The upstream map gradients are fixed tensors of ~1e-7 (the loss gradient's size at this batch), so only
 the head is timed.  HIP events around `--iters` steps after `--warmup`; per-launch times of one step from torch.profiler.  Prints one
-JSON line.
+JSON line.  `--input-grad` adds the gradient of the features on both sides (dgrad into P2: `head(features, input_grad=True)`, which also
+packs the NCHW features and unpacks their gradient inside the step; torch with `features.requires_grad`).
 
-    python tools/dbhead_train_bench.py [--batch 32] [--iters 20] [--warmup 5]
+    python tools/dbhead_train_bench.py [--batch 32] [--iters 20] [--warmup 5] [--input-grad]
 """
 import argparse
 import copy
@@ -62,7 +63,7 @@ def _clean(names):
 
 
 # the conv_igemm launches of one step, in launch order (vtd_launch_dbhead_forward / _backward)
-CONV_LABELS = ["conv3x3_forward", "convt1_forward_b0", "convt1_forward_b1", "convt1_dgrad_b0", "convt1_dgrad_b1"]
+CONV_LABELS = ["conv3x3_forward", "convt1_forward_b0", "convt1_forward_b1", "convt1_dgrad_b0", "convt1_dgrad_b1", "conv3x3_dgrad"]
 
 
 def per_launch(fn):
@@ -88,6 +89,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--input-grad", action="store_true")
     args = ap.parse_args()
     n, H, W = args.batch, 160, 160
     torch.manual_seed(0)
@@ -101,9 +103,13 @@ def main():
     gp = torch.randn((n, 1, 4 * H, 4 * W), generator=g, device="cuda") * 1e-7
     gt = torch.randn((n, 1, 4 * H, 4 * W), generator=g, device="cuda") * 1e-7
 
+    if args.input_grad:
+        feats.requires_grad_(True)
+
     def hip_step():
         head.zero_grad(set_to_none=True)
-        out = head.forward_padded(padded, H, W)
+        feats.grad = None
+        out = head(feats, input_grad=True) if args.input_grad else head.forward_padded(padded, H, W)
         torch.autograd.backward([out["probability"], out["threshold"]], [gp, gt])
 
     def hip_fwd():
@@ -112,15 +118,17 @@ def main():
 
     def torch_step():
         ref.zero_grad(set_to_none=True)
+        feats.grad = None
         torch.autograd.backward([ref.probability_head(feats), ref.threshold_head(feats)], [gp, gt])
 
     def torch_autocast_step():
         ref.zero_grad(set_to_none=True)
+        feats.grad = None
         with torch.autocast("cuda", dtype=torch.float16):
             p, t = ref.probability_head(feats), ref.threshold_head(feats)
         torch.autograd.backward([p, t], [gp.to(p.dtype), gt.to(t.dtype)])
 
-    res = {"batch": n, "features": [256, H, W]}
+    res = {"batch": n, "features": [256, H, W], "input_grad": bool(args.input_grad)}
     res["hip_step_ms"] = round(timed(hip_step, args.iters, args.warmup), 3)
     res["hip_forward_ms"] = round(timed(hip_fwd, args.iters, args.warmup), 3)
     res["torch_fp32_step_ms"] = round(timed(torch_step, args.iters, args.warmup), 3)
@@ -138,6 +146,8 @@ def main():
     tf = {}
     if t.get("conv3x3_forward"):
         tf["conv3x3_forward"] = conv_flop / (t["conv3x3_forward"] * 1e-6) / 1e12
+    if t.get("conv3x3_dgrad"):
+        tf["conv3x3_dgrad"] = 2.0 * M1 * 256 * 1152 / (t["conv3x3_dgrad"] * 1e-6) / 1e12   # K = 9 x 128, N = 256: 483 GFLOP at B = 32
     wg = [k for k in t if k.startswith("dbhead_train_wgrad_kernel<0>")]
     if wg:
         tf["conv3x3_wgrad"] = conv_flop / (t[wg[0]] * 1e-6) / 1e12
@@ -155,7 +165,9 @@ def main():
     bytes_ = {"dbhead_train_stats_partial_kernel<float>": M1 * 128 * 4, "dbhead_train_stats_partial_kernel<_Float16>": M2 * 128 * 2,
               "dbhead_train_bn_relu_kernel": M1 * 128 * 8, "dbhead_train_convt2_sigmoid_kernel": M2 * 128 * 2 + 32 * M2,
               "dbhead_train_bwd_reduce_kernel<2>": M2 * 128 * 2 + 64 * M2, "dbhead_train_bwd_form_kernel<2>": M2 * 128 * 4 + 64 * M2,
-              "dbhead_train_bwd_reduce_kernel<1>": M1 * 128 * 8, "dbhead_train_bwd_form_kernel<1>": M1 * 128 * 10}
+              "dbhead_train_bwd_reduce_kernel<1>": M1 * 128 * 8, "dbhead_train_bwd_form_kernel<1>": M1 * 128 * 10,
+              "dbhead_train_pad_dy1_kernel": M1 * 128 * 2 + n * (H + 2) * (W + 2) * 128 * 2,
+              "dbhead_train_unpack_input_grad_kernel": M1 * 256 * 8, "dbhead_train_pack_features_kernel<float>": M1 * 256 * 6}
     res["hbm_tb_per_s"] = {k: round(b / (t[k] * 1e-6) / 1e12, 2) for k, b in bytes_.items() if t.get(k)}
     res["speedup_vs_torch_fp32"] = round(res["torch_fp32_step_ms"] / res["hip_step_ms"], 2)
     res["speedup_vs_torch_autocast"] = round(res["torch_autocast_fp16_step_ms"] / res["hip_step_ms"], 2)

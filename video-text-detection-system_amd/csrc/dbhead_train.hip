@@ -23,6 +23,12 @@
 //   bwd_reduce<1>, bwd_finish<1>, bwd_form<1>: the same three steps for BN1 -> dy1 fp16 [M1][128] (scaled) + the conv bias gradient
 //   wgrad<0>         conv 3x3 weight gradient  dW[128][2304] = sum_m dy1[m]^T im2col(x)[m], split over M into slabs
 //   wgrad_reduce     the slabs summed in slab order, the scale undone, written in torch's layout
+// Input gradient (optional, a call of its own after the backward, on the same scratch; the steps above are untouched by it):
+//   pack_dgrad       the 3x3 weights, taps rotated by 180 degrees and transposed, both branches along K: [256][9 * 128] fp16; the two
+//                    branches' dy1 carry different power-of-two scales, so the branch with the larger one has the ratio folded into its
+//                    weights (a power of two <= 1: exact) and one GEMM sums both at the common (smaller) scale
+//   pad_dy1          dy1 [M1][128] -> ring-padded [n][H+2][W+2][128], ring zeroed (the layout a 3x3 window reads)
+//   conv 3x3         dP2 = conv3x3^T(dy1) as ONE implicit GEMM (conv_igemm.hip, K = 1152, N = 256) -> fp32 [M1][256], scaled
 // Every reduction has a grid that depends on the shape only and a fixed summation order, and no atomics: bitwise repeatable.
 #include "vtd_common.h"
 #include "../../include/vtd.h"
@@ -68,6 +74,11 @@ struct BwdLayout {
     int64_t dz, da1, dy1, coef2, coef1, part, bpart, slab, total;
 };
 
+// the input gradient's scratch, behind the backward's (mode 2 of the size query)
+struct DgradLayout {
+    int64_t dy1p, wd3, zero, total;
+};
+
 FwdLayout fwd_layout(int n, int H, int W) {
     FwdLayout L;
     const int64_t M1 = (int64_t)n * H * W, M2 = 4 * M1;
@@ -96,12 +107,23 @@ BwdLayout bwd_layout(int n, int H, int W) {
     L.dz = take(M2 * 128 * 2);
     L.da1 = take(M1 * 128 * 4);
     L.dy1 = take(M1 * 128 * 2);
-    L.coef2 = take((3 * 128 + 4) * 4);   // k[128], mean dz'[128], mean dz'x^[128], scale[2], 1/scale[2]
-    L.coef1 = take((3 * 128 + 4) * 4);
+    L.coef2 = take((3 * 128 + 6) * 4);   // k[128], mean dz'[128], mean dz'x^[128], scale[2], 1/scale[2], live[2]
+    L.coef1 = take((3 * 128 + 6) * 4);
     L.part = take((int64_t)DHT_MAX_RED_BLOCKS * 128 * DHT_RED_VALS * 8);
     L.bpart = take((int64_t)DHT_MAX_RED_BLOCKS * 128 * 8);
     const int64_t s0 = (int64_t)wgrad_slabs(M1, 0) * 128 * 2304 * 4, s1 = (int64_t)wgrad_slabs(M1, 1) * 2 * 64 * 256 * 4;
     L.slab = take(s0 > s1 ? s0 : s1);
+    L.total = o;
+    return L;
+}
+
+DgradLayout dgrad_layout(int n, int H, int W) {
+    DgradLayout L;
+    int64_t o = bwd_layout(n, H, W).total;
+    auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
+    L.dy1p = take((int64_t)n * (H + 2) * (W + 2) * 128 * 2);
+    L.wd3 = take((int64_t)256 * 1152 * 2);
+    L.zero = take(256 * 4);
     L.total = o;
     return L;
 }
@@ -437,7 +459,7 @@ __global__ __launch_bounds__(DHT_THREADS) void dbhead_train_bwd_reduce_kernel(co
 // One thread per channel: partials in workgroup order; gradients of this BN's gamma / beta (and of ConvT2 at LEVEL 2); the coefficients
 // of the BN backward (training: dy = k (d' - A - x^ B) with k = gamma invstd, A = mean d', B = mean d' x^; eval: A = B = 0); a
 // power-of-two scale per branch from the bound |k| (max|d'| + |A| + max|x^| |B|) >= max |dy|.
-// coef: k[128], A[128], B[128], scale[2], 1/scale[2]
+// coef: k[128], A[128], B[128], scale[2], 1/scale[2], live[2] (1 = the branch's bound is finite and not zero: its scale means something)
 template <int LEVEL>
 __global__ __launch_bounds__(128) void dbhead_train_bwd_finish_kernel(const double* part, const double* bpart, int G, int64_t rows, int training,
                                                                       Branches P, Branches Gr, const float* stat, float* coef) {
@@ -484,6 +506,7 @@ __global__ __launch_bounds__(128) void dbhead_train_bwd_finish_kernel(const doub
         }
         coef[384 + c] = ldexpf(1.0f, e);
         coef[386 + c] = ldexpf(1.0f, -e);
+        coef[388 + c] = (mx > 0.0 && isfinite(mx)) ? 1.f : 0.f;
     }
 }
 
@@ -695,6 +718,65 @@ __global__ __launch_bounds__(DHT_THREADS) void dbhead_train_wgrad_reduce_kernel(
     }
 }
 
+// ---- input gradient: dP2 = conv3x3^T(dy1) ---------------------------------------------------------------------------------------------
+// wd3 [256][1152]: row ci, k = tap' * 128 + b * 64 + co holds w_b[co][ci][8 - tap'] (the window rotated by 180 degrees), rounded to fp16 as
+// the forward packs it, times common / scale_b with common = the smaller of the live branches' dy1 scales (coef1 + 384): a power of two
+// <= 1, exact unless the product falls below fp16's normal range -- which takes a ratio below ~2^-10, i.e. a branch whose whole gradient
+// is below the other's fp16 rounding.  A branch that is not live (coef1 + 388: its dy1 is all zeros, or its bound is not finite) takes
+// no part in the choice, and its weights are packed as zeros (0 x 0 = 0, 0 x inf = NaN as torch would give).  dscale = {common, 1 / common}.
+__global__ __launch_bounds__(DHT_THREADS) void dbhead_train_pack_dgrad_weights_kernel(Branches P, const float* coef1, half_t* wd3, float* zero,
+                                                                                      float* dscale) {
+    const int i = blockIdx.x * DHT_THREADS + threadIdx.x;
+    const float s0 = coef1[384], s1 = coef1[385];
+    const bool l0 = coef1[388] != 0.f, l1 = coef1[389] != 0.f;
+    const float common = l0 && l1 ? (s0 < s1 ? s0 : s1) : l0 ? s0 : l1 ? s1 : 1.f;
+    if (i < 256 * 1152) {
+        const int ci = i / 1152, k = i % 1152, tap = k / 128, c = k % 128, b = c >> 6, co = c & 63;
+        const half_t h = (half_t)P.b[b].conv_w[(co * 256 + ci) * 9 + (8 - tap)];
+        wd3[i] = (b ? l1 : l0) ? (half_t)((float)h * (common / (b ? s1 : s0))) : (half_t)0.f;
+    } else if (i < 256 * 1152 + 256) {
+        zero[i - 256 * 1152] = 0.f;
+    } else if (i == 256 * 1152 + 256) {
+        dscale[0] = common;
+        dscale[1] = 1.0f / common;
+    }
+}
+constexpr int PACK_DGRAD_ITEMS = 256 * 1152 + 256 + 1;
+
+// dy1 [M1][128] fp16 -> ring-padded [n][H+2][W+2][128], ring zeroed.  One thread = 8 channels (16 bytes) of one padded pixel.
+__global__ __launch_bounds__(DHT_THREADS) void dbhead_train_pad_dy1_kernel(const half_t* dy1, int n, int H, int W, half_t* out) {
+    const int Hp = H + 2, Wp = W + 2;
+    const int64_t i = (int64_t)blockIdx.x * DHT_THREADS + threadIdx.x;
+    if (i >= (int64_t)n * Hp * Wp * 16) return;
+    const int c8 = (int)(i & 15);
+    const int64_t pp = i >> 4;
+    const int xp = (int)(pp % Wp);
+    const int64_t r = pp / Wp;
+    const int yp = (int)(r % Hp), img = (int)(r / Hp);
+    const int y = yp - 1, x = xp - 1;
+    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (y >= 0 && y < H && x >= 0 && x < W) v = *(const half8*)(dy1 + (((int64_t)img * H + y) * W + x) * 128 + c8 * 8);
+    *(half8*)(out + i * 8) = v;
+}
+
+// scaled NHWC fp32 [n][H][W][256] -> NCHW fp32 [n][256][H][W], the scale undone.  Workgroup = 64 pixels of one image x 64 channels through
+// an LDS tile: 256-byte rows in, 256-byte rows out.
+__global__ __launch_bounds__(DHT_THREADS) void dbhead_train_unpack_input_grad_kernel(const float* d, const float* dscale, int HW, float* out) {
+    __shared__ float tile[64][65];
+    const int t = threadIdx.x, lane = t & 63, row = t >> 6;
+    const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, img = blockIdx.z;
+    const float inv = dscale[1];
+    for (int r = row; r < 64; r += 4) {
+        const int p = p0 + r;
+        tile[r][lane] = p < HW ? d[((int64_t)img * HW + p) * 256 + c0 + lane] * inv : 0.f;
+    }
+    __syncthreads();
+    for (int r = row; r < 64; r += 4) {
+        const int p = p0 + lane;
+        if (p < HW) out[((int64_t)img * 256 + c0 + r) * HW + p] = tile[lane][r];
+    }
+}
+
 inline unsigned blocks_for(int64_t items) { return (unsigned)((items + DHT_THREADS - 1) / DHT_THREADS); }
 
 bool params_ok(const vtd_dbhead_params* p, bool need_stats) {
@@ -724,7 +806,7 @@ ConvParams base_conv() {
 
 int64_t vtd_dbhead_ws_bytes(int n, int H, int W, int backward) {
     if (n <= 0 || H <= 0 || W <= 0 || (int64_t)n * H * W * 4 >= (1ll << 31)) return -2802;
-    return backward ? bwd_layout(n, H, W).total : fwd_layout(n, H, W).total;
+    return backward == 2 ? dgrad_layout(n, H, W).total : backward ? bwd_layout(n, H, W).total : fwd_layout(n, H, W).total;
 }
 
 int vtd_launch_dbhead_pack(const void* x, int dtype, int n, int H, int W, void* feats, hipStream_t s) {
@@ -869,5 +951,40 @@ int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd
         hipLaunchKernelGGL(dbhead_train_wgrad_reduce_kernel<0>, dim3(blocks_for(128 * 2304)), dim3(DHT_THREADS), 0, s, (const float*)slab, S,
                            (const float*)(coef1 + 386), Gr);
     }
+    return -(int)hipGetLastError();
+}
+
+// dP2 after vtd_launch_dbhead_backward on the same scratch (sized by mode 2): reads dy1 and its two scales where the backward left them
+int vtd_launch_dbhead_backward_input(int n, int H, int W, const vtd_dbhead_params* params, void* scratch, float* dfeats, float* dscale, hipStream_t s) {
+    if (!scratch || !dfeats || !dscale || !params || vtd_dbhead_ws_bytes(n, H, W, 2) < 0) return -2802;
+    for (int b = 0; b < 2; ++b)
+        if (!params->branch[b].conv_w || ((uintptr_t)params->branch[b].conv_w & 3)) return -2802;
+    if (((uintptr_t)scratch & 255) || ((uintptr_t)dfeats & 15) || ((uintptr_t)dscale & 7)) return -2803;
+    const BwdLayout B = bwd_layout(n, H, W);
+    const DgradLayout D = dgrad_layout(n, H, W);
+    char* x = (char*)scratch;
+    const half_t* dy1 = (const half_t*)(x + B.dy1);
+    const float* coef1 = (const float*)(x + B.coef1);
+    half_t *dy1p = (half_t*)(x + D.dy1p), *wd3 = (half_t*)(x + D.wd3);
+    float* zero = (float*)(x + D.zero);
+    Branches P;
+    P.b[0] = params->branch[0]; P.b[1] = params->branch[1];
+    const int64_t M1 = (int64_t)n * H * W;
+    hipLaunchKernelGGL(dbhead_train_pack_dgrad_weights_kernel, dim3(blocks_for(PACK_DGRAD_ITEMS)), dim3(DHT_THREADS), 0, s, P, coef1, wd3, zero, dscale);
+    hipLaunchKernelGGL(dbhead_train_pad_dy1_kernel, dim3(blocks_for((int64_t)n * (H + 2) * (W + 2) * 16)), dim3(DHT_THREADS), 0, s, dy1, n, H, W, dy1p);
+    VTD_HIP_CHECK(hipGetLastError());
+    ConvParams c = base_conv();
+    c.in = dy1p; c.wgt = wd3; c.bias = zero; c.out = dfeats; c.ldc = 256; c.flags = EPI_OUT_F32;
+    c.cin_steps = 2; c.kw = 3; c.s_step = 128; c.r_step = (W + 2) * 128;
+    c.M = (int)M1; c.K = 1152; c.cout = 256; c.cout_pad = 256; c.ho = H; c.wo = W;
+    c.in_hp = H + 2; c.in_wp = W + 2; c.in_c = 128; c.in_y0 = 0; c.in_x0 = 0;
+    return vtd_launch_conv(c, -1, s);
+}
+
+int vtd_launch_dbhead_unpack_input_grad(const float* dfeats, const float* dscale, int n, int H, int W, float* out, hipStream_t s) {
+    if (!dfeats || !dscale || !out || vtd_dbhead_ws_bytes(n, H, W, 2) < 0 || n > 65535) return -2802;
+    if (((uintptr_t)dfeats & 15) || ((uintptr_t)dscale & 7) || ((uintptr_t)out & 3)) return -2803;
+    const int HW = H * W;
+    hipLaunchKernelGGL(dbhead_train_unpack_input_grad_kernel, dim3((HW + 63) / 64, 4, n), dim3(DHT_THREADS), 0, s, dfeats, dscale, HW, out);
     return -(int)hipGetLastError();
 }

@@ -61,6 +61,8 @@ int64_t vtd_dbhead_ws_bytes(int n, int H, int W, int backward);
 int vtd_launch_dbhead_pack(const void* x, int dtype, int n, int H, int W, void* feats, hipStream_t s);
 int vtd_launch_dbhead_forward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, float momentum, float eps,
                               void* ws, float* prob, float* thresh, float* stats_out, hipStream_t s);
+int vtd_launch_dbhead_backward_input(int n, int H, int W, const vtd_dbhead_params* params, void* scratch, float* dfeats, float* dscale, hipStream_t s);
+int vtd_launch_dbhead_unpack_input_grad(const float* dfeats, const float* dscale, int n, int H, int W, float* out, hipStream_t s);
 int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
                                const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
                                void* scratch, hipStream_t s);
@@ -1453,6 +1455,16 @@ int vtd_dbhead_train_backward(const void* feats_dev, int n, int height, int widt
                               const float* grad_thresh_dev, const vtd_dbhead_params* grads, void* scratch_dev, vtd_stream stream) {
     return vtd_launch_dbhead_backward(feats_dev, n, height, width, params, training, workspace_dev, prob_dev, thresh_dev, grad_prob_dev,
                                       grad_thresh_dev, grads, scratch_dev, (hipStream_t)stream);
+}
+
+int vtd_dbhead_train_backward_input(int n, int height, int width, const vtd_dbhead_params* params, void* scratch_dev, float* dfeats_dev,
+                                    float* dscale_dev, vtd_stream stream) {
+    return vtd_launch_dbhead_backward_input(n, height, width, params, scratch_dev, dfeats_dev, dscale_dev, (hipStream_t)stream);
+}
+
+int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_dev, int n, int height, int width, float* grad_nchw_dev,
+                                 vtd_stream stream) {
+    return vtd_launch_dbhead_unpack_input_grad(dfeats_dev, dscale_dev, n, height, width, grad_nchw_dev, (hipStream_t)stream);
 }
 
 int vtd_device_count(void) {

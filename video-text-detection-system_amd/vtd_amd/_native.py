@@ -109,6 +109,8 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_dbhead_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DbHeadParams), C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DbHeadParams), C.c_void_p, C.c_void_p]),
+    "vtd_dbhead_train_backward_input": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(DbHeadParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_dbhead_unpack_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_binary_counts_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "vtd_trocr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vtd_trocr_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),

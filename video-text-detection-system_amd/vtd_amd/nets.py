@@ -125,11 +125,13 @@ def _head_struct(tensors):
 
 class _DBHeadTrainFn(torch.autograd.Function):
     """DBHead.forward on the HIP training kernels (csrc/dbhead_train.hip), differentiable w.r.t. the 20 learnable head tensors.  Inputs:
-    padded features (include/vtd.h), (H, W), BatchNorm mode / momentum / eps, the four running-stat buffers per branch (updated in place
-    in training mode), then the learnable tensors branch-major in _HEAD_LEARNABLE order."""
+    padded features (include/vtd.h), `src`, (H, W), BatchNorm mode / momentum / eps, the four running-stat buffers per branch (updated in
+    place in training mode), then the learnable tensors branch-major in _HEAD_LEARNABLE order.  `src` is None, or the [n,256,H,W] tensor the
+    padded features were packed from: when it requires grad the backward also forms the gradient of the features (dgrad into P2,
+    vtd_dbhead_train_backward_input) and hands it to `src` in NCHW."""
 
     @staticmethod
-    def forward(ctx, feats, hw, training, momentum, eps, buffers, *params):
+    def forward(ctx, feats, src, hw, training, momentum, eps, buffers, *params):
         import ctypes as C
         from . import _native
         lib = _native.require()
@@ -152,6 +154,7 @@ class _DBHeadTrainFn(torch.autograd.Function):
                       "vtd_dbhead_train_forward")
         ctx.save_for_backward(feats, prob, thresh, *params)
         ctx.ws, ctx.hw, ctx.training = ws, (H, W), bool(training)
+        ctx.src_dtype = None if src is None else src.dtype
         ctx.mark_non_differentiable(stats)
         return prob, thresh, stats
 
@@ -170,13 +173,24 @@ class _DBHeadTrainFn(torch.autograd.Function):
                 tensors[(b, field)] = params[b * len(_HEAD_LEARNABLE) + i]
                 gtensors[(b, field)] = grads[b * len(_HEAD_LEARNABLE) + i]
         st, gst = _head_struct(tensors), _head_struct(gtensors)
-        scratch = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 1)), dtype=torch.uint8, device=feats.device)
+        want_input = ctx.src_dtype is not None and ctx.needs_input_grad[1]
+        scratch = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 2 if want_input else 1)), dtype=torch.uint8, device=feats.device)
         g = [None if t is None else t.to(torch.float32).contiguous() for t in (grad_prob, grad_thresh)]
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         _native.check(lib.vtd_dbhead_train_backward(ptr(feats), n, H, W, C.byref(st), 1 if ctx.training else 0, ptr(ctx.ws), ptr(prob),
                                                     ptr(thresh), ptr(g[0]), ptr(g[1]), C.byref(gst), ptr(scratch),
                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_dbhead_train_backward")
-        return (None, None, None, None, None, None, *grads)
+        grad_src = None
+        if want_input:
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            dfeats = torch.empty((n, H, W, 256), dtype=torch.float32, device=feats.device)   # NHWC, scaled by dscale[0]
+            dscale = torch.empty(2, dtype=torch.float32, device=feats.device)
+            _native.check(lib.vtd_dbhead_train_backward_input(n, H, W, C.byref(st), ptr(scratch), ptr(dfeats), ptr(dscale), stream),
+                          "vtd_dbhead_train_backward_input")
+            grad_src = torch.empty((n, 256, H, W), dtype=torch.float32, device=feats.device)
+            _native.check(lib.vtd_dbhead_unpack_input_grad(ptr(dfeats), ptr(dscale), n, H, W, ptr(grad_src), stream), "vtd_dbhead_unpack_input_grad")
+            grad_src = grad_src.to(ctx.src_dtype)
+        return (None, grad_src, None, None, None, None, None, *grads)
 
 
 def pack_features(features):
@@ -199,8 +213,10 @@ def pack_features(features):
 class DBHead(nn.Module):
     """DBHead (text_detector.py:58-86).  ``head(features)`` on a CUDA ``[n,256,H,W]`` tensor returns ``{'probability', 'threshold'}``
     (``[n,1,4H,4W]`` fp32) from the HIP training kernels, with torch's BatchNorm semantics in ``train()`` (batch statistics, running
-    statistics updated, ``num_batches_tracked`` + 1) and ``eval()``, differentiable w.r.t. the head's parameters.  No gradient flows into
-    the features: a ``features`` tensor that requires grad is refused."""
+    statistics updated, ``num_batches_tracked`` + 1) and ``eval()``, differentiable w.r.t. the head's parameters.  A ``features`` tensor
+    that requires grad is refused unless the call says ``input_grad=True``: then the backward also forms the gradient of the features
+    (dgrad into P2, one more implicit GEMM) and ``features`` receives it in its own layout and dtype.  The head's parameter gradients are
+    the same bits either way."""
 
     def __init__(self, in_channels):
         super().__init__()
@@ -211,18 +227,24 @@ class DBHead(nn.Module):
     def _branches(self):
         return (self.probability_head, self.threshold_head)
 
-    def forward(self, features):
+    def forward(self, features, input_grad=False):
         if not torch.is_tensor(features) or features.dim() != 4 or features.shape[1] != self.in_channels:
             raise ValueError(f"DBHead input must be a [n,{self.in_channels},H,W] tensor")
-        if features.requires_grad:
-            raise RuntimeError("DBHead: the features require grad, but backward into the features (dgrad into P2, i.e. through the "
-                               "FPN / trunk) is not implemented; pass features.detach()")
+        if features.requires_grad and not input_grad:
+            raise RuntimeError("DBHead: the features require grad, but backward into the features (dgrad into P2) is only formed on "
+                               "request; pass input_grad=True, or features.detach()")
         if not features.is_cuda:
             raise ValueError("DBHead runs on the HIP kernels: features must be a CUDA (HIP) tensor")
-        return self.forward_padded(pack_features(features), features.shape[2], features.shape[3])
+        src = features if input_grad and features.requires_grad and torch.is_grad_enabled() else None
+        return self._forward_padded(pack_features(features), features.shape[2], features.shape[3], src)
 
     def forward_padded(self, feats, H, W):
-        """The head on padded features (ring-padded NHWC fp16 [n,H+2,W+2,256], e.g. DetectorEngine.forward_features)."""
+        """The head on padded features (ring-padded NHWC fp16 [n,H+2,W+2,256], e.g. DetectorEngine.forward_features).  No gradient is
+        formed for padded features (fp16 storage would flush it): the gradient of the features goes through ``forward(features,
+        input_grad=True)``."""
+        return self._forward_padded(feats, H, W, None)
+
+    def _forward_padded(self, feats, H, W, src):
         if self.in_channels != 256:
             raise ValueError("the HIP DB-head kernels are specialised for 256 input channels")
         H, W = int(H), int(W)
@@ -242,7 +264,7 @@ class DBHead(nn.Module):
             if not t.is_cuda or t.device != feats.device or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("DBHead parameters and buffers must be contiguous float32 CUDA tensors on the features' device "
                                  "(call .cuda() on the model)")
-        prob, thresh, _ = _DBHeadTrainFn.apply(feats, (int(H), int(W)), self.training, bns[0].momentum, bns[0].eps, tuple(buffers), *params)
+        prob, thresh, _ = _DBHeadTrainFn.apply(feats, src, (int(H), int(W)), self.training, bns[0].momentum, bns[0].eps, tuple(buffers), *params)
         if self.training:
             with torch.no_grad():
                 for bn in bns:
