@@ -202,6 +202,46 @@ int vtd_dbhead_train_backward_input(int n, int height, int width, const vtd_dbhe
 int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_dev, int n, int height, int width, float* grad_nchw_dev,
                                  vtd_stream stream);
 
+/* ---- FPN training, forward and backward (text_detector.py:31-56 FeaturePyramidNetwork in the wiring of SURVEY.md B.3), over a frozen trunk
+ * L5 = inner_blocks[0](C5), L(k) = inner_blocks[5-k](C(k)) + nearest-2x(L(k+1)), P2 = layer_blocks[3](L2); layer_blocks[0..2] are dead and get no
+ * gradient.  The geometry is given by the C5 size: C(5-k) is [n][c5_channels >> k][h5 << k][w5 << k]; c5_channels is a multiple of 512
+ * (512 = ResNet-18, 2048 = ResNet-50) up to 4096.  Every other combination is refused.
+ *
+ * Taps are "padded taps": ring-padded NHWC fp16 [n][H+2][W+2][C] with a one-pixel ring (the detector engine's own layout), passed as an
+ * array of four device pointers ordered C2, C3, C4, C5 (16-byte aligned).
+ * vtd_detector_forward_trunk: the detector's ops up to the last residual stage of the current input, then a copy of the four taps into
+ * caller-owned buffers.  Needs a handle finalized with "fuse_fpn_head" = 0 (the fused graph pads C2 differently): -2901 otherwise.
+ * vtd_fpn_train_pack_tap: [n][channels][H][W] NCHW float32 (dtype 0) or fp16 (dtype 1) -> a padded tap, ring included; channels % 64 == 0.
+ *
+ * Parameters are torch's own tensors as device pointers, float32, contiguous: inner_w[i] / inner_b[i] = fpn.inner_blocks.i
+ * ([256][c5_channels >> i][1][1], [256]; i = 0 reads C5), layer_w / layer_b = fpn.layer_blocks.3 ([256][256][3][3], [256]).  Weights are
+ * converted to the kernels' fp16 layouts on the device inside every call, so an in-place optimizer step is seen by the next call.
+ * vtd_fpn_train_workspace_bytes: mode 0 = the forward's workspace (the four padded laterals and the packed weights), mode 1 = the
+ * backward's scratch; negative for a refused geometry.
+ * vtd_fpn_train_forward: writes P2 as padded features (what vtd_dbhead_train_forward reads: [n][8 h5 + 2][8 w5 + 2][256] fp16, ring zeroed)
+ * into p2_dev (16-byte aligned) and keeps padded L2 in workspace_dev (256-byte aligned) for the backward.
+ * vtd_fpn_train_unpack_p2: padded P2 -> [n][256][H][W] float32.  vtd_fpn_train_pack_grad: an upstream gradient of P2, [n][256][H][W]
+ * float32 -> NHWC float32 [n][H][W][256] (with dscale = {1, 1} what the backward reads).
+ * vtd_fpn_train_backward: gradients of the ten live tensors, written (not accumulated) as float32 into the grads struct's pointers.
+ * dp2_dev / dscale_dev are exactly what vtd_dbhead_train_backward_input writes: dP2 as NHWC float32 [n][H][W][256] times dscale_dev[0], and
+ * {scale, 1 / scale}.  GEMM operands are fp16 with an exact power-of-two scale per tensor chosen on the device from max |.|; the sum-pool
+ * chain dL(k+1) = sumpool2x2(dL(k)) and the bias sums are fp32 / fp64.  No atomics, shape-only grids: bitwise repeatable.  No gradient
+ * of C2..C5 is formed.
+ * Errors: -2901 (handle built with the fused head entry), -2902 (argument / shape), -2903 (alignment). */
+typedef struct vtd_fpn_params {
+    float *inner_w[4], *inner_b[4];
+    float *layer_w, *layer_b;
+} vtd_fpn_params;
+int vtd_detector_forward_trunk(vtd_detector* d, int n, void* c2_dev, void* c3_dev, void* c4_dev, void* c5_dev, vtd_stream stream);
+int vtd_fpn_train_pack_tap(const void* x_dev, int dtype, int n, int channels, int height, int width, void* tap_dev, vtd_stream stream);
+int64_t vtd_fpn_train_workspace_bytes(int n, int h5, int w5, int c5_channels, int mode);
+int vtd_fpn_train_forward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, void* workspace_dev,
+                          void* p2_dev, vtd_stream stream);
+int vtd_fpn_train_unpack_p2(const void* p2_dev, int n, int height, int width, float* p2_nchw_dev, vtd_stream stream);
+int vtd_fpn_train_pack_grad(const float* grad_nchw_dev, int n, int height, int width, float* dp2_dev, vtd_stream stream);
+int vtd_fpn_train_backward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, const void* workspace_dev,
+                           const float* dp2_dev, const float* dscale_dev, const vtd_fpn_params* grads, void* scratch_dev, vtd_stream stream);
+
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */
 int vtd_recognizer_create(int vocab_size, int max_crops, vtd_recognizer** out);

@@ -66,7 +66,7 @@ def _clean(names):
 CONV_LABELS = ["conv3x3_forward", "convt1_forward_b0", "convt1_forward_b1", "convt1_dgrad_b0", "convt1_dgrad_b1", "conv3x3_dgrad"]
 
 
-def per_launch(fn):
+def per_launch(fn, labels=None):
     """[(label, microseconds)] of every kernel one step launches, in launch order (torch.profiler's device events)."""
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -75,10 +75,11 @@ def per_launch(fn):
     evs = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and e.time_range.elapsed_us() > 0]
     evs.sort(key=lambda e: e.time_range.start)
     names = _clean([e.name for e in evs])
+    labels = CONV_LABELS if labels is None else labels
     out, conv = [], 0
     for e, nm in zip(evs, names):
         if nm.startswith("conv_igemm"):
-            nm = CONV_LABELS[conv] if conv < len(CONV_LABELS) else nm
+            nm = labels[conv] if conv < len(labels) else nm
             conv += 1
         out.append((nm, float(e.time_range.elapsed_us())))
     return out

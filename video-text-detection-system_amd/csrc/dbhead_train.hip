@@ -31,6 +31,7 @@
 //   conv 3x3         dP2 = conv3x3^T(dy1) as ONE implicit GEMM (conv_igemm.hip, K = 1152, N = 256) -> fp32 [M1][256], scaled
 // Every reduction has a grid that depends on the shape only and a fixed summation order, and no atomics: bitwise repeatable.
 #include "vtd_common.h"
+#include "wgrad_mfma.h"
 #include "../../include/vtd.h"
 
 #include <cstring>
@@ -58,7 +59,6 @@ inline int red_blocks(int64_t rows) {
 inline int64_t rows_per_block(int64_t rows, int g) { return (rows + g - 1) / g; }
 
 // weight-gradient slabs (split over M)
-constexpr int WG_KC = 32;   // rows per K chunk (one v_mfma_f32_16x16x32_f16 K-step)
 inline int wgrad_slabs(int64_t rows, int mode) {
     const int64_t per = mode == 0 ? 8192 : 4096, cap = mode == 0 ? 64 : 256;
     int64_t s = (rows + per - 1) / per;
@@ -568,139 +568,7 @@ __global__ __launch_bounds__(128) void dbhead_train_bias_finish_kernel(const dou
     (which ? Gr.b[b].ct1_b : Gr.b[b].conv_b)[cc] = (float)s;
 }
 
-// ---- weight gradients: C[p][q] = sum_m A[m][p] B[m][q] over one slab of rows, on v_mfma_f32_16x16x32_f16 ---------------------------
-// MODE 0 (conv 3x3): A = dy1 [M1][128] (P_T = 128, both branches), B = im2col of the padded features, q-tile qt = 128 channels of tap
-//   qt / 2: 18 q-tiles.  MODE 1 (ConvT1): A = a1 columns of branch qt / 2 (P_T = 64), B = dz of that branch at pixel (2y+ky, 2x+kx),
-//   q = tap * 64 + co, two taps per q-tile: 4 q-tiles.
-// Workgroup = 4 waves, one (q-tile, slab); each wave a (P_T / 2) x 64 block.  Per K chunk of 32 rows every thread loads rows 8o .. 8o+7
-// of one column pair of A and B with 4-byte loads (the next chunk's loads are in flight during this chunk's MFMAs), transposes them into
-// LDS as [row octet][column][8] so that a fragment (8 consecutive rows of one column) is one 16-byte read, double-buffered: one barrier
-// per chunk.  Rows past the slab load zeros.  slab[s][P][Q] fp32: MODE 0 [128][2304], MODE 1 [2][64][256].
-struct WgArgs {
-    const half_t* a;    // [rows][lda]
-    int lda;
-    const half_t* x;    // MODE 0: padded features; MODE 1: dz [M2][128]
-    int n, H, W;
-    int64_t rows, slab_len;
-    float* slab;
-};
-
-template <int MODE>
-__device__ __forceinline__ const half_t* wg_brow(const WgArgs& A, int img, int y, int xx, int qt, int grp) {
-    if constexpr (MODE == 0) {
-        const int tap = qt >> 1, ky = tap / 3, kx = tap % 3;
-        return A.x + (((int64_t)img * (A.H + 2) + y + ky) * (A.W + 2) + xx + kx) * 256 + (qt & 1) * 128 + grp * 64;
-    } else {
-        const int b = qt >> 1, tap = (qt & 1) * 2 + grp, ky = tap >> 1, kx = tap & 1;
-        return A.x + (((int64_t)img * 2 * A.H + 2 * y + ky) * 2 * A.W + 2 * xx + kx) * 128 + b * 64;
-    }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(DHT_THREADS) void dbhead_train_wgrad_kernel(const WgArgs A) {
-    constexpr int PT = MODE == 0 ? 128 : 64, QT = 128, FP = PT / 32, FQ = 4;
-    constexpr int NQT = MODE == 0 ? 18 : 4;
-    const int qt = blockIdx.x % NQT, sl = blockIdx.x / NQT;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wp = w >> 1, wq = w & 1;
-    const int a_col0 = MODE == 0 ? 0 : (qt >> 1) * 128;   // MODE 1: the hi half of the branch's a1 pair
-    __shared__ __attribute__((aligned(16))) half_t lds[2][4 * (PT + QT) * 8];
-
-    const int64_t r0 = (int64_t)sl * A.slab_len;
-    const int64_t r1 = r0 + A.slab_len < A.rows ? r0 + A.slab_len : A.rows;
-    const int nchunks = r1 > r0 ? (int)((r1 - r0 + WG_KC - 1) / WG_KC) : 0;
-
-    // this thread's load slots: A column pair ap (octet ao), B column pair bp (octet bo)
-    const int ap = t % (PT / 2), ao = t / (PT / 2);          // ao < 4 active (MODE 1: 8 octets per pass, only 4 needed)
-    const int bp = t % (QT / 2), bo = t / (QT / 2);          // bo in 0..3
-    const bool a_act = ao < 4;
-    const int bgrp = (2 * bp) / 64, bcol = (2 * bp) % 64;
-    const int HW = A.H * A.W;
-
-    uint32_t ra[8], rb[8];
-    auto gload = [&](int ch) {
-        const int64_t base = r0 + (int64_t)ch * WG_KC;
-        // A: rows base + 8 ao + j, columns a_col0 + 2 ap, +1
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int64_t m = base + 8 * ao + j;
-            ra[j] = (a_act && m < r1) ? *(const uint32_t*)(A.a + m * A.lda + a_col0 + 2 * ap) : 0u;
-        }
-        // B: rows base + 8 bo + j (consecutive: decode the first, then step x)
-        int64_t m = base + 8 * bo;
-        int img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / A.W, xx = rem - y * A.W;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            rb[j] = (m < r1) ? *(const uint32_t*)(wg_brow<MODE>(A, img, y, xx, qt, bgrp) + bcol) : 0u;
-            ++m;
-            if (++xx == A.W) { xx = 0; if (++y == A.H) { y = 0; ++img; } }
-        }
-    };
-    auto lstore = [&](int buf) {
-        half_t* la = lds[buf];
-        half_t* lb = lds[buf] + 4 * PT * 8;
-        if (a_act) {
-            half8 lo, hi;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                lo[j] = __builtin_bit_cast(half2v, ra[j])[0];
-                hi[j] = __builtin_bit_cast(half2v, ra[j])[1];
-            }
-            *(half8*)(la + (ao * PT + 2 * ap) * 8) = lo;
-            *(half8*)(la + (ao * PT + 2 * ap + 1) * 8) = hi;
-        }
-        half8 lo, hi;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            lo[j] = __builtin_bit_cast(half2v, rb[j])[0];
-            hi[j] = __builtin_bit_cast(half2v, rb[j])[1];
-        }
-        *(half8*)(lb + (bo * QT + 2 * bp) * 8) = lo;
-        *(half8*)(lb + (bo * QT + 2 * bp + 1) * 8) = hi;
-    };
-
-    floatx4 acc[FP][FQ];
-#pragma unroll
-    for (int i = 0; i < FP; ++i)
-#pragma unroll
-        for (int j = 0; j < FQ; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-    if (nchunks > 0) gload(0);
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const int buf = ch & 1;
-        lstore(buf);
-        __syncthreads();
-        if (ch + 1 < nchunks) gload(ch + 1);
-        const half_t* la = lds[buf];
-        const half_t* lb = lds[buf] + 4 * PT * 8;
-        const int oct = lane >> 4, col = lane & 15;
-        half8 fa[FP], fb[FQ];
-#pragma unroll
-        for (int i = 0; i < FP; ++i) fa[i] = *(const half8*)(la + (oct * PT + wp * (PT / 2) + i * 16 + col) * 8);
-#pragma unroll
-        for (int j = 0; j < FQ; ++j) fb[j] = *(const half8*)(lb + (oct * QT + wq * 64 + j * 16 + col) * 8);
-#pragma unroll
-        for (int i = 0; i < FP; ++i)
-#pragma unroll
-            for (int j = 0; j < FQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-
-    // C row p = wp * PT/2 + i*16 + 4*(lane>>4) + e, column q = wq*64 + j*16 + (lane&15)
-    const int ldq = MODE == 0 ? 2304 : 256;
-    float* out = A.slab + (int64_t)sl * (MODE == 0 ? 128 * 2304 : 2 * 64 * 256);
-    const int p_base = MODE == 0 ? 0 : (qt >> 1) * 64;
-    const int q_base = MODE == 0 ? qt * 128 : (qt & 1) * 128;
-#pragma unroll
-    for (int i = 0; i < FP; ++i)
-#pragma unroll
-        for (int j = 0; j < FQ; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int p = p_base + wp * (PT / 2) + i * 16 + 4 * (lane >> 4) + e;
-                const int q = q_base + wq * 64 + j * 16 + (lane & 15);
-                out[(int64_t)p * ldq + q] = acc[i][j][e];
-            }
-}
-
+// ---- weight gradients: the MFMA kernel is wgrad_mfma.h (shared with fpn_train.hip); MODE 0 = conv 3x3, MODE 1 = ConvT1 ----------------------
 // slabs summed in slab order, scale undone per branch, written in torch's layout
 template <int MODE>
 __global__ __launch_bounds__(DHT_THREADS) void dbhead_train_wgrad_reduce_kernel(const float* slab, int S, const float* inv_sc, Branches Gr) {
@@ -921,6 +789,7 @@ int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd
     }
     {
         WgArgs wa;
+        wa.xc = 0;
         wa.a = a1; wa.lda = 256; wa.x = dz; wa.n = n; wa.H = H; wa.W = W; wa.rows = M1; wa.slab = slab;
         const int S = wgrad_slabs(M1, 1);
         wa.slab_len = slab_rows(M1, S);
@@ -944,6 +813,7 @@ int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd
     // ---- conv 3x3 weight gradient
     {
         WgArgs wa;
+        wa.xc = 0;
         wa.a = dy1; wa.lda = 128; wa.x = (const half_t*)feats; wa.n = n; wa.H = H; wa.W = W; wa.rows = M1; wa.slab = slab;
         const int S = wgrad_slabs(M1, 0);
         wa.slab_len = slab_rows(M1, S);

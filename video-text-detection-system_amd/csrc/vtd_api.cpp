@@ -63,6 +63,13 @@ int vtd_launch_dbhead_forward(const void* feats, int n, int H, int W, const vtd_
                               void* ws, float* prob, float* thresh, float* stats_out, hipStream_t s);
 int vtd_launch_dbhead_backward_input(int n, int H, int W, const vtd_dbhead_params* params, void* scratch, float* dfeats, float* dscale, hipStream_t s);
 int vtd_launch_dbhead_unpack_input_grad(const float* dfeats, const float* dscale, int n, int H, int W, float* out, hipStream_t s);
+int64_t vtd_fpn_ws_bytes(int n, int h5, int w5, int c5, int mode);
+int vtd_launch_fpn_pack_tap(const void* x, int dtype, int n, int channels, int H, int W, void* out, hipStream_t s);
+int vtd_launch_fpn_unpack_p2(const void* p2, int n, int H, int W, float* out, hipStream_t s);
+int vtd_launch_fpn_pack_grad(const float* g, int n, int H, int W, float* out, hipStream_t s);
+int vtd_launch_fpn_forward(const void* const* taps, int n, int h5, int w5, int c5, const vtd_fpn_params* params, void* ws, void* p2_out, hipStream_t s);
+int vtd_launch_fpn_backward(const void* const* taps, int n, int h5, int w5, int c5, const vtd_fpn_params* params, const void* ws, const float* dp2,
+                            const float* dscale, const vtd_fpn_params* grads, void* scratch, hipStream_t s);
 int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
                                const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
                                void* scratch, hipStream_t s);
@@ -578,6 +585,7 @@ struct vtd_detector : vtd::ModelBase {
     bool fuse_stem_pool = true;  // conv7x7/s2 + BN + ReLU + maxpool3x3/s2 in one kernel (the 320x320x64 map is never written)
     bool fuse_fpn_head = true;  // compose FPN lateral(C2) + top-down add + P2 smooth + head conv into one classed conv
     bool fuse_downsample = true;  // a downsample block's 1x1 projection rides in the block's last conv as extra K-steps (attach_second_segment)
+    size_t trunk_ops = 0;  // ops up to and including the last residual stage (vtd_detector_forward_trunk)
     size_t p2_ops = 0;  // unfused graph: ops up to and including the one that writes P2 (vtd_detector_forward_features)
     // optional per-op HIP-event timing (bench / roofline accounting)
     bool profiling = false;
@@ -1212,6 +1220,7 @@ static int build_detector_graph(vtd_detector* d) {
         tapsC[st] = x;
         d->taps["c" + std::to_string(st + 2)] = x;
     }
+    d->trunk_ops = d->ops.size();
 
     // FPN, intended wiring: inner[i] on C5,C4,C3,C2; top-down nearest-2x add fused in the epilogue
     TensorDesc last;
@@ -1403,6 +1412,9 @@ const char* vtd_strerror(int code) {
         case -2801: return "feature export needs a detector finalized with fuse_fpn_head=0 (the fused head entry never forms P2)";
         case -2802: return "DB head training: invalid argument or shape";
         case -2803: return "DB head training: misaligned buffer";
+        case -2901: return "trunk export needs a detector finalized with fuse_fpn_head=0 (the fused graph pads C2 for the composed head entry)";
+        case -2902: return "FPN training: invalid argument or shape";
+        case -2903: return "FPN training: misaligned buffer";
         default: break;
     }
     if (code <= -1000) {
@@ -1460,6 +1472,31 @@ int vtd_dbhead_train_backward(const void* feats_dev, int n, int height, int widt
 int vtd_dbhead_train_backward_input(int n, int height, int width, const vtd_dbhead_params* params, void* scratch_dev, float* dfeats_dev,
                                     float* dscale_dev, vtd_stream stream) {
     return vtd_launch_dbhead_backward_input(n, height, width, params, scratch_dev, dfeats_dev, dscale_dev, (hipStream_t)stream);
+}
+
+// ---- FPN training (fpn_train.hip)
+int vtd_fpn_train_pack_tap(const void* x_dev, int dtype, int n, int channels, int height, int width, void* tap_dev, vtd_stream stream) {
+    return vtd_launch_fpn_pack_tap(x_dev, dtype, n, channels, height, width, tap_dev, (hipStream_t)stream);
+}
+
+int64_t vtd_fpn_train_workspace_bytes(int n, int h5, int w5, int c5_channels, int mode) { return vtd_fpn_ws_bytes(n, h5, w5, c5_channels, mode); }
+
+int vtd_fpn_train_forward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, void* workspace_dev,
+                          void* p2_dev, vtd_stream stream) {
+    return vtd_launch_fpn_forward(taps, n, h5, w5, c5_channels, params, workspace_dev, p2_dev, (hipStream_t)stream);
+}
+
+int vtd_fpn_train_unpack_p2(const void* p2_dev, int n, int height, int width, float* p2_nchw_dev, vtd_stream stream) {
+    return vtd_launch_fpn_unpack_p2(p2_dev, n, height, width, p2_nchw_dev, (hipStream_t)stream);
+}
+
+int vtd_fpn_train_pack_grad(const float* grad_nchw_dev, int n, int height, int width, float* dp2_dev, vtd_stream stream) {
+    return vtd_launch_fpn_pack_grad(grad_nchw_dev, n, height, width, dp2_dev, (hipStream_t)stream);
+}
+
+int vtd_fpn_train_backward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, const void* workspace_dev,
+                           const float* dp2_dev, const float* dscale_dev, const vtd_fpn_params* grads, void* scratch_dev, vtd_stream stream) {
+    return vtd_launch_fpn_backward(taps, n, h5, w5, c5_channels, params, workspace_dev, dp2_dev, dscale_dev, grads, scratch_dev, (hipStream_t)stream);
 }
 
 int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_dev, int n, int height, int width, float* grad_nchw_dev,
@@ -1603,6 +1640,29 @@ int vtd_detector_forward_features(vtd_detector* d, int n, void* feats_dev, vtd_s
     if (rc) return rc;
     const TensorDesc& p2 = d->taps["p2"];
     VTD_HIP_CHECK(hipMemcpyAsync(feats_dev, p2.ptr, (size_t)n * p2.hp * p2.wp * p2.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// the trunk only, then a copy of the n frames' ring-padded taps C2..C5 into the caller's buffers (same layout: [n][h+2][w+2][c] fp16)
+int vtd_detector_forward_trunk(vtd_detector* d, int n, void* c2_dev, void* c3_dev, void* c4_dev, void* c5_dev, vtd_stream stream) {
+    void* dst[4] = {c2_dev, c3_dev, c4_dev, c5_dev};
+    if (!d || !c2_dev || !c3_dev || !c4_dev || !c5_dev) return ERR_ARG;
+    if (!d->finalized) return ERR_NOT_FINALIZED;
+    if (n <= 0 || n > d->max_batch) return ERR_BATCH;
+    if (d->fuse_fpn_head || !d->trunk_ops) return -2901;
+    const char* names[4] = {"c2", "c3", "c4", "c5"};
+    for (int i = 0; i < 4; ++i) {
+        if ((uintptr_t)dst[i] & 15) return -2903;
+        auto it = d->taps.find(names[i]);
+        if (it == d->taps.end() || it->second.ring != 1) return -2901;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_detector_ops(d, n, nullptr, nullptr, s, d->trunk_ops);
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) {
+        const TensorDesc& t = d->taps[names[i]];
+        VTD_HIP_CHECK(hipMemcpyAsync(dst[i], t.ptr, (size_t)n * t.hp * t.wp * t.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+    }
     return 0;
 }
 

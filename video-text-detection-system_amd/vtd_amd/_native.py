@@ -43,6 +43,14 @@ class DbHeadParams(C.Structure):
     _fields_ = [("branch", DbHeadBranch * 2)]
 
 
+class FpnParams(C.Structure):
+    """vtd_fpn_params of include/vtd.h: device pointers to the FPN's ten live fp32 tensors (inner_blocks.0..3, layer_blocks.3)"""
+    _fields_ = [("inner_w", C.c_void_p * 4), ("inner_b", C.c_void_p * 4), ("layer_w", C.c_void_p), ("layer_b", C.c_void_p)]
+
+
+FpnTaps = C.c_void_p * 4   # padded taps C2, C3, C4, C5
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vtd.h
 SIGNATURES = {
     "vtd_version": (C.c_char_p, []),
@@ -111,6 +119,15 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DbHeadParams), C.c_void_p, C.c_void_p]),
     "vtd_dbhead_train_backward_input": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(DbHeadParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_dbhead_unpack_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_detector_forward_trunk": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_fpn_train_pack_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_fpn_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtd_fpn_train_forward": (C.c_int, [C.POINTER(FpnTaps), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "vtd_fpn_train_unpack_p2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_fpn_train_pack_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_fpn_train_backward": (C.c_int, [C.POINTER(FpnTaps), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.POINTER(FpnParams), C.c_void_p, C.c_void_p]),
     "vtd_binary_counts_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "vtd_trocr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vtd_trocr_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),

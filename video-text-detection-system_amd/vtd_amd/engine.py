@@ -228,6 +228,18 @@ class DetectorEngine(_Tunable):
             del keep
             return feats
 
+    def forward_trunk(self, x):
+        """The four trunk taps C2..C5 of the input as new padded-tap tensors, ring-padded NHWC fp16 [n,h+2,w+2,c] with h = w = 160, 80,
+        40, 20 (the layout the FPN training kernels read; include/vtd.h vtd_detector_forward_trunk).  Needs options fuse_fpn_head=0."""
+        wide = 4 if self.backbone == "resnet50" else 1
+        with self.lock:
+            n, keep = self._set_input(x)
+            taps = [torch.empty((n, (160 >> i) + 2, (160 >> i) + 2, (64 << i) * wide), dtype=torch.float16, device="cuda") for i in range(4)]
+            _native.check(self.lib.vtd_detector_forward_trunk(self.handle, n, *(C.c_void_p(t.data_ptr()) for t in taps), _stream_ptr()),
+                          "vtd_detector_forward_trunk")
+            del keep
+            return taps
+
     def read_tap(self, name, n):
         shapes = {"input": (3, 640, 640), "stem": (64, 320, 320), "pool": (64, 160, 160), "p2": (256, 160, 160), "head1": (64, 160, 160),
                   "head2": (64, 320, 320)}

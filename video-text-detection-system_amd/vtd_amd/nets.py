@@ -88,12 +88,89 @@ def trunk_out_channels(name):
 
 
 class FeaturePyramidNetwork(nn.Module):
-    """Same parameters as text_detector.py:31-41; the wiring (B.3 of SURVEY.md) is in the engine."""
+    """Same parameters as text_detector.py:31-41, in the wiring of SURVEY.md B.3 (the one the engine implements):
+    L5 = inner_blocks[0](C5), L(k) = inner_blocks[5-k](C(k)) + nearest-2x(L(k+1)), P2 = layer_blocks[3](L2).
+
+    ``fpn([C2, C3, C4, C5])`` on CUDA NCHW tensors (fp32 or fp16; C(k) has in_channels >> (5 - k) channels and each level is exactly twice
+    the size of the one above) returns P2 as ``[n,256,H,W]`` fp32 from the HIP training kernels (csrc/fpn_train.hip), differentiable
+    w.r.t. the ten live tensors (the four laterals and layer_blocks[3], weights and biases).  layer_blocks[0..2] are dead
+    (text_detector.py:56) and receive no gradient, as under torch autograd.  No gradient of the input features is formed: features that
+    require grad are refused."""
 
     def __init__(self, in_channels):
         super().__init__()
+        self.in_channels = in_channels
         self.inner_blocks = nn.ModuleList(nn.Conv2d(in_channels >> i, 256, 1) for i in range(4))
         self.layer_blocks = nn.ModuleList(nn.Conv2d(256, 256, 3, padding=1) for _ in range(4))
+
+    def live_parameters(self):
+        """The ten tensors that receive a gradient, in the kernels' order."""
+        return ([m.weight for m in self.inner_blocks] + [m.bias for m in self.inner_blocks] +
+                [self.layer_blocks[3].weight, self.layer_blocks[3].bias])
+
+    def _in_channels(self):
+        return self.inner_blocks[0].weight.shape[1]
+
+    def _geometry(self, shapes):
+        """(n, h5, w5, c5) from the four (n, C, H, W) shapes C2..C5, or ValueError."""
+        c5 = self._in_channels()
+        if c5 < 512 or c5 > 4096 or c5 % 512:
+            raise ValueError(f"the HIP FPN kernels need in_channels to be a multiple of 512 up to 4096, got {c5}")
+        n, _, h5, w5 = shapes[3]
+        for lv, shp in enumerate(shapes):
+            k = 3 - lv
+            if shp[1] != c5 >> k:
+                raise ValueError(f"FPN input C{lv + 2} must have {c5 >> k} channels, got {shp[1]}")
+            if shp[0] != n or shp[2] != h5 << k or shp[3] != w5 << k:
+                raise ValueError(f"FPN inputs must be exact doublings of C5 ({n}x{h5}x{w5}): C{lv + 2} must be [{n},{c5 >> k},{h5 << k},"
+                                 f"{w5 << k}], got {list(shp)}")
+        if n < 1 or h5 < 1 or w5 < 1:
+            raise ValueError("FPN inputs must not be empty")
+        return int(n), int(h5), int(w5), int(c5)
+
+    def _live_checked(self, device):
+        params = self.live_parameters()
+        for t in params:
+            if not t.is_cuda or t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("FeaturePyramidNetwork parameters must be contiguous float32 CUDA tensors on the features' device "
+                                 "(call .cuda() on the model)")
+        return params
+
+    def forward(self, features):
+        if not isinstance(features, (list, tuple)) or len(features) != 4 or not all(torch.is_tensor(t) and t.dim() == 4 for t in features):
+            raise ValueError("FeaturePyramidNetwork input must be the four [n,C,H,W] trunk taps [C2, C3, C4, C5]")
+        geom = self._geometry([tuple(t.shape) for t in features])
+        if any(t.requires_grad for t in features):
+            raise RuntimeError("FeaturePyramidNetwork: the input features require grad, but backward into the trunk is not built; "
+                               "only the FPN's own parameters receive a gradient (pass features.detach())")
+        if not all(t.is_cuda for t in features):
+            raise ValueError("FeaturePyramidNetwork runs on the HIP kernels: features must be CUDA (HIP) tensors")
+        params = self._live_checked(features[0].device)
+        return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *params)
+
+    def forward_padded(self, taps, head=None):
+        """The FPN on padded taps (ring-padded NHWC fp16 [n,h+2,w+2,C] for C2..C5, e.g. DetectorEngine.forward_trunk).  Without `head`:
+        P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
+        returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
+        to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if not isinstance(taps, (list, tuple)) or len(taps) != 4:
+            raise ValueError("padded taps must be the four tensors [C2, C3, C4, C5]")
+        for t in taps:
+            # the kernels trust the buffers' extents: a mismatch here would be a device-side out-of-bounds read
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
+                raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+        geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps])
+        params = self._live_checked(taps[0].device)
+        taps = tuple(t.detach() for t in taps)
+        if head is None:
+            return _fpn_forward_raw(taps, geom, [p.detach() for p in params])[0]
+        bns, hparams, hbuffers = head._train_operands(taps[0].device)
+        prob, thresh, _ = _FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), *params, *hparams)
+        if head.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
 
 
 def _db_branch(c):
@@ -123,6 +200,61 @@ def _head_struct(tensors):
     return st
 
 
+def _head_structs(params, buffers=None, grads=None):
+    tensors, gtensors = {}, {}
+    for b in range(2):
+        for i, (field, _, _) in enumerate(_HEAD_LEARNABLE):
+            tensors[(b, field)] = params[b * len(_HEAD_LEARNABLE) + i]
+            if grads is not None:
+                gtensors[(b, field)] = grads[b * len(_HEAD_LEARNABLE) + i]
+        if buffers is not None:
+            for i, (field, _, _) in enumerate(_HEAD_BUFFERS):
+                tensors[(b, field)] = buffers[b * len(_HEAD_BUFFERS) + i]
+    return _head_struct(tensors), (_head_struct(gtensors) if grads is not None else None)
+
+
+def _head_forward_raw(feats, hw, training, momentum, eps, buffers, params):
+    """vtd_dbhead_train_forward on padded features: (workspace, prob, thresh, stats)."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, (H, W) = feats.shape[0], hw
+    st, _ = _head_structs(params, buffers)
+    dev = feats.device
+    ws = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 0)), dtype=torch.uint8, device=dev)
+    prob = torch.empty((n, 1, 4 * H, 4 * W), dtype=torch.float32, device=dev)
+    thresh = torch.empty_like(prob)
+    stats = torch.empty((4, 2, 64), dtype=torch.float32, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _native.check(lib.vtd_dbhead_train_forward(ptr(feats), n, H, W, C.byref(st), 1 if training else 0, float(momentum), float(eps), ptr(ws),
+                                               ptr(prob), ptr(thresh), ptr(stats), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "vtd_dbhead_train_forward")
+    return ws, prob, thresh, stats
+
+
+def _head_backward_raw(feats, hw, training, ws, prob, thresh, params, grad_prob, grad_thresh, want_input):
+    """vtd_dbhead_train_backward (+ _backward_input): (the 20 gradients, dfeats, dscale); dfeats is NHWC fp32 [n,H,W,256] times dscale[0]."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, (H, W) = feats.shape[0], hw
+    grads = [torch.empty_like(p) for p in params]
+    st, gst = _head_structs(params, None, grads)
+    scratch = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 2 if want_input else 1)), dtype=torch.uint8, device=feats.device)
+    g = [None if t is None else t.to(torch.float32).contiguous() for t in (grad_prob, grad_thresh)]
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _native.check(lib.vtd_dbhead_train_backward(ptr(feats), n, H, W, C.byref(st), 1 if training else 0, ptr(ws), ptr(prob),
+                                                ptr(thresh), ptr(g[0]), ptr(g[1]), C.byref(gst), ptr(scratch), stream), "vtd_dbhead_train_backward")
+    dfeats = dscale = None
+    if want_input:
+        dfeats = torch.empty((n, H, W, 256), dtype=torch.float32, device=feats.device)   # NHWC, scaled by dscale[0]
+        dscale = torch.empty(2, dtype=torch.float32, device=feats.device)
+        _native.check(lib.vtd_dbhead_train_backward_input(n, H, W, C.byref(st), ptr(scratch), ptr(dfeats), ptr(dscale), stream),
+                      "vtd_dbhead_train_backward_input")
+    return grads, dfeats, dscale
+
+
 class _DBHeadTrainFn(torch.autograd.Function):
     """DBHead.forward on the HIP training kernels (csrc/dbhead_train.hip), differentiable w.r.t. the 20 learnable head tensors.  Inputs:
     padded features (include/vtd.h), `src`, (H, W), BatchNorm mode / momentum / eps, the four running-stat buffers per branch (updated in
@@ -132,28 +264,9 @@ class _DBHeadTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feats, src, hw, training, momentum, eps, buffers, *params):
-        import ctypes as C
-        from . import _native
-        lib = _native.require()
-        n, (H, W) = feats.shape[0], hw
-        tensors = {}
-        for b in range(2):
-            for i, (field, _, _) in enumerate(_HEAD_LEARNABLE):
-                tensors[(b, field)] = params[b * len(_HEAD_LEARNABLE) + i]
-            for i, (field, _, _) in enumerate(_HEAD_BUFFERS):
-                tensors[(b, field)] = buffers[b * len(_HEAD_BUFFERS) + i]
-        st = _head_struct(tensors)
-        dev = feats.device
-        ws = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 0)), dtype=torch.uint8, device=dev)
-        prob = torch.empty((n, 1, 4 * H, 4 * W), dtype=torch.float32, device=dev)
-        thresh = torch.empty_like(prob)
-        stats = torch.empty((4, 2, 64), dtype=torch.float32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        _native.check(lib.vtd_dbhead_train_forward(ptr(feats), n, H, W, C.byref(st), 1 if training else 0, float(momentum), float(eps), ptr(ws),
-                                                   ptr(prob), ptr(thresh), ptr(stats), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                      "vtd_dbhead_train_forward")
+        ws, prob, thresh, stats = _head_forward_raw(feats, hw, training, momentum, eps, buffers, params)
         ctx.save_for_backward(feats, prob, thresh, *params)
-        ctx.ws, ctx.hw, ctx.training = ws, (H, W), bool(training)
+        ctx.ws, ctx.hw, ctx.training = ws, tuple(hw), bool(training)
         ctx.src_dtype = None if src is None else src.dtype
         ctx.mark_non_differentiable(stats)
         return prob, thresh, stats
@@ -163,34 +276,149 @@ class _DBHeadTrainFn(torch.autograd.Function):
     def backward(ctx, grad_prob, grad_thresh, _grad_stats):
         import ctypes as C
         from . import _native
-        lib = _native.require()
         feats, prob, thresh, *params = ctx.saved_tensors
         n, (H, W) = feats.shape[0], ctx.hw
-        grads = [torch.empty_like(p) for p in params]
-        tensors, gtensors = {}, {}
-        for b in range(2):
-            for i, (field, _, _) in enumerate(_HEAD_LEARNABLE):
-                tensors[(b, field)] = params[b * len(_HEAD_LEARNABLE) + i]
-                gtensors[(b, field)] = grads[b * len(_HEAD_LEARNABLE) + i]
-        st, gst = _head_struct(tensors), _head_struct(gtensors)
         want_input = ctx.src_dtype is not None and ctx.needs_input_grad[1]
-        scratch = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 2 if want_input else 1)), dtype=torch.uint8, device=feats.device)
-        g = [None if t is None else t.to(torch.float32).contiguous() for t in (grad_prob, grad_thresh)]
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        _native.check(lib.vtd_dbhead_train_backward(ptr(feats), n, H, W, C.byref(st), 1 if ctx.training else 0, ptr(ctx.ws), ptr(prob),
-                                                    ptr(thresh), ptr(g[0]), ptr(g[1]), C.byref(gst), ptr(scratch),
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_dbhead_train_backward")
+        grads, dfeats, dscale = _head_backward_raw(feats, ctx.hw, ctx.training, ctx.ws, prob, thresh, params, grad_prob, grad_thresh, want_input)
         grad_src = None
         if want_input:
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            dfeats = torch.empty((n, H, W, 256), dtype=torch.float32, device=feats.device)   # NHWC, scaled by dscale[0]
-            dscale = torch.empty(2, dtype=torch.float32, device=feats.device)
-            _native.check(lib.vtd_dbhead_train_backward_input(n, H, W, C.byref(st), ptr(scratch), ptr(dfeats), ptr(dscale), stream),
-                          "vtd_dbhead_train_backward_input")
+            lib = _native.require()
+            ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
             grad_src = torch.empty((n, 256, H, W), dtype=torch.float32, device=feats.device)
-            _native.check(lib.vtd_dbhead_unpack_input_grad(ptr(dfeats), ptr(dscale), n, H, W, ptr(grad_src), stream), "vtd_dbhead_unpack_input_grad")
+            _native.check(lib.vtd_dbhead_unpack_input_grad(ptr(dfeats), ptr(dscale), n, H, W, ptr(grad_src),
+                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_dbhead_unpack_input_grad")
             grad_src = grad_src.to(ctx.src_dtype)
         return (None, grad_src, None, None, None, None, None, *grads)
+
+
+# ---- FPN training (csrc/fpn_train.hip).  geom = (n, h5, w5, c5 channels); taps = padded taps C2..C5; params = the ten live tensors:
+# inner_blocks[0..3].weight, inner_blocks[0..3].bias, layer_blocks[3].weight, layer_blocks[3].bias
+def _fpn_struct(tensors):
+    import ctypes as C
+    from . import _native
+    st = _native.FpnParams()
+    for i in range(4):
+        st.inner_w[i] = C.c_void_p(tensors[i].data_ptr())
+        st.inner_b[i] = C.c_void_p(tensors[4 + i].data_ptr())
+    st.layer_w = C.c_void_p(tensors[8].data_ptr())
+    st.layer_b = C.c_void_p(tensors[9].data_ptr())
+    return st
+
+
+def _fpn_taps(taps):
+    import ctypes as C
+    from . import _native
+    return _native.FpnTaps(*(C.c_void_p(t.data_ptr()) for t in taps))
+
+
+def _fpn_forward_raw(taps, geom, params):
+    """vtd_fpn_train_forward: (padded P2 [n,8 h5 + 2,8 w5 + 2,256] fp16, workspace)."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, h5, w5, c5 = geom
+    dev = taps[0].device
+    nbytes = int(lib.vtd_fpn_train_workspace_bytes(n, h5, w5, c5, 0))
+    _native.check(min(nbytes, 0), "vtd_fpn_train_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    p2 = torch.empty((n, 8 * h5 + 2, 8 * w5 + 2, 256), dtype=torch.float16, device=dev)
+    st, tp = _fpn_struct(params), _fpn_taps(taps)
+    _native.check(lib.vtd_fpn_train_forward(C.byref(tp), n, h5, w5, c5, C.byref(st), C.c_void_p(ws.data_ptr()), C.c_void_p(p2.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_forward")
+    return p2, ws
+
+
+def _fpn_backward_raw(taps, geom, params, ws, dp2, dscale):
+    """vtd_fpn_train_backward on dP2 as NHWC fp32 times dscale[0]: the ten gradients, in the order of `params`."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, h5, w5, c5 = geom
+    grads = [torch.empty_like(p) for p in params]
+    scratch = torch.empty(int(lib.vtd_fpn_train_workspace_bytes(n, h5, w5, c5, 1)), dtype=torch.uint8, device=dp2.device)
+    st, gst, tp = _fpn_struct(params), _fpn_struct(grads), _fpn_taps(taps)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _native.check(lib.vtd_fpn_train_backward(C.byref(tp), n, h5, w5, c5, C.byref(st), ptr(ws), ptr(dp2), ptr(dscale), C.byref(gst), ptr(scratch),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_backward")
+    return grads
+
+
+class _FPNTrainFn(torch.autograd.Function):
+    """The FPN alone on the HIP training kernels: padded taps in, P2 as [n,256,H,W] fp32 out, differentiable w.r.t. the ten live tensors."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, *params):
+        import ctypes as C
+        from . import _native
+        lib = _native.require()
+        p2p, ws = _fpn_forward_raw(taps, geom, params)
+        n, h5, w5, _ = geom
+        out = torch.empty((n, 256, 8 * h5, 8 * w5), dtype=torch.float32, device=p2p.device)
+        _native.check(lib.vtd_fpn_train_unpack_p2(C.c_void_p(p2p.data_ptr()), n, 8 * h5, 8 * w5, C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_unpack_p2")
+        ctx.save_for_backward(*params)
+        ctx.taps, ctx.geom, ctx.ws = taps, geom, ws
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        import ctypes as C
+        from . import _native
+        lib = _native.require()
+        n, h5, w5, _ = ctx.geom
+        g = grad_out.to(torch.float32).contiguous()
+        dp2 = torch.empty((n, 8 * h5, 8 * w5, 256), dtype=torch.float32, device=g.device)
+        _native.check(lib.vtd_fpn_train_pack_grad(C.c_void_p(g.data_ptr()), n, 8 * h5, 8 * w5, C.c_void_p(dp2.data_ptr()),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_pack_grad")
+        dscale = torch.ones(2, dtype=torch.float32, device=g.device)
+        grads = _fpn_backward_raw(ctx.taps, ctx.geom, ctx.saved_tensors, ctx.ws, dp2, dscale)
+        return (None, None, *grads)
+
+
+class _FPNHeadTrainFn(torch.autograd.Function):
+    """FPN -> DB head as one node: the backward hands the head's dP2 (NHWC fp32 with its power-of-two scale, as
+    vtd_dbhead_train_backward_input leaves it) straight to the FPN's backward, so the gradient never passes through an fp16 tensor or an
+    NCHW copy.  Inputs: padded taps, geom, BatchNorm mode / momentum / eps, the head's running-stat buffers, the FPN's ten tensors, the
+    head's twenty."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, buffers, *params):
+        fpn_params, head_params = params[:10], params[10:]
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        p2p, fws = _fpn_forward_raw(taps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, buffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, *params = ctx.saved_tensors
+        fpn_params, head_params = params[:10], params[10:]
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        fgrads = _fpn_backward_raw(ctx.taps, ctx.geom, fpn_params, ctx.fws, dp2, dscale)
+        return (None, None, None, None, None, None, *fgrads, *hgrads)
+
+
+def pack_tap(feature):
+    """[n,C,H,W] float32 / float16 CUDA tensor (C a multiple of 64) -> a padded tap (ring-padded NHWC fp16 [n,H+2,W+2,C]) on the device."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    x = feature.detach()
+    if x.dtype not in (torch.float32, torch.float16):
+        x = x.float()
+    x = x.contiguous()
+    n, ch, H, W = x.shape
+    out = torch.empty((n, H + 2, W + 2, ch), dtype=torch.float16, device=x.device)
+    _native.check(lib.vtd_fpn_train_pack_tap(C.c_void_p(x.data_ptr()), 0 if x.dtype == torch.float32 else 1, n, ch, H, W,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "vtd_fpn_train_pack_tap")
+    return out
 
 
 def pack_features(features):
@@ -244,6 +472,23 @@ class DBHead(nn.Module):
         input_grad=True)``."""
         return self._forward_padded(feats, H, W, None)
 
+    def _train_operands(self, device):
+        """(the four BatchNorms, the 20 learnable tensors, the 8 running-stat buffers) as the kernels take them, validated."""
+        if self.in_channels != 256:
+            raise ValueError("the HIP DB-head kernels are specialised for 256 input channels")
+        bns = [seq[i] for seq in self._branches() for i in (1, 4)]
+        if any(bn.momentum is None or bn.momentum != bns[0].momentum or bn.eps != bns[0].eps or not bn.track_running_stats for bn in bns):
+            raise ValueError("the HIP DB-head kernels need one fixed momentum and eps on all four BatchNorms, with running stats tracked")
+        params, buffers = [], []
+        for seq in self._branches():
+            params += [getattr(seq[i], a) for _, i, a in _HEAD_LEARNABLE]
+            buffers += [getattr(seq[i], a) for _, i, a in _HEAD_BUFFERS]
+        for t in params + buffers:
+            if not t.is_cuda or t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("DBHead parameters and buffers must be contiguous float32 CUDA tensors on the features' device "
+                                 "(call .cuda() on the model)")
+        return bns, params, buffers
+
     def _forward_padded(self, feats, H, W, src):
         if self.in_channels != 256:
             raise ValueError("the HIP DB-head kernels are specialised for 256 input channels")
@@ -253,17 +498,7 @@ class DBHead(nn.Module):
                 or H < 1 or W < 1 or feats.shape[0] < 1 or tuple(feats.shape[1:]) != (H + 2, W + 2, 256)):
             raise ValueError(f"padded features must be a contiguous float16 CUDA tensor [n,{H + 2},{W + 2},256] (H={H}, W={W}), got "
                              f"{tuple(feats.shape) if torch.is_tensor(feats) else type(feats).__name__}")
-        bns = [seq[i] for seq in self._branches() for i in (1, 4)]
-        if any(bn.momentum is None or bn.momentum != bns[0].momentum or bn.eps != bns[0].eps or not bn.track_running_stats for bn in bns):
-            raise ValueError("the HIP DB-head kernels need one fixed momentum and eps on all four BatchNorms, with running stats tracked")
-        params, buffers = [], []
-        for seq in self._branches():
-            params += [getattr(seq[i], a) for _, i, a in _HEAD_LEARNABLE]
-            buffers += [getattr(seq[i], a) for _, i, a in _HEAD_BUFFERS]
-        for t in params + buffers:
-            if not t.is_cuda or t.device != feats.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("DBHead parameters and buffers must be contiguous float32 CUDA tensors on the features' device "
-                                 "(call .cuda() on the model)")
+        bns, params, buffers = self._train_operands(feats.device)
         prob, thresh, _ = _DBHeadTrainFn.apply(feats, src, (int(H), int(W)), self.training, bns[0].momentum, bns[0].eps, tuple(buffers), *params)
         if self.training:
             with torch.no_grad():
@@ -344,18 +579,41 @@ class DBNet(_EngineOwner, nn.Module):
         """None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
         FPN -- their parameters stop requiring grad, and a forward in train mode runs trunk + FPN on a separate features engine (built
         with fuse_fpn_head=0, rebuilt only when trunk / FPN weights change) and the head on the HIP training kernels, differentiable
-        w.r.t. the head's parameters.  eval() forwards keep the fused inference engine, rebuilt after head updates."""
-        if trainable not in (None, "head"):
-            raise ValueError(f"trainable must be None or 'head', got {trainable!r}")
+        w.r.t. the head's parameters.  "head+fpn": fine-tune the FPN and the head over a frozen trunk -- the backbone's parameters stop
+        requiring grad, and a forward in train mode runs the trunk on a trunk engine (fuse_fpn_head=0, keyed on the backbone tensors
+        only: an optimizer step on FPN or head weights never rebuilds it), then the FPN and the head on the HIP training kernels as one
+        autograd node, differentiable w.r.t. the FPN's ten live tensors and the head's twenty.  The trunk's BatchNorms use their running
+        statistics (folded into the convolutions), as in "head" mode; backward through the trunk is not built.  eval() forwards keep
+        the fused inference engine, rebuilt after updates of the trained tensors."""
+        if trainable not in (None, "head", "head+fpn"):
+            raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         self.trainable = trainable
         if trainable == "head":
             for p in list(self.backbone.parameters()) + list(self.fpn.parameters()):
+                p.requires_grad_(False)
+        elif trainable == "head+fpn":
+            for p in self.backbone.parameters():
                 p.requires_grad_(False)
         self._head_versions = None
         return self
 
     def _head_tensor_versions(self):
-        return tuple(t._version for t in list(self.head.parameters()) + list(self.head.buffers()))
+        tensors = list(self.head.parameters()) + list(self.head.buffers())
+        if self.trainable == "head+fpn":
+            tensors += list(self.fpn.parameters())
+        return tuple(t._version for t in tensors)
+
+    def trunk_engine(self):
+        """The trunk engine of the "head+fpn" path (options fuse_fpn_head=0, see engine.DetectorEngine.forward_trunk)."""
+        from . import engine as _e
+        with self._engine_lock:
+            # keyed on the backbone tensors' versions only (load_state_dict bumps them): FPN and head updates never rebuild it
+            version = tuple(t._version for t in self.backbone.state_dict().values())
+            te = self.__dict__.get("_trunk_engine")
+            if te is None or self.__dict__.get("_trunk_version") != version:
+                te = _e.DetectorEngine(self.backbone_name, self.state_dict(), getattr(self, "_max_batch", None), options={"fuse_fpn_head": 0})
+                self._trunk_engine, self._trunk_version = te, version
+            return te
 
     def features_engine(self):
         """The trunk + FPN engine of the trainable path (options fuse_fpn_head=0, see engine.DetectorEngine.forward_features)."""
@@ -372,6 +630,7 @@ class DBNet(_EngineOwner, nn.Module):
     def __getstate__(self):
         state = super().__getstate__()
         state["_features_engine"] = None
+        state["_trunk_engine"] = None
         return state
 
     def engine(self):
@@ -391,9 +650,9 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable == "head":
+        if self.trainable in ("head", "head+fpn"):
             if self.training:
-                return self._forward_train_head(x)
+                return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
             # the inference engine packs the head on the host: rebuild it after an optimizer step (parameter versions) or a
             # train-mode forward (running statistics, mark_dirty)
             versions = self._head_tensor_versions()
@@ -413,6 +672,19 @@ class DBNet(_EngineOwner, nn.Module):
         feats = self.features_engine().forward_features(x)   # a new tensor per call: autograd may keep it
         out = self.head.forward_padded(feats, 160, 160)
         self.mark_dirty()   # the kernels updated the running statistics in place
+        return out
+
+    def _forward_train_head_fpn(self, x):
+        frozen = [n for n, p in self.backbone.named_parameters(prefix="backbone") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head+fpn'): {frozen[0]} requires grad, but backward through the trunk is not "
+                               "implemented; only the FPN and the DB head train (set requires_grad_(False) on backbone)")
+        for m in (self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = self.trunk_engine().forward_trunk(x)   # new tensors per call: autograd may keep them
+        out = self.fpn.forward_padded(taps, head=self.head)
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
 
