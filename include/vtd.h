@@ -226,7 +226,15 @@ int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_de
  * dp2_dev / dscale_dev are exactly what vtd_dbhead_train_backward_input writes: dP2 as NHWC float32 [n][H][W][256] times dscale_dev[0], and
  * {scale, 1 / scale}.  GEMM operands are fp16 with an exact power-of-two scale per tensor chosen on the device from max |.|; the sum-pool
  * chain dL(k+1) = sumpool2x2(dL(k)) and the bias sums are fp32 / fp64.  No atomics, shape-only grids: bitwise repeatable.  No gradient
- * of C2..C5 is formed.
+ * of C2..C5 is formed by this call.
+ * vtd_fpn_train_backward_input: the gradients of the taps, dC(k) = inner_w[5-k]^T dL(k), one GEMM per level (M = n h w, K = 256, N = the
+ * tap's channels).  Call it after vtd_fpn_train_backward, on the same stream, with the same scratch_dev, which must then have
+ * vtd_fpn_train_input_workspace_bytes (the backward's scratch with this call's buffers behind it; the backward writes the same bits into a
+ * scratch of either size).  level_mask: bit lv asks for the gradient of C(2 + lv).  dtaps_dev: four device pointers ordered C2..C5 (16-byte
+ * aligned; entries of levels not asked for are ignored); each requested one receives NHWC float32 [n][h][w][C] times an exact power of two.
+ * dscale_dev: [4][2] floats, row lv = {scale, 1 / scale} of dtaps_dev[lv] (rows of levels not asked for are left alone): the convention of
+ * vtd_dbhead_train_backward_input.  vtd_fpn_train_unpack_tap_grad: one such tensor and its {scale, 1 / scale} -> [n][C][H][W] float32 with
+ * the scale undone.
  * Errors: -2901 (handle built with the fused head entry), -2902 (argument / shape), -2903 (alignment). */
 typedef struct vtd_fpn_params {
     float *inner_w[4], *inner_b[4];
@@ -241,6 +249,41 @@ int vtd_fpn_train_unpack_p2(const void* p2_dev, int n, int height, int width, fl
 int vtd_fpn_train_pack_grad(const float* grad_nchw_dev, int n, int height, int width, float* dp2_dev, vtd_stream stream);
 int vtd_fpn_train_backward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, const void* workspace_dev,
                            const float* dp2_dev, const float* dscale_dev, const vtd_fpn_params* grads, void* scratch_dev, vtd_stream stream);
+int64_t vtd_fpn_train_input_workspace_bytes(int n, int h5, int w5, int c5_channels);
+int vtd_fpn_train_backward_input(int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, void* scratch_dev, int level_mask,
+                                 float* const* dtaps_dev, float* dscale_dev, vtd_stream stream);
+int vtd_fpn_train_unpack_tap_grad(const float* dtap_dev, const float* dscale_dev, int n, int channels, int height, int width, float* grad_nchw_dev,
+                                  vtd_stream stream);
+
+/* ---- ResNet BasicBlock training with frozen-statistics BatchNorm (csrc/resblock_train.hip): y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id),
+ * id = x or ds_bn(ds(x)).  The running statistics normalise and are never written, whatever mode the caller's module is in; gamma and beta
+ * are learnable and get the gradients torch's eval-mode BatchNorm gives them.  Tensors are padded taps (ring-padded NHWC fp16, ring 1):
+ * x_dev [n][h_in+2][w_in+2][cin], y_dev [n][h+2][w+2][width] with h = h_in / stride.  Parameters are torch's own float32 tensors as device
+ * pointers; weights are folded (w gamma rstd) and packed on the device in every call, so an in-place optimizer step is seen by the next call.
+ * Two geometries are built, the blocks of ResNet-18's layer4: (cin 256, width 512, stride 2, even h_in and w_in, with downsample: ds_*
+ * set) and (cin 512, width 512, stride 1, identity: ds_* ignored).  Every other geometry is refused with -3001.
+ * vtd_basicblock_train_workspace_bytes: mode 0 = the forward's workspace (kept for the backward: the post-ReLU activation a1 and the
+ * downsample's output), mode 1 = the backward's scratch.
+ * vtd_basicblock_train_backward: dy_dev is NHWC float32 [n][h][w][width] times dscale_dev[0] (a power of two; dscale_dev = {scale,
+ * 1 / scale}), y_dev the forward's output.  Gradients are written (not accumulated) into the grads struct's conv1_w, bn1_w, bn1_b, conv2_w,
+ * bn2_w, bn2_b and, with a downsample, ds_w, ds_bn_w, ds_bn_b (the *_mean / *_var fields are ignored).  Per convolution + BatchNorm pair,
+ * with g the gradient at the BatchNorm output, G = g^T x (MFMA, slabs summed in order) and s = sum g:  dW = gamma rstd G, dbeta = s,
+ * dgamma = rstd (sum_k w G - mean s): exact for gamma = 0, nothing divides by gamma.  dx_dev (optional): the input gradient as NHWC float32
+ * [n][h][w][512] times dxscale_dev[0], with dxscale_dev = {scale, 1 / scale}.  LIMITATION: the input gradient is formed for the stride-1
+ * block only; the stride-2 block would need a strided dgrad that is not built, and a non-NULL dx_dev is refused there with -3003.
+ * No atomics, shape-only grids: bitwise repeatable.
+ * Errors: -3001 (argument / unsupported geometry), -3002 (alignment), -3003 (input gradient of the stride-2 block). */
+typedef struct vtd_basicblock_params {
+    float *conv1_w, *bn1_w, *bn1_b, *bn1_mean, *bn1_var;
+    float *conv2_w, *bn2_w, *bn2_b, *bn2_mean, *bn2_var;
+    float *ds_w, *ds_bn_w, *ds_bn_b, *ds_bn_mean, *ds_bn_var;
+} vtd_basicblock_params;
+int64_t vtd_basicblock_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_basicblock_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                 float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                  float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                  const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */

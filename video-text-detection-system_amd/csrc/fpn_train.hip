@@ -15,6 +15,10 @@
 //   conv 3x3         dL2 = conv3x3^T(dP2): window rotated by 180 degrees, weights transposed, K = 2304 (conv_igemm.hip) -> fp32, scaled
 //   per level        dL(k+1) = sumpool2x2(dL(k)) in fp32 (the adjoint of the nearest up-sampling); reduce / finish / form; wgrad<2>
 //                    dW_inner[256][C_k] = sum_m dL(k)[m]^T C(k)[m]
+// Input gradients (on request, after the backward, from the dL(k) and scales it left in the scratch):
+//   per level        pack inner_w[5-k]^T as an fp16 panel [C_k][256]; form dL(k) times its scale as fp16 again (the bits the weight gradient
+//                    read); dC(k) = dL(k) inner_w[5-k]: one GEMM, M = n h w, K = 256, N = C_k (conv_igemm.hip as a 1x1 convolution over
+//                    the flat operand) -> NHWC fp32 at dL(k)'s total scale
 // Every reduction has a grid that depends on the shape only and a fixed summation order, and no atomics: bitwise repeatable.
 #include "vtd_common.h"
 #include "wgrad_mfma.h"
@@ -106,6 +110,22 @@ BwdLayout bwd_layout(const Geo& g) {
         slab = s > slab ? s : slab;
     }
     L.slab = take(slab);
+    L.total = o;
+    return L;
+}
+
+// the input-gradient call's buffers lie behind the backward's scratch, which keeps its own layout: the backward writes the same bits into
+// a scratch of either size
+struct InLayout {
+    int64_t wt[4], zero, total;
+};
+
+InLayout in_layout(const Geo& g) {
+    InLayout L;
+    int64_t o = bwd_layout(g).total;
+    auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
+    for (int lv = 0; lv < 4; ++lv) L.wt[lv] = take((int64_t)g.c[lv] * 256 * 2);
+    L.zero = take((int64_t)g.c[3] * 4);
     L.total = o;
     return L;
 }
@@ -220,6 +240,42 @@ __global__ __launch_bounds__(FT_THREADS) void fpn_train_pack_dgrad_weights_kerne
         wd3[i] = (half_t)lw[(co * 256 + ci) * 9 + (8 - tap)];
     } else if (i < 256 * 2304 + 256) {
         zero[i - 256 * 2304] = 0.f;
+    }
+}
+
+// wt [C][256]: row ci, k = co holds w[co][ci] (the lateral's weights transposed), rounded to fp16 as the forward packs it; a zero bias
+// row of C floats
+__global__ __launch_bounds__(FT_THREADS) void fpn_train_pack_input_weights_kernel(const float* w, int Cc, half_t* wt, float* zero) {
+    const int i = blockIdx.x * FT_THREADS + threadIdx.x;
+    if (i < 256 * Cc) {
+        const int ci = i >> 8, co = i & 255;
+        wt[i] = (half_t)w[co * Cc + ci];
+    } else if (i < 256 * Cc + Cc) {
+        zero[i - 256 * Cc] = 0.f;
+    }
+}
+
+// out[lv] = {total scale, 1 / total} of the requested levels, from the backward's per-stage scales
+__global__ void fpn_train_copy_scales_kernel(const float* sc, int mask, float* out) {
+    const int t = threadIdx.x, lv = t >> 1;
+    if (t < 8 && ((mask >> lv) & 1)) out[t] = sc[4 * (lv + 1) + (t & 1)];
+}
+
+// NHWC fp32 [n][HW][C] times sc[0] -> NCHW fp32 [n][C][HW], the scale undone (sc[1] = 1 / scale, exact: a power of two).  Workgroup =
+// 64 pixels of one image x 64 channels through an LDS tile.
+__global__ __launch_bounds__(FT_THREADS) void fpn_train_unpack_tap_grad_kernel(const float* g, const float* sc, int Cc, int HW, float* out) {
+    __shared__ float tile[64][65];
+    const int t = threadIdx.x, lane = t & 63, row = t >> 6;
+    const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, img = blockIdx.z;
+    const float inv = sc[1];
+    for (int r = row; r < 64; r += 4) {
+        const int p = p0 + r;
+        tile[r][lane] = p < HW ? g[((int64_t)img * HW + p) * Cc + c0 + lane] * inv : 0.f;
+    }
+    __syncthreads();
+    for (int r = row; r < 64; r += 4) {
+        const int p = p0 + lane;
+        if (p < HW) out[((int64_t)img * Cc + c0 + r) * HW + p] = tile[lane][r];
     }
 }
 
@@ -365,6 +421,21 @@ int64_t vtd_fpn_ws_bytes(int n, int h5, int w5, int c5, int mode) {
     Geo g;
     if (!make_geo(n, h5, w5, c5, g) || mode < 0 || mode > 1) return -2902;
     return mode ? bwd_layout(g).total : fwd_layout(g).total;
+}
+
+int64_t vtd_fpn_input_ws_bytes(int n, int h5, int w5, int c5) {
+    Geo g;
+    if (!make_geo(n, h5, w5, c5, g)) return -2902;
+    return in_layout(g).total;
+}
+
+int vtd_launch_fpn_unpack_tap_grad(const float* g, const float* sc, int n, int channels, int H, int W, float* out, hipStream_t s) {
+    if (!g || !sc || !out || n <= 0 || H <= 0 || W <= 0 || n > 65535 || channels < 64 || channels > 4096 || (channels & 63) ||
+        (int64_t)n * H * W * 4 >= (1ll << 31) || (int64_t)H * W * channels >= (1ll << 31))
+        return -2902;
+    if (((uintptr_t)g & 15) || ((uintptr_t)sc & 7) || ((uintptr_t)out & 3)) return -2903;
+    hipLaunchKernelGGL(fpn_train_unpack_tap_grad_kernel, dim3((H * W + 63) / 64, channels / 64, n), dim3(FT_THREADS), 0, s, g, sc, channels, H * W, out);
+    return -(int)hipGetLastError();
 }
 
 int vtd_launch_fpn_pack_tap(const void* x, int dtype, int n, int channels, int H, int W, void* out, hipStream_t s) {
@@ -517,4 +588,44 @@ int vtd_launch_fpn_backward(const void* const* taps, int n, int h5, int w5, int 
         VTD_HIP_CHECK(hipGetLastError());
     }
     return 0;
+}
+
+// dC(k) = dL(k) inner_w[5-k] for the levels of `mask` (bit lv = C(2 + lv)), from what vtd_launch_fpn_backward left in `scratch`
+int vtd_launch_fpn_backward_input(int n, int h5, int w5, int c5, const vtd_fpn_params* params, void* scratch, int mask, float* const* dtaps,
+                                  float* dscale, hipStream_t s) {
+    Geo g;
+    if (!params || !scratch || !dtaps || !dscale || mask < 1 || mask > 15 || !make_geo(n, h5, w5, c5, g)) return -2902;
+    for (int lv = 0; lv < 4; ++lv)
+        if ((mask >> lv) & 1)
+            if (!dtaps[lv] || !params->inner_w[3 - lv] || ((uintptr_t)params->inner_w[3 - lv] & 3)) return -2902;
+    if (((uintptr_t)scratch & 255) || ((uintptr_t)dscale & 7)) return -2903;
+    for (int lv = 0; lv < 4; ++lv)
+        if (((mask >> lv) & 1) && ((uintptr_t)dtaps[lv] & 15)) return -2903;
+    const BwdLayout B = bwd_layout(g);
+    const InLayout I = in_layout(g);
+    char* x = (char*)scratch;
+    half_t* ah = (half_t*)(x + B.ah);
+    const float* sc = (const float*)(x + B.sc);
+    float* zero = (float*)(x + I.zero);
+    int rc;
+    for (int lv = 0; lv < 4; ++lv) {
+        if (!((mask >> lv) & 1)) continue;
+        const int h = g.h[lv], w = g.w[lv], Cc = g.c[lv];
+        const int64_t m = g.m[lv];
+        half_t* wt = (half_t*)(x + I.wt[lv]);
+        hipLaunchKernelGGL(fpn_train_pack_input_weights_kernel, dim3(blocks_for((int64_t)256 * Cc + Cc)), dim3(FT_THREADS), 0, s,
+                           (const float*)params->inner_w[3 - lv], Cc, wt, zero);
+        // the operand the level's weight gradient read, formed again (the backward's `ah` holds the last level only)
+        hipLaunchKernelGGL(fpn_train_form_kernel, dim3(blocks_for(m * 32)), dim3(FT_THREADS), 0, s, (const float*)(x + B.dl[lv]), m, sc + 4 * (lv + 1), h, w,
+                           ah, (half_t*)nullptr);
+        VTD_HIP_CHECK(hipGetLastError());
+        ConvParams c = base_conv();   // a 1x1 convolution over the flat [n][h][w][256] operand (no ring)
+        c.in = ah; c.wgt = wt; c.bias = zero; c.out = dtaps[lv]; c.ldc = Cc; c.flags = EPI_OUT_F32;
+        c.cin_steps = 4; c.kw = 1; c.s_step = 256; c.r_step = w * 256;
+        c.M = (int)m; c.K = 256; c.cout = Cc; c.cout_pad = Cc; c.ho = h; c.wo = w;
+        c.in_hp = h; c.in_wp = w; c.in_c = 256; c.in_y0 = 0; c.in_x0 = 0;
+        if ((rc = vtd_launch_conv(c, -1, s))) return rc;
+    }
+    hipLaunchKernelGGL(fpn_train_copy_scales_kernel, dim3(1), dim3(64), 0, s, sc, mask, dscale);
+    return -(int)hipGetLastError();
 }

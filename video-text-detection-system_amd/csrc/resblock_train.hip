@@ -1,0 +1,416 @@
+// ResNet BasicBlock training with frozen-statistics BatchNorm (the running statistics normalise and are never written; gamma and beta
+// learn), forward and backward, for the two blocks of ResNet-18's layer4: (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).
+// Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
+//
+// Forward:
+//   fold             per convolution: w gamma rstd -> fp16 GEMM panel [512][ksz^2 cin] (k = tap * cin + ci), bias = beta - mean gamma rstd;
+//                    on the device, every call
+//   conv x 2 or 3    conv_igemm.hip: conv1 (3x3, stride s, ReLU) -> padded a1; downsample (1x1, stride 2) -> padded id; conv2 (3x3,
+//                    EPI_RESIDUAL from id or x, ReLU) -> padded y.  a1 and id stay in the workspace
+// Backward from dy (NHWC fp32 times a power of two):
+//   mask             g2 = dy (y > 0) in fp32: the gradient at bn2's output and of the identity path
+//   reduce / finish  per-channel fp64 sums s_c in a fixed order, max |.|, a power-of-two scale; form: the fp16 operands (flat and ring-padded)
+//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h (four 128-column tiles; 3x3 / 1x1 gather at stride 1 / 2), slabs
+//   param            slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s): no division by gamma
+//   dgrad            da1 = conv2^T(g2): conv_igemm.hip on the folded weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
+//   dx (stride 1)    conv1^T(g1) the same way, plus g2 brought to the same scale
+// No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
+#include "vtd_common.h"
+#include "wgrad_mfma.h"
+#include "../../include/vtd.h"
+
+#include <cstring>
+
+int vtd_launch_conv(const ConvParams& p, int cfg, hipStream_t stream);
+
+namespace {
+
+constexpr int RB_THREADS = 256;
+constexpr int RB_MAX_RED = 256;
+constexpr int RB_W = 512;   // block width
+constexpr float RB_SCALE_TARGET = 16384.0f;
+
+inline int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+inline unsigned nblk(int64_t items) { return (unsigned)((items + RB_THREADS - 1) / RB_THREADS); }
+
+struct Geo {
+    int n, hin, win, cin, stride, h, w;
+    int64_t m;
+    bool ds;
+};
+
+bool make_geo(int n, int hin, int win, int cin, int width, int stride, Geo& g) {
+    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096 || width != RB_W) return false;
+    if (!((cin == 256 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == 512 && stride == 1))) return false;
+    g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.stride = stride; g.h = hin / stride; g.w = win / stride;
+    g.m = (int64_t)n * g.h * g.w;
+    g.ds = stride == 2;
+    return (int64_t)n * (hin + 2) * (win + 2) * 512 < (1ll << 31);
+}
+
+struct FwdLayout { int64_t a1, id, w1, w2, wd, bias, total; };
+struct BwdLayout { int64_t g2, g1, g2h, g1h, g2p, g1p, wt, zero, part, pmax, sum2, sum1, sc, slab, total; };
+
+FwdLayout fwd_layout(const Geo& g) {
+    FwdLayout L;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
+    const int64_t pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * RB_W * 2;
+    L.a1 = take(pad); L.id = take(g.ds ? pad : 0);
+    L.w1 = take((int64_t)RB_W * 9 * g.cin * 2); L.w2 = take((int64_t)RB_W * 9 * RB_W * 2); L.wd = take(g.ds ? (int64_t)RB_W * g.cin * 2 : 0);
+    L.bias = take(3 * RB_W * 4);
+    L.total = o;
+    return L;
+}
+
+inline int wg_slabs(int64_t rows) { int64_t s = (rows + 4095) / 4096; return (int)(s < 1 ? 1 : s > 8 ? 8 : s); }
+inline int64_t slab_rows(int64_t rows, int s) { return ((rows + s - 1) / s + WG_KC - 1) / WG_KC * WG_KC; }
+
+BwdLayout bwd_layout(const Geo& g) {
+    BwdLayout L;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
+    const int64_t pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * RB_W * 2;
+    L.g2 = take(g.m * RB_W * 4); L.g1 = take(g.m * RB_W * 4);
+    L.g2h = take(g.m * RB_W * 2); L.g1h = take(g.m * RB_W * 2);
+    L.g2p = take(pad); L.g1p = take(pad);
+    L.wt = take((int64_t)RB_W * 9 * RB_W * 2);
+    L.zero = take(RB_W * 4);
+    L.part = take((int64_t)RB_MAX_RED * RB_W * 8); L.pmax = take(RB_MAX_RED * 4);
+    L.sum2 = take(RB_W * 8); L.sum1 = take(RB_W * 8);
+    L.sc = take(2 * 4 * 4);
+    L.slab = take((int64_t)wg_slabs(g.m) * RB_W * 9 * RB_W * 4);
+    L.total = o;
+    return L;
+}
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------------------
+// wp [512][ksz^2 cin], k = tap * cin + ci: half(w[co][ci][tap] gamma rstd); bias[co] = beta - mean gamma rstd
+__global__ __launch_bounds__(RB_THREADS) void rb_fold_kernel(const float* w, const float* gam, const float* bet, const float* mean, const float* var,
+                                                             float eps, int cin, int taps, half_t* wp, float* bias) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    const int K = taps * cin;
+    if (i < (int64_t)RB_W * K) {
+        const int co = (int)(i / K), k = (int)(i - (int64_t)co * K), tap = k / cin, ci = k - tap * cin;
+        const float sc = gam[co] / sqrtf(var[co] + eps);
+        wp[i] = (half_t)(w[((int64_t)co * cin + ci) * taps + tap] * sc);
+    } else if (i < (int64_t)RB_W * K + RB_W) {
+        const int co = (int)(i - (int64_t)RB_W * K);
+        bias[co] = bet[co] - mean[co] * (gam[co] / sqrtf(var[co] + eps));
+    }
+}
+
+// the one-pixel ring of a padded NHWC fp16 tensor of 512 channels.  One thread = 8 channels of one ring pixel.
+__global__ __launch_bounds__(RB_THREADS) void rb_zero_ring_kernel(half_t* t, int n, int H, int W) {
+    const int Hp = H + 2, Wp = W + 2, R = 2 * Wp + 2 * H;
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    if (i >= (int64_t)n * R * 64) return;
+    const int c8 = (int)(i & 63);
+    const int64_t q = i >> 6;
+    const int r = (int)(q % R), img = (int)(q / R);
+    int yp, xp;
+    if (r < Wp) { yp = 0; xp = r; }
+    else if (r < 2 * Wp) { yp = Hp - 1; xp = r - Wp; }
+    else { const int k = r - 2 * Wp; yp = 1 + (k >> 1); xp = (k & 1) ? Wp - 1 : 0; }
+    const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    *(half8*)(t + (((int64_t)img * Hp + yp) * Wp + xp) * RB_W + c8 * 8) = z;
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------------------------------
+// out[m][c] = v[m][c] where the padded activation at pixel m is positive, else 0.  One thread = 4 channels.
+__global__ __launch_bounds__(RB_THREADS) void rb_mask_kernel(const float* v, const half_t* act, int64_t rows, int H, int W, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    if (i >= rows * (RB_W / 4)) return;
+    const int cq = (int)(i & 127);
+    const int64_t m = i >> 7;
+    const int HW = H * W, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / W, x = rem - y * W;
+    const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (W + 2) + x + 1) * RB_W + 4 * cq;
+    const floatx4 f = *(const floatx4*)(v + i * 4);
+    floatx4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (float)a[e] > 0.f ? f[e] : 0.f;
+    *(floatx4*)(out + i * 4) = o;
+}
+
+// v [rows][512] fp32: thread t owns channels t and t + 256 over the rows of its workgroup, in row order: part[g][512] fp64, pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
+    const int t = threadIdx.x;
+    const int64_t m0 = (int64_t)blockIdx.x * per, m1 = m0 + per < rows ? m0 + per : rows;
+    double s0 = 0.0, s1 = 0.0;
+    float mx = 0.f;
+    for (int64_t m = m0; m < m1; ++m) {
+        const float a = v[m * RB_W + t], b = v[m * RB_W + 256 + t];
+        s0 += (double)a; s1 += (double)b;
+        const float fa = fabsf(a), fb = fabsf(b);
+        mx = fa > mx || fa != fa ? fa : mx;
+        mx = fb > mx || fb != fb ? fb : mx;
+    }
+    part[(int64_t)blockIdx.x * RB_W + t] = s0;
+    part[(int64_t)blockIdx.x * RB_W + 256 + t] = s1;
+    __shared__ float shm[RB_THREADS];
+    shm[t] = mx;
+    __syncthreads();
+    if (t == 0) {
+        float m = shm[0];
+        for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
+        pmax[blockIdx.x] = m;
+    }
+}
+
+// partials in workgroup order: sum[c] = the channel sum with the incoming scale undone (fp64); out_sc = {total scale, 1 / total,
+// this stage's multiplier, 0}, the multiplier a power of two from max |v| (1 when that is zero or not finite)
+__global__ __launch_bounds__(RB_THREADS) void rb_finish_kernel(const double* part, const float* pmax, int G, const float* in_sc, double* sum, float* out_sc) {
+    const int t = threadIdx.x;
+    for (int c = t; c < RB_W; c += RB_THREADS) {
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) s += part[(int64_t)g * RB_W + c];
+        sum[c] = s * (double)in_sc[1];
+    }
+    if (t == 0) {
+        float mx = pmax[0];
+        for (int g = 1; g < G; ++g) mx = pmax[g] > mx || pmax[g] != pmax[g] ? pmax[g] : mx;
+        const double tin = (double)in_sc[0];
+        int e = 0;
+        if (mx > 0.f && isfinite(mx)) e = (int)floor(log2((double)RB_SCALE_TARGET / (double)mx));
+        const int ein = (tin > 0.0 && isfinite(tin)) ? ilogb(tin) : 0;
+        int et = ein + e;
+        et = et < -120 ? -120 : et > 120 ? 120 : et;
+        e = et - ein;
+        const double tot = tin * ldexp(1.0, e);
+        out_sc[0] = (float)tot; out_sc[1] = (float)(1.0 / tot); out_sc[2] = ldexpf(1.0f, e); out_sc[3] = 0.f;
+    }
+}
+
+// v times the multiplier as fp16: flat [rows][512] and the interior of a ring-padded [n][H+2][W+2][512].  One thread = 8 channels.
+__global__ __launch_bounds__(RB_THREADS) void rb_form_kernel(const float* v, int64_t rows, const float* sc, int H, int W, half_t* flat, half_t* padded) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    if (i >= rows * 64) return;
+    const float mul = sc[2];
+    const floatx4 v0 = *(const floatx4*)(v + i * 8), v1 = *(const floatx4*)(v + i * 8 + 4);
+    half8 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { h[e] = (half_t)(v0[e] * mul); h[4 + e] = (half_t)(v1[e] * mul); }
+    *(half8*)(flat + i * 8) = h;
+    const int64_t m = i >> 6;
+    const int c8 = (int)(i & 63), HW = H * W;
+    const int img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / W, x = rem - y * W;
+    *(half8*)(padded + (((int64_t)img * (H + 2) + y + 1) * (W + 2) + x + 1) * RB_W + c8 * 8) = h;
+}
+
+// wt [512][9 * 512]: row ci, k = tap' * 512 + co holds half(w[co][ci][8 - tap'] gamma rstd) (the window rotated by 180 degrees, the folded
+// weights transposed, rounded as the forward packs them); a zero bias row
+__global__ __launch_bounds__(RB_THREADS) void rb_pack_dgrad_kernel(const float* w, const float* gam, const float* var, float eps, half_t* wt, float* zero) {
+    const int i = blockIdx.x * RB_THREADS + threadIdx.x;
+    if (i < RB_W * 9 * RB_W) {
+        const int ci = i / (9 * RB_W), k = i - ci * 9 * RB_W, tap = k / RB_W, co = k - tap * RB_W;
+        wt[i] = (half_t)(w[((int64_t)co * RB_W + ci) * 9 + (8 - tap)] * (gam[co] / sqrtf(var[co] + eps)));
+    } else if (i < RB_W * 9 * RB_W + RB_W) {
+        zero[i - RB_W * 9 * RB_W] = 0.f;
+    }
+}
+
+// One workgroup per output channel c.  G[c][k] = the slabs summed in slab order (fp64) with the scale undone, k = tap * cin + ci;
+// dW[c][ci][tap] = gamma rstd G; dbeta = s; dgamma = rstd (sum_k w[c][k] G[c][k] - mean s), the sum in fp64 in a fixed tree order
+__global__ __launch_bounds__(RB_THREADS) void rb_param_kernel(const float* slab, int S, int cin, int taps, const float* sc, const double* sum, const float* w,
+                                                              const float* gam, const float* mean, const float* var, float eps, float* dw, float* dgam,
+                                                              float* dbet) {
+    const int c = blockIdx.x, t = threadIdx.x, K = taps * cin;
+    const double rstd = 1.0 / sqrt((double)var[c] + (double)eps), inv = (double)sc[1], f = (double)gam[c] * rstd;
+    const int64_t nel = (int64_t)RB_W * K;
+    double dot = 0.0;
+    for (int k = t; k < K; k += RB_THREADS) {
+        double G = 0.0;
+        for (int s = 0; s < S; ++s) G += (double)slab[(int64_t)s * nel + (int64_t)c * K + k];
+        G *= inv;
+        const int tap = k / cin, ci = k - tap * cin;
+        const int64_t wi = ((int64_t)c * cin + ci) * taps + tap;
+        dw[wi] = (float)(f * G);
+        dot += (double)w[wi] * G;
+    }
+    __shared__ double sh[RB_THREADS];
+    sh[t] = dot;
+    __syncthreads();
+    for (int o = RB_THREADS / 2; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        dgam[c] = (float)(rstd * (sh[0] - (double)mean[c] * sum[c]));
+        dbet[c] = (float)sum[c];
+    }
+}
+
+// dx = conv1^T(g1) (at g1's total scale) + g2 (at the incoming scale) brought to that scale: both multipliers are powers of two
+__global__ __launch_bounds__(RB_THREADS) void rb_add_identity_kernel(float* dx, const float* g2, int64_t items, const float* sc2, const float* sc1) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const float mul = sc2[2] * sc1[2];
+    floatx4 a = *(floatx4*)(dx + i * 4);
+    const floatx4 b = *(const floatx4*)(g2 + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] += b[e] * mul;
+    *(floatx4*)(dx + i * 4) = a;
+}
+
+__global__ void rb_copy_scale_kernel(const float* sc, float* out) {
+    if (threadIdx.x < 2) out[threadIdx.x] = sc[threadIdx.x];
+}
+
+bool bn_ok(const float* w, const float* b, const float* m, const float* v) {
+    return w && b && m && v && !(((uintptr_t)w | (uintptr_t)b | (uintptr_t)m | (uintptr_t)v) & 3);
+}
+
+bool params_ok(const vtd_basicblock_params* p, bool ds) {
+    if (!p || !p->conv1_w || !p->conv2_w || (((uintptr_t)p->conv1_w | (uintptr_t)p->conv2_w) & 3)) return false;
+    if (!bn_ok(p->bn1_w, p->bn1_b, p->bn1_mean, p->bn1_var) || !bn_ok(p->bn2_w, p->bn2_b, p->bn2_mean, p->bn2_var)) return false;
+    if (ds && (!p->ds_w || ((uintptr_t)p->ds_w & 3) || !bn_ok(p->ds_bn_w, p->ds_bn_b, p->ds_bn_mean, p->ds_bn_var))) return false;
+    return true;
+}
+
+bool grads_ok(const vtd_basicblock_params* p, bool ds) {
+    if (!p || !p->conv1_w || !p->conv2_w || !p->bn1_w || !p->bn1_b || !p->bn2_w || !p->bn2_b) return false;
+    if (ds && (!p->ds_w || !p->ds_bn_w || !p->ds_bn_b)) return false;
+    return true;
+}
+
+ConvParams base_conv() {
+    ConvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.k_hi_step = 32;
+    p.stride = 1;
+    return p;
+}
+
+// a 3x3 (pad 1) or 1x1 (pad 0) convolution of a padded tap at `stride` into `M` rows of 512 columns
+ConvParams conv_of(const Geo& g, const half_t* in, int cin, int hin, int win, int ksz, int stride, const half_t* wgt, const float* bias) {
+    ConvParams c = base_conv();
+    c.in = in; c.wgt = wgt; c.bias = bias;
+    c.cin_steps = cin / 64; c.kw = ksz; c.s_step = cin; c.r_step = (win + 2) * cin;
+    c.M = (int)g.m; c.K = ksz * ksz * cin; c.cout = RB_W; c.cout_pad = RB_W; c.ho = g.h; c.wo = g.w;
+    c.in_hp = hin + 2; c.in_wp = win + 2; c.in_c = cin; c.in_y0 = c.in_x0 = ksz == 3 ? 0 : 1; c.stride = stride;
+    return c;
+}
+
+void to_padded(ConvParams& c, const Geo& g, half_t* out) {
+    c.out = out; c.out_hp = g.h + 2; c.out_wp = g.w + 2; c.out_c = RB_W; c.out_ring = 1;
+}
+
+}  // namespace
+
+int64_t vtd_basicblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    Geo g;
+    if (!make_geo(n, hin, win, cin, width, stride, g) || mode < 0 || mode > 1) return -3001;
+    return mode ? bwd_layout(g).total : fwd_layout(g).total;
+}
+
+int vtd_launch_basicblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                  void* ws, void* y, hipStream_t s) {
+    Geo g;
+    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, g) || !params_ok(P, g.ds) || !(eps > 0.f)) return -3001;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255)) return -3002;
+    const FwdLayout L = fwd_layout(g);
+    char* w = (char*)ws;
+    half_t *a1 = (half_t*)(w + L.a1), *id = (half_t*)(w + L.id), *w1 = (half_t*)(w + L.w1), *w2 = (half_t*)(w + L.w2), *wd = (half_t*)(w + L.wd);
+    float* bias = (float*)(w + L.bias);
+    hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)RB_W * 9 * cin + RB_W)), dim3(RB_THREADS), 0, s, (const float*)P->conv1_w, (const float*)P->bn1_w,
+                       (const float*)P->bn1_b, (const float*)P->bn1_mean, (const float*)P->bn1_var, eps, cin, 9, w1, bias);
+    hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)RB_W * 9 * RB_W + RB_W)), dim3(RB_THREADS), 0, s, (const float*)P->conv2_w, (const float*)P->bn2_w,
+                       (const float*)P->bn2_b, (const float*)P->bn2_mean, (const float*)P->bn2_var, eps, RB_W, 9, w2, bias + RB_W);
+    if (g.ds)
+        hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)RB_W * cin + RB_W)), dim3(RB_THREADS), 0, s, (const float*)P->ds_w, (const float*)P->ds_bn_w,
+                           (const float*)P->ds_bn_b, (const float*)P->ds_bn_mean, (const float*)P->ds_bn_var, eps, cin, 1, wd, bias + 2 * RB_W);
+    const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * 64);
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, a1, n, g.h, g.w);
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, (half_t*)y, n, g.h, g.w);
+    VTD_HIP_CHECK(hipGetLastError());
+    int rc;
+    ConvParams c = conv_of(g, (const half_t*)x, cin, hin, win, 3, stride, w1, bias);
+    c.flags = EPI_RELU;
+    to_padded(c, g, a1);
+    if ((rc = vtd_launch_conv(c, -1, s))) return rc;
+    if (g.ds) {
+        ConvParams d = conv_of(g, (const half_t*)x, cin, hin, win, 1, 2, wd, bias + 2 * RB_W);
+        to_padded(d, g, id);
+        if ((rc = vtd_launch_conv(d, -1, s))) return rc;
+    }
+    ConvParams e = conv_of(g, a1, RB_W, g.h, g.w, 3, 1, w2, bias + RB_W);
+    e.flags = EPI_RELU | EPI_RESIDUAL;
+    e.res = g.ds ? id : (const half_t*)x; e.res_hp = g.h + 2; e.res_wp = g.w + 2; e.res_ring = 1; e.res_shift = 0;
+    to_padded(e, g, (half_t*)y);
+    return vtd_launch_conv(e, -1, s);
+}
+
+int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                   const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                   float* dx, float* dxscale, hipStream_t s) {
+    Geo g;
+    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
+        !(eps > 0.f) || (dx && !dxscale))
+        return -3001;
+    if (dx && g.stride != 1) return -3003;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dy & 15) || ((uintptr_t)dscale & 7) ||
+        ((uintptr_t)dx & 15) || ((uintptr_t)dxscale & 7))
+        return -3002;
+    const FwdLayout L = fwd_layout(g);
+    const BwdLayout B = bwd_layout(g);
+    char* q = (char*)scratch;
+    const half_t* a1 = (const half_t*)((const char*)ws + L.a1);
+    float *g2 = (float*)(q + B.g2), *g1 = (float*)(q + B.g1), *zero = (float*)(q + B.zero), *pmax = (float*)(q + B.pmax), *sc = (float*)(q + B.sc),
+          *slab = (float*)(q + B.slab);
+    half_t *g2h = (half_t*)(q + B.g2h), *g1h = (half_t*)(q + B.g1h), *g2p = (half_t*)(q + B.g2p), *g1p = (half_t*)(q + B.g1p), *wt = (half_t*)(q + B.wt);
+    double *part = (double*)(q + B.part), *sum2 = (double*)(q + B.sum2), *sum1 = (double*)(q + B.sum1);
+    float *sc2 = sc, *sc1 = sc + 4;
+    const int64_t M = g.m;
+    int Gr = (int)((M + 255) / 256);
+    Gr = Gr < 1 ? 1 : Gr > RB_MAX_RED ? RB_MAX_RED : Gr;
+    const int64_t per = (M + Gr - 1) / Gr;
+    const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * 64);
+    const int S = wg_slabs(M);
+    int rc;
+
+    auto stage = [&](const float* v, const half_t* act, float* gout, const float* in_sc, double* sum, float* out_sc, half_t* flat, half_t* padded) {
+        hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * 128)), dim3(RB_THREADS), 0, s, v, act, M, g.h, g.w, gout);
+        hipLaunchKernelGGL(rb_reduce_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, part, pmax);
+        hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(RB_THREADS), 0, s, (const double*)part, (const float*)pmax, Gr, in_sc, sum, out_sc);
+        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, padded, n, g.h, g.w);
+        hipLaunchKernelGGL(rb_form_kernel, dim3(nblk(M * 64)), dim3(RB_THREADS), 0, s, (const float*)gout, M, (const float*)out_sc, g.h, g.w, flat, padded);
+    };
+    auto wgrad = [&](const half_t* a, const half_t* xin, int xc, int hi, int wi, int ksz, int st, const float* scl, const double* sum, const float* w,
+                     const float* gam, const float* mean, const float* var, float* dw, float* dgam, float* dbet) {
+        WgArgs wa;
+        wa.a = a; wa.lda = RB_W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
+        wa.slab_len = slab_rows(M, S); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
+        hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(ksz * ksz * xc / 128 * S, 4), dim3(WG_THREADS), 0, s, wa);
+        hipLaunchKernelGGL(rb_param_kernel, dim3(RB_W), dim3(RB_THREADS), 0, s, (const float*)slab, S, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
+                           dbet);
+    };
+    auto dgrad = [&](const half_t* gp, const float* w, const float* gam, const float* var, float* out) {
+        hipLaunchKernelGGL(rb_pack_dgrad_kernel, dim3(nblk(RB_W * 9 * RB_W + RB_W)), dim3(RB_THREADS), 0, s, w, gam, var, eps, wt, zero);
+        ConvParams c = conv_of(g, gp, RB_W, g.h, g.w, 3, 1, wt, zero);
+        c.out = out; c.ldc = RB_W; c.flags = EPI_OUT_F32;
+        return vtd_launch_conv(c, -1, s);
+    };
+
+    // g2 = dy (y > 0): the gradient at bn2's output, of the downsample's BatchNorm output, and of an identity input
+    stage(dy, (const half_t*)y, g2, dscale, sum2, sc2, g2h, g2p);
+    VTD_HIP_CHECK(hipGetLastError());
+    wgrad(g2h, a1, RB_W, g.h, g.w, 3, 1, sc2, sum2, (const float*)P->conv2_w, (const float*)P->bn2_w, (const float*)P->bn2_mean, (const float*)P->bn2_var,
+          Gp->conv2_w, Gp->bn2_w, Gp->bn2_b);
+    if (g.ds)
+        wgrad(g2h, (const half_t*)x, cin, hin, win, 1, 2, sc2, sum2, (const float*)P->ds_w, (const float*)P->ds_bn_w, (const float*)P->ds_bn_mean,
+              (const float*)P->ds_bn_var, Gp->ds_w, Gp->ds_bn_w, Gp->ds_bn_b);
+    VTD_HIP_CHECK(hipGetLastError());
+    // da1 = conv2^T(g2) into the g1 buffer, masked in place by a1 > 0
+    if ((rc = dgrad(g2p, (const float*)P->conv2_w, (const float*)P->bn2_w, (const float*)P->bn2_var, g1))) return rc;
+    stage(g1, a1, g1, sc2, sum1, sc1, g1h, g1p);
+    wgrad(g1h, (const half_t*)x, cin, hin, win, 3, stride, sc1, sum1, (const float*)P->conv1_w, (const float*)P->bn1_w, (const float*)P->bn1_mean,
+          (const float*)P->bn1_var, Gp->conv1_w, Gp->bn1_w, Gp->bn1_b);
+    VTD_HIP_CHECK(hipGetLastError());
+    if (dx) {
+        if ((rc = dgrad(g1p, (const float*)P->conv1_w, (const float*)P->bn1_w, (const float*)P->bn1_var, dx))) return rc;
+        hipLaunchKernelGGL(rb_add_identity_kernel, dim3(nblk(M * 128)), dim3(RB_THREADS), 0, s, dx, (const float*)g2, M * 128, (const float*)sc2,
+                           (const float*)sc1);
+        hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
+    }
+    return -(int)hipGetLastError();
+}

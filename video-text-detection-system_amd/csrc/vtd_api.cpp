@@ -70,6 +70,16 @@ int vtd_launch_fpn_pack_grad(const float* g, int n, int H, int W, float* out, hi
 int vtd_launch_fpn_forward(const void* const* taps, int n, int h5, int w5, int c5, const vtd_fpn_params* params, void* ws, void* p2_out, hipStream_t s);
 int vtd_launch_fpn_backward(const void* const* taps, int n, int h5, int w5, int c5, const vtd_fpn_params* params, const void* ws, const float* dp2,
                             const float* dscale, const vtd_fpn_params* grads, void* scratch, hipStream_t s);
+int64_t vtd_fpn_input_ws_bytes(int n, int h5, int w5, int c5);
+int vtd_launch_fpn_backward_input(int n, int h5, int w5, int c5, const vtd_fpn_params* params, void* scratch, int mask, float* const* dtaps,
+                                  float* dscale, hipStream_t s);
+int64_t vtd_basicblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_basicblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                  void* ws, void* y, hipStream_t s);
+int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                   const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                   float* dx, float* dxscale, hipStream_t s);
+int vtd_launch_fpn_unpack_tap_grad(const float* g, const float* sc, int n, int channels, int H, int W, float* out, hipStream_t s);
 int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
                                const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
                                void* scratch, hipStream_t s);
@@ -1415,6 +1425,9 @@ const char* vtd_strerror(int code) {
         case -2901: return "trunk export needs a detector finalized with fuse_fpn_head=0 (the fused graph pads C2 for the composed head entry)";
         case -2902: return "FPN training: invalid argument or shape";
         case -2903: return "FPN training: misaligned buffer";
+        case -3001: return "BasicBlock training: invalid argument or unsupported geometry (built: 256 -> 512 stride 2 with even extents, 512 -> 512 stride 1)";
+        case -3002: return "BasicBlock training: misaligned buffer";
+        case -3003: return "BasicBlock training: the input gradient of the stride-2 block is not built (it needs a strided dgrad)";
         default: break;
     }
     if (code <= -1000) {
@@ -1497,6 +1510,35 @@ int vtd_fpn_train_pack_grad(const float* grad_nchw_dev, int n, int height, int w
 int vtd_fpn_train_backward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, const void* workspace_dev,
                            const float* dp2_dev, const float* dscale_dev, const vtd_fpn_params* grads, void* scratch_dev, vtd_stream stream) {
     return vtd_launch_fpn_backward(taps, n, h5, w5, c5_channels, params, workspace_dev, dp2_dev, dscale_dev, grads, scratch_dev, (hipStream_t)stream);
+}
+
+// ---- BasicBlock training (resblock_train.hip)
+int64_t vtd_basicblock_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_basicblock_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_basicblock_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                 float eps, void* workspace_dev, void* y_dev, vtd_stream stream) {
+    return vtd_launch_basicblock_forward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, (hipStream_t)stream);
+}
+
+int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                  float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                  const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
+    return vtd_launch_basicblock_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
+                                          scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+int64_t vtd_fpn_train_input_workspace_bytes(int n, int h5, int w5, int c5_channels) { return vtd_fpn_input_ws_bytes(n, h5, w5, c5_channels); }
+
+int vtd_fpn_train_backward_input(int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, void* scratch_dev, int level_mask,
+                                 float* const* dtaps_dev, float* dscale_dev, vtd_stream stream) {
+    return vtd_launch_fpn_backward_input(n, h5, w5, c5_channels, params, scratch_dev, level_mask, dtaps_dev, dscale_dev, (hipStream_t)stream);
+}
+
+int vtd_fpn_train_unpack_tap_grad(const float* dtap_dev, const float* dscale_dev, int n, int channels, int height, int width, float* grad_nchw_dev,
+                                  vtd_stream stream) {
+    return vtd_launch_fpn_unpack_tap_grad(dtap_dev, dscale_dev, n, channels, height, width, grad_nchw_dev, (hipStream_t)stream);
 }
 
 int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_dev, int n, int height, int width, float* grad_nchw_dev,

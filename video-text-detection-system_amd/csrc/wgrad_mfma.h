@@ -6,6 +6,9 @@
 //   per q-tile: 4 q-tiles.
 // MODE 2 (conv 1x1, the FPN laterals): A as MODE 0, B = the centre pixel of a ring-padded tensor of xc channels (a multiple of 64),
 //   q-tile qt = channels 128 qt .. 128 qt + 127; columns at or past xc load zeros and are not stored (ResNet-18's C2 has 64 channels).
+// MODE 3 (a ResNet block's convolutions): A as MODE 0 with gridDim.y 128-column tiles (four for a 512-wide gradient), B = the ksz x ksz
+//   window (ksz = 3: pad 1, ksz = 1: pad 0) at stride `stride` of a ring-padded input of xc channels (a multiple of 128) and Hin x Win
+//   pixels; q = tap * xc + ci, q-tile qt = 128 channels of tap 128 qt / xc: ksz^2 xc / 128 q-tiles.  slab [128 gridDim.y][ksz^2 xc].
 // Workgroup = 4 waves, one (q-tile, slab); each wave a (P_T / 2) x 64 block.  Per K chunk of 32 rows every thread loads rows 8o .. 8o+7
 // of one column pair of A and B with 4-byte loads (the next chunk's loads are in flight during this chunk's MFMAs), transposes them into
 // LDS as [row octet][column][8] so that a fragment (8 consecutive rows of one column) is one 16-byte read, double-buffered: one barrier
@@ -28,6 +31,7 @@ struct WgArgs {
     int n, H, W;
     int64_t rows, slab_len;
     float* slab;
+    int ksz, stride, Hin, Win;   // MODE 3 only
 };
 
 template <int MODE>
@@ -38,15 +42,18 @@ __device__ __forceinline__ const half_t* wg_brow(const WgArgs& A, int img, int y
     } else if constexpr (MODE == 1) {
         const int b = qt >> 1, tap = (qt & 1) * 2 + grp, ky = tap >> 1, kx = tap & 1;
         return A.x + (((int64_t)img * 2 * A.H + 2 * y + ky) * 2 * A.W + 2 * xx + kx) * 128 + b * 64;
-    } else {
+    } else if constexpr (MODE == 2) {
         return A.x + (((int64_t)img * (A.H + 2) + y + 1) * (A.W + 2) + xx + 1) * A.xc + qt * 128 + grp * 64;
+    } else {
+        const int q0 = qt * 128, tap = q0 / A.xc, c0 = q0 - tap * A.xc, ky = tap / A.ksz, kx = tap - ky * A.ksz, o = 1 - (A.ksz >> 1);
+        return A.x + (((int64_t)img * (A.Hin + 2) + y * A.stride + ky + o) * (A.Win + 2) + xx * A.stride + kx + o) * A.xc + c0 + grp * 64;
     }
 }
 
 template <int MODE>
 __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const WgArgs A) {
     constexpr int PT = MODE == 1 ? 64 : 128, QT = 128, FP = PT / 32, FQ = 4;
-    const int NQT = MODE == 0 ? 18 : MODE == 1 ? 4 : (A.xc + 127) / 128;
+    const int NQT = MODE == 0 ? 18 : MODE == 1 ? 4 : MODE == 2 ? (A.xc + 127) / 128 : A.ksz * A.ksz * A.xc / 128;
     const int qt = blockIdx.x % NQT, sl = blockIdx.x / NQT, pt = blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wp = w >> 1, wq = w & 1;
     const int a_col0 = MODE == 1 ? (qt >> 1) * 128 : pt * 128;   // MODE 1: the hi half of the branch's a1 pair
@@ -133,7 +140,7 @@ __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const Wg
     }
 
     // C row p = wp * PT/2 + i*16 + 4*(lane>>4) + e, column q = wq*64 + j*16 + (lane&15)
-    const int ldq = MODE == 0 ? 2304 : MODE == 1 ? 256 : A.xc;
+    const int ldq = MODE == 0 ? 2304 : MODE == 1 ? 256 : MODE == 2 ? A.xc : A.ksz * A.ksz * A.xc;
     const int64_t slab_elems = MODE == 1 ? 2 * 64 * 256 : (int64_t)gridDim.y * 128 * ldq;
     float* out = A.slab + (int64_t)sl * slab_elems;
     const int p_base = MODE == 1 ? (qt >> 1) * 64 : pt * 128;

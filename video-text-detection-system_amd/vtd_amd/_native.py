@@ -48,6 +48,15 @@ class FpnParams(C.Structure):
     _fields_ = [("inner_w", C.c_void_p * 4), ("inner_b", C.c_void_p * 4), ("layer_w", C.c_void_p), ("layer_b", C.c_void_p)]
 
 
+BLOCK_FIELDS = ("conv1_w", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "conv2_w", "bn2_w", "bn2_b", "bn2_mean", "bn2_var",
+                "ds_w", "ds_bn_w", "ds_bn_b", "ds_bn_mean", "ds_bn_var")
+
+
+class BasicBlockParams(C.Structure):
+    """vtd_basicblock_params of include/vtd.h: device pointers to one BasicBlock's fp32 tensors, PyTorch layouts"""
+    _fields_ = [(k, C.c_void_p) for k in BLOCK_FIELDS]
+
+
 FpnTaps = C.c_void_p * 4   # padded taps C2, C3, C4, C5
 
 
@@ -128,6 +137,14 @@ SIGNATURES = {
     "vtd_fpn_train_pack_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_fpn_train_backward": (C.c_int, [C.POINTER(FpnTaps), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.POINTER(FpnParams), C.c_void_p, C.c_void_p]),
+    "vtd_basicblock_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
+    "vtd_basicblock_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_basicblock_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(BasicBlockParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_fpn_train_input_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtd_fpn_train_backward_input": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_int, C.POINTER(FpnTaps),
+                                               C.c_void_p, C.c_void_p]),
+    "vtd_fpn_train_unpack_tap_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_binary_counts_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "vtd_trocr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vtd_trocr_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),

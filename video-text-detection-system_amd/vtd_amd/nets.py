@@ -35,6 +35,11 @@ class _Residual(nn.Module):
 
 
 class BasicBlock(_Residual):
+    """ResNet BasicBlock.  ``block(x)`` on a CUDA NCHW tensor (fp32 or fp16) runs the block on the HIP training kernels
+    (csrc/resblock_train.hip) with frozen-statistics BatchNorm -- the running statistics normalise and are never written, whatever
+    ``training`` says -- and returns ``[n,width,h,w]`` fp32, differentiable w.r.t. the block's learnable tensors (convolution weights,
+    BatchNorm gamma and beta) and, for the stride-1 block, w.r.t. ``x``.  Built geometries: ResNet-18's layer4 (256 -> 512 stride 2 with
+    downsample and even extents, 512 -> 512 stride 1)."""
     expansion = 1
 
     def __init__(self, cin, width, stride):
@@ -44,6 +49,41 @@ class BasicBlock(_Residual):
         self.stride = stride
         if stride != 1 or cin != width:
             self.downsample = nn.Sequential(*_conv_bn(cin, width, 1, stride, 0))
+
+    def _train_operands(self, device):
+        """((cin, width, stride), eps, the learnable tensors, the running statistics) as the kernels take them, validated."""
+        cin, width = self.conv1.in_channels, self.conv1.out_channels
+        ds = hasattr(self, "downsample")
+        if (cin, width, self.stride, ds) not in ((256, 512, 2, True), (512, 512, 1, False)):
+            raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): the HIP training kernels are built for ResNet-18's layer4 only "
+                               "(256 -> 512 stride 2 with downsample, 512 -> 512 stride 1)")
+        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)] + ([(self.downsample[0], self.downsample[1])] if ds else [])
+        if any(bn.eps != self.bn1.eps or not bn.track_running_stats for _, bn in pairs):
+            raise ValueError("the HIP BasicBlock kernels need one eps on all BatchNorms, with running stats tracked")
+        learn, stats = [], []
+        for conv, bn in pairs:
+            learn += [conv.weight, bn.weight, bn.bias]
+            stats += [bn.running_mean, bn.running_var]
+        for t in learn + stats:
+            if not t.is_cuda or t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("BasicBlock parameters and buffers must be contiguous float32 CUDA tensors on the input's device "
+                                 "(call .cuda() on the model)")
+        return (cin, width, self.stride), float(self.bn1.eps), learn, stats
+
+    def forward(self, x):
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != self.conv1.in_channels:
+            raise ValueError(f"BasicBlock input must be a [n,{self.conv1.in_channels},H,W] tensor")
+        if not x.is_cuda:
+            raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+        (cin, width, stride), eps, learn, stats = self._train_operands(x.device)
+        n, _, hin, win = x.shape
+        if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
+            raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+        if stride != 1 and x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("BasicBlock(stride 2): the input requires grad, but the input gradient of the stride-2 block (a strided dgrad) is "
+                               "not built; pass x.detach()")
+        src = x if x.requires_grad and torch.is_grad_enabled() else None
+        return _BasicBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
 
 
 class Bottleneck(_Residual):
@@ -94,8 +134,10 @@ class FeaturePyramidNetwork(nn.Module):
     ``fpn([C2, C3, C4, C5])`` on CUDA NCHW tensors (fp32 or fp16; C(k) has in_channels >> (5 - k) channels and each level is exactly twice
     the size of the one above) returns P2 as ``[n,256,H,W]`` fp32 from the HIP training kernels (csrc/fpn_train.hip), differentiable
     w.r.t. the ten live tensors (the four laterals and layer_blocks[3], weights and biases).  layer_blocks[0..2] are dead
-    (text_detector.py:56) and receive no gradient, as under torch autograd.  No gradient of the input features is formed: features that
-    require grad are refused."""
+    (text_detector.py:56) and receive no gradient, as under torch autograd.  Features that require grad are refused unless the call says
+    ``input_grad=True``: then the backward also forms dC(k) = inner_blocks[5-k].weight^T dL(k) for the features that require grad (one
+    more GEMM per level, none for the others) and each receives it in its own layout and dtype.  The ten parameter gradients are the same
+    bits either way."""
 
     def __init__(self, in_channels):
         super().__init__()
@@ -136,23 +178,32 @@ class FeaturePyramidNetwork(nn.Module):
                                  "(call .cuda() on the model)")
         return params
 
-    def forward(self, features):
+    def forward(self, features, input_grad=False):
         if not isinstance(features, (list, tuple)) or len(features) != 4 or not all(torch.is_tensor(t) and t.dim() == 4 for t in features):
             raise ValueError("FeaturePyramidNetwork input must be the four [n,C,H,W] trunk taps [C2, C3, C4, C5]")
         geom = self._geometry([tuple(t.shape) for t in features])
-        if any(t.requires_grad for t in features):
+        if any(t.requires_grad for t in features) and not input_grad:
             raise RuntimeError("FeaturePyramidNetwork: the input features require grad, but backward into the trunk is not built; "
-                               "only the FPN's own parameters receive a gradient (pass features.detach())")
+                               "only the FPN's own parameters receive a gradient (pass features.detach(), or input_grad=True for the "
+                               "gradient of the features themselves)")
         if not all(t.is_cuda for t in features):
             raise ValueError("FeaturePyramidNetwork runs on the HIP kernels: features must be CUDA (HIP) tensors")
         params = self._live_checked(features[0].device)
-        return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *params)
+        srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
+        return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None):
-        """The FPN on padded taps (ring-padded NHWC fp16 [n,h+2,w+2,C] for C2..C5, e.g. DetectorEngine.forward_trunk).  Without `head`:
+    def forward_padded(self, taps, head=None, layer4=None):
+        """With `layer4` (ResNet-18's last stage, an nn.Sequential of two BasicBlocks) and a DBHead: layer4 -> FPN -> head as ONE autograd node
+        on the padded taps [C2, C3, C4] (a fourth entry is ignored: C5 is computed here from C4), differentiable w.r.t. layer4's fifteen
+        learnable tensors, the FPN's ten and the head's twenty; dP2 and dC5 travel between the stages as the kernels leave them (NHWC fp32
+        with their power-of-two scales), never through fp16.  Otherwise:
+
+        The FPN on padded taps (ring-padded NHWC fp16 [n,h+2,w+2,C] for C2..C5, e.g. DetectorEngine.forward_trunk).  Without `head`:
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if layer4 is not None:
+            return self._forward_padded_layer4(taps, head, layer4)
         if not isinstance(taps, (list, tuple)) or len(taps) != 4:
             raise ValueError("padded taps must be the four tensors [C2, C3, C4, C5]")
         for t in taps:
@@ -171,6 +222,52 @@ class FeaturePyramidNetwork(nn.Module):
                 for bn in bns:
                     bn.num_batches_tracked.add_(1)
         return {"probability": prob, "threshold": thresh}
+
+
+    def _forward_padded_layer4(self, taps, head, layer4):
+        if head is None:
+            raise ValueError("forward_padded(taps, layer4=...) is the training node: it needs the DBHead too")
+        if not isinstance(taps, (list, tuple)) or len(taps) < 3:
+            raise ValueError("padded taps must be the tensors [C2, C3, C4]")
+        taps = tuple(t.detach() for t in taps[:3])
+        for t in taps:
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
+                raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+        blocks, bgeoms, beps, blearn, bstats = _layer4_operands(layer4, taps[2])
+        n, h5, w5 = bgeoms[1][0], bgeoms[1][1], bgeoms[1][2]
+        geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps] + [(n, 512, h5, w5)])
+        params = self._live_checked(taps[0].device)
+        bns, hparams, hbuffers = head._train_operands(taps[0].device)
+        prob, thresh, _ = _Layer4FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(bgeoms), beps,
+                                                      tuple(bstats), *blearn[0], *blearn[1], *params, *hparams)
+        if head.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
+
+
+def _layer4_operands(layer4, c4_tap):
+    """ResNet-18's layer4 on a padded C4 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics)."""
+    blocks = list(layer4)
+    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
+        raise RuntimeError("layer4 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
+    n, h4, w4 = int(c4_tap.shape[0]), int(c4_tap.shape[1]) - 2, int(c4_tap.shape[2]) - 2
+    ops = [b._train_operands(c4_tap.device) for b in blocks]
+    if [o[0] for o in ops] != [(256, 512, 2), (512, 512, 1)] or c4_tap.shape[3] != 256:
+        raise RuntimeError("layer4 training is built for ResNet-18's layer4 (256 -> 512 stride 2, then 512 -> 512 stride 1)")
+    if h4 % 2 or w4 % 2 or ops[0][1] != ops[1][1]:
+        raise RuntimeError("layer4 training needs a C4 of even extents and one BatchNorm eps")
+    geoms = [(n, h4, w4, 256, 512, 2), (n, h4 // 2, w4 // 2, 512, 512, 1)]
+    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_layer4_padded(layer4, c4_tap):
+    """ResNet-18's layer4 on a padded C4 tap with the HIP training kernels, no gradient: padded C5 [n,h5+2,w5+2,512] fp16."""
+    _, geoms, eps, learn, stats = _layer4_operands(layer4, c4_tap)
+    with torch.no_grad():
+        mid, _ = _block_forward_raw(c4_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0])
+        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1])[0]
 
 
 def _db_branch(c):
@@ -291,6 +388,84 @@ class _DBHeadTrainFn(torch.autograd.Function):
         return (None, grad_src, None, None, None, None, None, *grads)
 
 
+# ---- BasicBlock training (csrc/resblock_train.hip).  geom = (n, h_in, w_in, cin, width, stride); learn = conv1.weight, bn1.weight, bn1.bias,
+# conv2.*, bn2.*, then the downsample's three; stats = the running means and variances in the same order
+def _block_struct(learn, stats=None):
+    import ctypes as C
+    from . import _native
+    st = _native.BasicBlockParams()
+    for i, pre in enumerate(("conv1_w bn1_w bn1_b", "conv2_w bn2_w bn2_b", "ds_w ds_bn_w ds_bn_b")[:len(learn) // 3]):
+        for j, field in enumerate(pre.split()):
+            setattr(st, field, C.c_void_p(learn[3 * i + j].data_ptr()))
+        if stats is not None:
+            bn = pre.split()[1][:-2]
+            setattr(st, bn + "_mean", C.c_void_p(stats[2 * i].data_ptr()))
+            setattr(st, bn + "_var", C.c_void_p(stats[2 * i + 1].data_ptr()))
+    return st
+
+
+def _block_forward_raw(tap, geom, eps, learn, stats):
+    """vtd_basicblock_train_forward on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace)."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, hin, win, cin, width, stride = geom
+    nbytes = int(lib.vtd_basicblock_train_workspace_bytes(*geom, 0))
+    _native.check(min(nbytes, 0), "vtd_basicblock_train_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
+    st = _block_struct(learn, stats)
+    _native.check(lib.vtd_basicblock_train_forward(C.c_void_p(tap.data_ptr()), *geom, C.byref(st), eps, C.c_void_p(ws.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_basicblock_train_forward")
+    return y, ws
+
+
+def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx):
+    """vtd_basicblock_train_backward on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale); dx is NHWC
+    fp32 [n,h,w,512] times dxscale[0], or None."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, hin, win, cin, width, stride = geom
+    grads = [torch.empty_like(p) for p in learn]
+    nbytes = int(lib.vtd_basicblock_train_workspace_bytes(*geom, 1))
+    _native.check(min(nbytes, 0), "vtd_basicblock_train_workspace_bytes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    st, gst = _block_struct(learn, stats), _block_struct(grads)
+    dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
+    dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _native.check(lib.vtd_basicblock_train_backward(ptr(tap), *geom, C.byref(st), eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale), C.byref(gst), ptr(scratch),
+                                                    ptr(dx), ptr(dxs), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "vtd_basicblock_train_backward")
+    return grads, dx, dxs
+
+
+class _BasicBlockTrainFn(torch.autograd.Function):
+    """One BasicBlock on the HIP training kernels: padded tap in, [n,width,h,w] fp32 out.  `src` is None or the NCHW tensor the tap was packed
+    from (stride-1 block only): when it requires grad it receives the input gradient in its own dtype."""
+
+    @staticmethod
+    def forward(ctx, tap, src, geom, eps, stats, *learn):
+        y, ws = _block_forward_raw(tap, geom, eps, learn, stats)
+        ctx.save_for_backward(tap, y, *stats, *learn)
+        ctx.ws, ctx.geom, ctx.eps, ctx.nstats = ws, geom, eps, len(stats)
+        ctx.src_dtype = None if src is None else src.dtype
+        return y[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        tap, y, *rest = ctx.saved_tensors
+        stats, learn = rest[:ctx.nstats], rest[ctx.nstats:]
+        dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
+        want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
+        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx)
+        gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
+        return (None, gsrc, None, None, None, *grads)
+
+
 # ---- FPN training (csrc/fpn_train.hip).  geom = (n, h5, w5, c5 channels); taps = padded taps C2..C5; params = the ten live tensors:
 # inner_blocks[0..3].weight, inner_blocks[0..3].bias, layer_blocks[3].weight, layer_blocks[3].bias
 def _fpn_struct(tensors):
@@ -328,26 +503,53 @@ def _fpn_forward_raw(taps, geom, params):
     return p2, ws
 
 
-def _fpn_backward_raw(taps, geom, params, ws, dp2, dscale):
-    """vtd_fpn_train_backward on dP2 as NHWC fp32 times dscale[0]: the ten gradients, in the order of `params`."""
+def _fpn_backward_raw(taps, geom, params, ws, dp2, dscale, input_mask=0):
+    """vtd_fpn_train_backward on dP2 as NHWC fp32 times dscale[0]: the ten gradients, in the order of `params`.  With `input_mask` (bit lv
+    asks for C(2 + lv)) also vtd_fpn_train_backward_input: (the ten gradients, [dC2..dC5] with None for levels not asked for, their scales
+    [4,2]); each dC(k) is NHWC fp32 [n,h,w,C] times its scales[lv, 0]."""
     import ctypes as C
     from . import _native
     lib = _native.require()
     n, h5, w5, c5 = geom
     grads = [torch.empty_like(p) for p in params]
-    scratch = torch.empty(int(lib.vtd_fpn_train_workspace_bytes(n, h5, w5, c5, 1)), dtype=torch.uint8, device=dp2.device)
+    nbytes = int(lib.vtd_fpn_train_input_workspace_bytes(n, h5, w5, c5) if input_mask else lib.vtd_fpn_train_workspace_bytes(n, h5, w5, c5, 1))
+    _native.check(min(nbytes, 0), "vtd_fpn_train_workspace_bytes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dp2.device)
     st, gst, tp = _fpn_struct(params), _fpn_struct(grads), _fpn_taps(taps)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _native.check(lib.vtd_fpn_train_backward(C.byref(tp), n, h5, w5, c5, C.byref(st), ptr(ws), ptr(dp2), ptr(dscale), C.byref(gst), ptr(scratch),
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_backward")
-    return grads
+                                             stream), "vtd_fpn_train_backward")
+    if not input_mask:
+        return grads
+    dtaps = [torch.empty((n, h5 << (3 - lv), w5 << (3 - lv), c5 >> (3 - lv)), dtype=torch.float32, device=dp2.device) if (input_mask >> lv) & 1 else None
+             for lv in range(4)]
+    scales = torch.zeros((4, 2), dtype=torch.float32, device=dp2.device)
+    out = _native.FpnTaps(*(None if t is None else ptr(t) for t in dtaps))
+    _native.check(lib.vtd_fpn_train_backward_input(n, h5, w5, c5, C.byref(st), ptr(scratch), int(input_mask), C.byref(out), ptr(scales), stream),
+                  "vtd_fpn_train_backward_input")
+    return grads, dtaps, scales
+
+
+def _fpn_unpack_tap_grad(dtap, scale):
+    """vtd_fpn_train_unpack_tap_grad: NHWC fp32 [n,h,w,C] times scale[0] -> [n,C,h,w] fp32, the scale undone."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, h, w, ch = dtap.shape
+    out = torch.empty((n, ch, h, w), dtype=torch.float32, device=dtap.device)
+    _native.check(lib.vtd_fpn_train_unpack_tap_grad(C.c_void_p(dtap.data_ptr()), C.c_void_p(scale.data_ptr()), n, ch, h, w, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_unpack_tap_grad")
+    return out
 
 
 class _FPNTrainFn(torch.autograd.Function):
-    """The FPN alone on the HIP training kernels: padded taps in, P2 as [n,256,H,W] fp32 out, differentiable w.r.t. the ten live tensors."""
+    """The FPN alone on the HIP training kernels: padded taps in, P2 as [n,256,H,W] fp32 out, differentiable w.r.t. the ten live tensors.
+    `s2..s5` are None, or the [n,C,H,W] tensors the padded taps were packed from: those that require grad receive their gradient
+    (vtd_fpn_train_backward_input, only the levels that need one) in their own dtype."""
 
     @staticmethod
-    def forward(ctx, taps, geom, *params):
+    def forward(ctx, taps, geom, s2, s3, s4, s5, *params):
         import ctypes as C
         from . import _native
         lib = _native.require()
@@ -358,6 +560,7 @@ class _FPNTrainFn(torch.autograd.Function):
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_unpack_p2")
         ctx.save_for_backward(*params)
         ctx.taps, ctx.geom, ctx.ws = taps, geom, ws
+        ctx.src_dtypes = tuple(None if t is None else t.dtype for t in (s2, s3, s4, s5))
         return out
 
     @staticmethod
@@ -372,8 +575,12 @@ class _FPNTrainFn(torch.autograd.Function):
         _native.check(lib.vtd_fpn_train_pack_grad(C.c_void_p(g.data_ptr()), n, 8 * h5, 8 * w5, C.c_void_p(dp2.data_ptr()),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_fpn_train_pack_grad")
         dscale = torch.ones(2, dtype=torch.float32, device=g.device)
-        grads = _fpn_backward_raw(ctx.taps, ctx.geom, ctx.saved_tensors, ctx.ws, dp2, dscale)
-        return (None, None, *grads)
+        mask = sum(1 << lv for lv in range(4) if ctx.src_dtypes[lv] is not None and ctx.needs_input_grad[2 + lv])
+        if not mask:
+            return (None, None, None, None, None, None, *_fpn_backward_raw(ctx.taps, ctx.geom, ctx.saved_tensors, ctx.ws, dp2, dscale))
+        grads, dtaps, scales = _fpn_backward_raw(ctx.taps, ctx.geom, ctx.saved_tensors, ctx.ws, dp2, dscale, mask)
+        dsrc = [None if t is None else _fpn_unpack_tap_grad(t, scales[lv]).to(ctx.src_dtypes[lv]) for lv, t in enumerate(dtaps)]
+        return (None, None, *dsrc, *grads)
 
 
 class _FPNHeadTrainFn(torch.autograd.Function):
@@ -402,6 +609,41 @@ class _FPNHeadTrainFn(torch.autograd.Function):
         hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
         fgrads = _fpn_backward_raw(ctx.taps, ctx.geom, fpn_params, ctx.fws, dp2, dscale)
         return (None, None, None, None, None, None, *fgrads, *hgrads)
+
+
+class _Layer4FPNHeadTrainFn(torch.autograd.Function):
+    """layer4 -> FPN -> DB head as one node on the padded taps C2..C4.  The backward hands the head's dP2 to the FPN's backward and the FPN's
+    dC5 (vtd_fpn_train_backward_input, level C5 alone) to the second block's backward, then that block's dx to the first block's, each as
+    the kernels leave it: NHWC fp32 with its power-of-two scale.  Inputs: taps, FPN geom, the head's BatchNorm mode / momentum / eps and
+    buffers, the blocks' geometries, eps and running statistics, then the learnable tensors: 9 + 6 of the blocks, the FPN's 10, the head's 20."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
+        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        mid, bws0 = _block_forward_raw(taps[2], bgeoms[0], beps, b0, bstats[0])
+        c5, bws1 = _block_forward_raw(mid, bgeoms[1], beps, b1, bstats[1])
+        ftaps = (taps[0], taps[1], taps[2], c5)
+        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, mid, c5, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, (bws0, bws1)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, mid, c5, *params = ctx.saved_tensors
+        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        ftaps = (ctx.taps[0], ctx.taps[1], ctx.taps[2], c5)
+        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 8)
+        g1, dmid, dmid_scale = _block_backward_raw(mid, ctx.bgeoms[1], ctx.beps, b1, ctx.bstats[1], ctx.bws[1], c5, dtaps[3], scales[3], True)
+        g0, _, _ = _block_backward_raw(ctx.taps[2], ctx.bgeoms[0], ctx.beps, b0, ctx.bstats[0], ctx.bws[0], mid, dmid, dmid_scale, False)
+        return (None,) * 9 + (*g0, *g1, *fgrads, *hgrads)
 
 
 def pack_tap(feature):
@@ -584,8 +826,17 @@ class DBNet(_EngineOwner, nn.Module):
         only: an optimizer step on FPN or head weights never rebuilds it), then the FPN and the head on the HIP training kernels as one
         autograd node, differentiable w.r.t. the FPN's ten live tensors and the head's twenty.  The trunk's BatchNorms use their running
         statistics (folded into the convolutions), as in "head" mode; backward through the trunk is not built.  eval() forwards keep
-        the fused inference engine, rebuilt after updates of the trained tensors."""
-        if trainable not in (None, "head", "head+fpn"):
+        the fused inference engine, rebuilt after updates of the trained tensors.  "head+fpn+layer4" (ResNet-18 only): also fine-tune
+        the trunk's last stage -- backbone.0 .. backbone.6 stop requiring grad; backbone.7, fpn and head train.  A forward in train mode
+        runs the trunk engine (keyed on the versions of the frozen backbone tensors only: an optimizer step on layer4, FPN or head never
+        rebuilds it), takes C2..C4 from it -- the engine's own C5 comes from the layer4 weights it was built with and is ignored --, then
+        runs layer4 on C4, the FPN and the head on the HIP training kernels as one autograd node.  layer4's BatchNorms, like the rest of
+        the trunk's, normalise with their running statistics, which are never written."""
+        if trainable == "head+fpn+layer4":
+            if self.backbone_name != "resnet18":
+                raise ValueError(f"trainable='head+fpn+layer4' is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
+                                 "Bottleneck training is not built")
+        elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         self.trainable = trainable
         if trainable == "head":
@@ -594,13 +845,21 @@ class DBNet(_EngineOwner, nn.Module):
         elif trainable == "head+fpn":
             for p in self.backbone.parameters():
                 p.requires_grad_(False)
+        elif trainable == "head+fpn+layer4":
+            for i in range(7):
+                for p in self.backbone[i].parameters():
+                    p.requires_grad_(False)
+            for p in list(self.backbone[7].parameters()) + list(self.fpn.parameters()) + list(self.head.parameters()):
+                p.requires_grad_(True)
         self._head_versions = None
         return self
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable == "head+fpn":
+        if self.trainable in ("head+fpn", "head+fpn+layer4"):
             tensors += list(self.fpn.parameters())
+        if self.trainable == "head+fpn+layer4":
+            tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
         return tuple(t._version for t in tensors)
 
     def trunk_engine(self):
@@ -608,7 +867,10 @@ class DBNet(_EngineOwner, nn.Module):
         from . import engine as _e
         with self._engine_lock:
             # keyed on the backbone tensors' versions only (load_state_dict bumps them): FPN and head updates never rebuild it
-            version = tuple(t._version for t in self.backbone.state_dict().values())
+            frozen = self.backbone.state_dict()
+            if self.trainable == "head+fpn+layer4":      # the frozen tensors only: the engine's C5 (stale layer4 weights) is never read
+                frozen = {k: v for k, v in frozen.items() if not k.startswith("7.")}
+            version = tuple(t._version for t in frozen.values())
             te = self.__dict__.get("_trunk_engine")
             if te is None or self.__dict__.get("_trunk_version") != version:
                 te = _e.DetectorEngine(self.backbone_name, self.state_dict(), getattr(self, "_max_batch", None), options={"fuse_fpn_head": 0})
@@ -650,8 +912,10 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn"):
+        if self.trainable in ("head", "head+fpn", "head+fpn+layer4"):
             if self.training:
+                if self.trainable == "head+fpn+layer4":
+                    return self._forward_train_head_fpn_layer4(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
             # the inference engine packs the head on the host: rebuild it after an optimizer step (parameter versions) or a
             # train-mode forward (running statistics, mark_dirty)
@@ -684,6 +948,20 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)   # new tensors per call: autograd may keep them
         out = self.fpn.forward_padded(taps, head=self.head)
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+
+    def _forward_train_head_fpn_layer4(self, x):
+        frozen = [n for i in range(7) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4'): {frozen[0]} requires grad, but backward below layer4 is not "
+                               "implemented; only layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. backbone.6)")
+        for m in (self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = self.trunk_engine().forward_trunk(x)   # C5 of the engine is computed from the weights it was built with: ignored
+        out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
