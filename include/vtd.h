@@ -270,7 +270,8 @@ int vtd_fpn_train_unpack_tap_grad(const float* dtap_dev, const float* dscale_dev
  * with g the gradient at the BatchNorm output, G = g^T x (MFMA, slabs summed in order) and s = sum g:  dW = gamma rstd G, dbeta = s,
  * dgamma = rstd (sum_k w G - mean s): exact for gamma = 0, nothing divides by gamma.  dx_dev (optional): the input gradient as NHWC float32
  * [n][h][w][512] times dxscale_dev[0], with dxscale_dev = {scale, 1 / scale}.  LIMITATION: the input gradient is formed for the stride-1
- * block only; the stride-2 block would need a strided dgrad that is not built, and a non-NULL dx_dev is refused there with -3003.
+ * block only through these entries: a non-NULL dx_dev on the stride-2 block is refused with -3003 (vtd_resblock_train_backward, below,
+ * forms it with a strided dgrad).
  * No atomics, shape-only grids: bitwise repeatable.
  * Errors: -3001 (argument / unsupported geometry), -3002 (alignment), -3003 (input gradient of the stride-2 block). */
 typedef struct vtd_basicblock_params {
@@ -284,6 +285,27 @@ int vtd_basicblock_train_forward(const void* x_dev, int n, int h_in, int w_in, i
 int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
                                   float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                   const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
+/* The same block on four geometries (cin, width, stride): (128, 256, 2) and (256, 256, 1), ResNet-18's layer3, and (256, 512, 2) and
+ * (512, 512, 1), its layer4; stride 2 needs even h_in and w_in and the downsample's tensors.  Arguments, layouts, numerics and the
+ * parameter gradients are those of vtd_basicblock_train_* (for layer4's geometries: the same bits).  dx_dev (optional) is formed for all
+ * four: NHWC float32 [n][h_in][w_in][cin] times dxscale_dev[0].  For a stride-2 block dx = conv1^T(g1) + ds^T(g2) at the input's
+ * resolution: input row i receives tap t of output row o where 2 o + t - 1 = i (even rows: the centre tap; odd rows: the two outer taps;
+ * row h_in - 1 has no contribution from o = h), columns alike, computed as the stride-1 3x3 path over g1 written into the even positions
+ * of a zeroed plane of the input's size (4x the multiply-adds of a phase-split form); the 1x1 stride-2 transpose lands on the even (row,
+ * column) positions only, brought to g1's power-of-two scale before the add.  The workspace sizes differ from vtd_basicblock_train_*'s:
+ * ask vtd_resblock_train_workspace_bytes.  Errors: -3101 (argument / unsupported geometry), -3102 (alignment), before any launch. */
+/* vtd_resblock_train_combine: a_dev [numel] float32 (times ascale_dev[0]) <- a + b (times bscale_dev[0]), both brought to the smaller of
+ * the two power-of-two scales, which is written to outscale_dev = {scale, 1 / scale} (a buffer of its own).  numel is a multiple of 4.
+ * It adds two gradients of one tensor that arrive from different stages: layer4.0's input gradient and the FPN's dC4. */
+int64_t vtd_resblock_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_resblock_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_resblock_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
+int vtd_resblock_train_combine(float* a_dev, const float* ascale_dev, const float* b_dev, const float* bscale_dev, int64_t numel, float* outscale_dev,
+                               vtd_stream stream);
 
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */

@@ -1,19 +1,26 @@
 // ResNet BasicBlock training with frozen-statistics BatchNorm (the running statistics normalise and are never written; gamma and beta
-// learn), forward and backward, for the two blocks of ResNet-18's layer4: (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).
+// learn), forward and backward, for the blocks of ResNet-18's layer3 and layer4: (128 -> 256, stride 2, downsample), (256 -> 256, stride 1),
+// (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W below is the block's width (256 or 512), a launch argument.
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
 //
 // Forward:
-//   fold             per convolution: w gamma rstd -> fp16 GEMM panel [512][ksz^2 cin] (k = tap * cin + ci), bias = beta - mean gamma rstd;
+//   fold             per convolution: w gamma rstd -> fp16 GEMM panel [W][ksz^2 cin] (k = tap * cin + ci), bias = beta - mean gamma rstd;
 //                    on the device, every call
 //   conv x 2 or 3    conv_igemm.hip: conv1 (3x3, stride s, ReLU) -> padded a1; downsample (1x1, stride 2) -> padded id; conv2 (3x3,
 //                    EPI_RESIDUAL from id or x, ReLU) -> padded y.  a1 and id stay in the workspace
 // Backward from dy (NHWC fp32 times a power of two):
 //   mask             g2 = dy (y > 0) in fp32: the gradient at bn2's output and of the identity path
 //   reduce / finish  per-channel fp64 sums s_c in a fixed order, max |.|, a power-of-two scale; form: the fp16 operands (flat and ring-padded)
-//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h (four 128-column tiles; 3x3 / 1x1 gather at stride 1 / 2), slabs
+//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h (W / 128 128-column tiles; 3x3 / 1x1 gather at stride 1 / 2), slabs
 //   param            slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s): no division by gamma
 //   dgrad            da1 = conv2^T(g2): conv_igemm.hip on the folded weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
 //   dx (stride 1)    conv1^T(g1) the same way, plus g2 brought to the same scale
+//   dx (stride 2)    at the input's 2h x 2w: input row i receives tap t of output row o where 2 o + t - 1 = i.  g1 is written into a zeroed
+//                    ring-padded plane Z of 2h x 2w pixels at the even positions (Z[2o][2p] = g1[o][p]); then dx[i] = sum_t' Z[i + t' - 1]
+//                    w[2 - t'], the stride-1 3x3 path on the rotated, transposed folded weights: even rows meet a non-zero Z at the
+//                    centre tap only, odd rows at the two outer taps, and row 2h - 1 reads the ring (zero) for o = h.  The downsample's
+//                    transpose is a 1x1 GEMM of g2 on the transposed folded weights, added at the even (row, column) positions after
+//                    the power-of-two multiplier that brings it to g1's scale.  (The new entries only: vtd_resblock_train_*.)
 // No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
 #include "vtd_common.h"
 #include "wgrad_mfma.h"
@@ -27,38 +34,41 @@ namespace {
 
 constexpr int RB_THREADS = 256;
 constexpr int RB_MAX_RED = 256;
-constexpr int RB_W = 512;   // block width
 constexpr float RB_SCALE_TARGET = 16384.0f;
+// error bases: the vtd_basicblock_train_* entries (layer4's two geometries, no strided dgrad) answer -3001 / -3002 / -3003, the
+// vtd_resblock_train_* entries (four geometries) -3101 / -3102
+constexpr int RB_LEGACY = -3000, RB_GENERAL = -3100;
 
 inline int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline unsigned nblk(int64_t items) { return (unsigned)((items + RB_THREADS - 1) / RB_THREADS); }
 
 struct Geo {
-    int n, hin, win, cin, stride, h, w;
+    int n, hin, win, cin, width, stride, h, w;
     int64_t m;
     bool ds;
 };
 
-bool make_geo(int n, int hin, int win, int cin, int width, int stride, Geo& g) {
-    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096 || width != RB_W) return false;
-    if (!((cin == 256 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == 512 && stride == 1))) return false;
-    g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.stride = stride; g.h = hin / stride; g.w = win / stride;
+bool make_geo(int n, int hin, int win, int cin, int width, int stride, bool legacy, Geo& g) {
+    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096) return false;
+    if (width != 512 && (legacy || width != 256)) return false;
+    if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
+    g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.width = width; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w;
     g.ds = stride == 2;
-    return (int64_t)n * (hin + 2) * (win + 2) * 512 < (1ll << 31);
+    return (int64_t)n * (hin + 2) * (win + 2) * width < (1ll << 31);
 }
 
 struct FwdLayout { int64_t a1, id, w1, w2, wd, bias, total; };
-struct BwdLayout { int64_t g2, g1, g2h, g1h, g2p, g1p, wt, zero, part, pmax, sum2, sum1, sc, slab, total; };
+struct BwdLayout { int64_t g2, g1, g2h, g1h, g2p, g1p, wt, zero, part, pmax, sum2, sum1, sc, slab, zp, wdt, total; };
 
 FwdLayout fwd_layout(const Geo& g) {
     FwdLayout L;
     int64_t o = 0;
     auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
-    const int64_t pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * RB_W * 2;
+    const int64_t W = g.width, pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * W * 2;
     L.a1 = take(pad); L.id = take(g.ds ? pad : 0);
-    L.w1 = take((int64_t)RB_W * 9 * g.cin * 2); L.w2 = take((int64_t)RB_W * 9 * RB_W * 2); L.wd = take(g.ds ? (int64_t)RB_W * g.cin * 2 : 0);
-    L.bias = take(3 * RB_W * 4);
+    L.w1 = take(W * 9 * g.cin * 2); L.w2 = take(W * 9 * W * 2); L.wd = take(g.ds ? W * g.cin * 2 : 0);
+    L.bias = take(3 * W * 4);
     L.total = o;
     return L;
 }
@@ -66,65 +76,69 @@ FwdLayout fwd_layout(const Geo& g) {
 inline int wg_slabs(int64_t rows) { int64_t s = (rows + 4095) / 4096; return (int)(s < 1 ? 1 : s > 8 ? 8 : s); }
 inline int64_t slab_rows(int64_t rows, int s) { return ((rows + s - 1) / s + WG_KC - 1) / WG_KC * WG_KC; }
 
-BwdLayout bwd_layout(const Geo& g) {
+// `strided`: room for the stride-2 block's input gradient (the zero-inserted plane and the downsample's transposed panel), at the end
+BwdLayout bwd_layout(const Geo& g, bool strided) {
     BwdLayout L;
     int64_t o = 0;
     auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
-    const int64_t pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * RB_W * 2;
-    L.g2 = take(g.m * RB_W * 4); L.g1 = take(g.m * RB_W * 4);
-    L.g2h = take(g.m * RB_W * 2); L.g1h = take(g.m * RB_W * 2);
+    const int64_t W = g.width, pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * W * 2;
+    L.g2 = take(g.m * W * 4); L.g1 = take(g.m * W * 4);
+    L.g2h = take(g.m * W * 2); L.g1h = take(g.m * W * 2);
     L.g2p = take(pad); L.g1p = take(pad);
-    L.wt = take((int64_t)RB_W * 9 * RB_W * 2);
-    L.zero = take(RB_W * 4);
-    L.part = take((int64_t)RB_MAX_RED * RB_W * 8); L.pmax = take(RB_MAX_RED * 4);
-    L.sum2 = take(RB_W * 8); L.sum1 = take(RB_W * 8);
+    L.wt = take(W * 9 * W * 2);
+    L.zero = take(W * 4);
+    L.part = take((int64_t)RB_MAX_RED * W * 8); L.pmax = take(RB_MAX_RED * 4);
+    L.sum2 = take(W * 8); L.sum1 = take(W * 8);
     L.sc = take(2 * 4 * 4);
-    L.slab = take((int64_t)wg_slabs(g.m) * RB_W * 9 * RB_W * 4);
+    L.slab = take((int64_t)wg_slabs(g.m) * W * 9 * W * 4);
+    L.zp = take(strided ? (int64_t)g.n * (g.hin + 2) * (g.win + 2) * W * 2 : 0);
+    L.wdt = take(strided ? (int64_t)g.cin * W * 2 : 0);
     L.total = o;
     return L;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------
-// wp [512][ksz^2 cin], k = tap * cin + ci: half(w[co][ci][tap] gamma rstd); bias[co] = beta - mean gamma rstd
+// wp [W][ksz^2 cin], k = tap * cin + ci: half(w[co][ci][tap] gamma rstd); bias[co] = beta - mean gamma rstd
 __global__ __launch_bounds__(RB_THREADS) void rb_fold_kernel(const float* w, const float* gam, const float* bet, const float* mean, const float* var,
-                                                             float eps, int cin, int taps, half_t* wp, float* bias) {
+                                                             float eps, int W, int cin, int taps, half_t* wp, float* bias) {
     const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
     const int K = taps * cin;
-    if (i < (int64_t)RB_W * K) {
+    if (i < (int64_t)W * K) {
         const int co = (int)(i / K), k = (int)(i - (int64_t)co * K), tap = k / cin, ci = k - tap * cin;
         const float sc = gam[co] / sqrtf(var[co] + eps);
         wp[i] = (half_t)(w[((int64_t)co * cin + ci) * taps + tap] * sc);
-    } else if (i < (int64_t)RB_W * K + RB_W) {
-        const int co = (int)(i - (int64_t)RB_W * K);
+    } else if (i < (int64_t)W * K + W) {
+        const int co = (int)(i - (int64_t)W * K);
         bias[co] = bet[co] - mean[co] * (gam[co] / sqrtf(var[co] + eps));
     }
 }
 
-// the one-pixel ring of a padded NHWC fp16 tensor of 512 channels.  One thread = 8 channels of one ring pixel.
-__global__ __launch_bounds__(RB_THREADS) void rb_zero_ring_kernel(half_t* t, int n, int H, int W) {
-    const int Hp = H + 2, Wp = W + 2, R = 2 * Wp + 2 * H;
+// the one-pixel ring of a padded NHWC fp16 tensor of W channels.  One thread = 8 channels of one ring pixel.
+__global__ __launch_bounds__(RB_THREADS) void rb_zero_ring_kernel(half_t* t, int n, int H, int Wd, int W) {
+    const int Hp = H + 2, Wp = Wd + 2, R = 2 * Wp + 2 * H, C8 = W >> 3;
     const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
-    if (i >= (int64_t)n * R * 64) return;
-    const int c8 = (int)(i & 63);
-    const int64_t q = i >> 6;
+    if (i >= (int64_t)n * R * C8) return;
+    const int c8 = (int)(i % C8);
+    const int64_t q = i / C8;
     const int r = (int)(q % R), img = (int)(q / R);
     int yp, xp;
     if (r < Wp) { yp = 0; xp = r; }
     else if (r < 2 * Wp) { yp = Hp - 1; xp = r - Wp; }
     else { const int k = r - 2 * Wp; yp = 1 + (k >> 1); xp = (k & 1) ? Wp - 1 : 0; }
     const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    *(half8*)(t + (((int64_t)img * Hp + yp) * Wp + xp) * RB_W + c8 * 8) = z;
+    *(half8*)(t + (((int64_t)img * Hp + yp) * Wp + xp) * W + c8 * 8) = z;
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------------
 // out[m][c] = v[m][c] where the padded activation at pixel m is positive, else 0.  One thread = 4 channels.
-__global__ __launch_bounds__(RB_THREADS) void rb_mask_kernel(const float* v, const half_t* act, int64_t rows, int H, int W, float* out) {
+__global__ __launch_bounds__(RB_THREADS) void rb_mask_kernel(const float* v, const half_t* act, int64_t rows, int H, int Wd, int W, float* out) {
     const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
-    if (i >= rows * (RB_W / 4)) return;
-    const int cq = (int)(i & 127);
-    const int64_t m = i >> 7;
-    const int HW = H * W, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / W, x = rem - y * W;
-    const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (W + 2) + x + 1) * RB_W + 4 * cq;
+    const int C4 = W >> 2;
+    if (i >= rows * C4) return;
+    const int cq = (int)(i % C4);
+    const int64_t m = i / C4;
+    const int HW = H * Wd, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * W + 4 * cq;
     const floatx4 f = *(const floatx4*)(v + i * 4);
     floatx4 o;
 #pragma unroll
@@ -132,21 +146,23 @@ __global__ __launch_bounds__(RB_THREADS) void rb_mask_kernel(const float* v, con
     *(floatx4*)(out + i * 4) = o;
 }
 
-// v [rows][512] fp32: thread t owns channels t and t + 256 over the rows of its workgroup, in row order: part[g][512] fp64, pmax[g]
-__global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
+// v [rows][W] fp32, W = 256 or 512: thread t owns channel t (and t + 256 of a 512-wide v) over the rows of its workgroup, in row order:
+// part[g][W] fp64, pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, int64_t rows, int64_t per, int W, double* part, float* pmax) {
     const int t = threadIdx.x;
+    const bool two = W > 256;
     const int64_t m0 = (int64_t)blockIdx.x * per, m1 = m0 + per < rows ? m0 + per : rows;
     double s0 = 0.0, s1 = 0.0;
     float mx = 0.f;
     for (int64_t m = m0; m < m1; ++m) {
-        const float a = v[m * RB_W + t], b = v[m * RB_W + 256 + t];
+        const float a = v[m * W + t], b = two ? v[m * W + 256 + t] : 0.f;
         s0 += (double)a; s1 += (double)b;
         const float fa = fabsf(a), fb = fabsf(b);
         mx = fa > mx || fa != fa ? fa : mx;
         mx = fb > mx || fb != fb ? fb : mx;
     }
-    part[(int64_t)blockIdx.x * RB_W + t] = s0;
-    part[(int64_t)blockIdx.x * RB_W + 256 + t] = s1;
+    part[(int64_t)blockIdx.x * W + t] = s0;
+    if (two) part[(int64_t)blockIdx.x * W + 256 + t] = s1;
     __shared__ float shm[RB_THREADS];
     shm[t] = mx;
     __syncthreads();
@@ -159,11 +175,12 @@ __global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, i
 
 // partials in workgroup order: sum[c] = the channel sum with the incoming scale undone (fp64); out_sc = {total scale, 1 / total,
 // this stage's multiplier, 0}, the multiplier a power of two from max |v| (1 when that is zero or not finite)
-__global__ __launch_bounds__(RB_THREADS) void rb_finish_kernel(const double* part, const float* pmax, int G, const float* in_sc, double* sum, float* out_sc) {
+__global__ __launch_bounds__(RB_THREADS) void rb_finish_kernel(const double* part, const float* pmax, int G, int W, const float* in_sc, double* sum,
+                                                               float* out_sc) {
     const int t = threadIdx.x;
-    for (int c = t; c < RB_W; c += RB_THREADS) {
+    for (int c = t; c < W; c += RB_THREADS) {
         double s = 0.0;
-        for (int g = 0; g < G; ++g) s += part[(int64_t)g * RB_W + c];
+        for (int g = 0; g < G; ++g) s += part[(int64_t)g * W + c];
         sum[c] = s * (double)in_sc[1];
     }
     if (t == 0) {
@@ -181,31 +198,36 @@ __global__ __launch_bounds__(RB_THREADS) void rb_finish_kernel(const double* par
     }
 }
 
-// v times the multiplier as fp16: flat [rows][512] and the interior of a ring-padded [n][H+2][W+2][512].  One thread = 8 channels.
-__global__ __launch_bounds__(RB_THREADS) void rb_form_kernel(const float* v, int64_t rows, const float* sc, int H, int W, half_t* flat, half_t* padded) {
+// v times the multiplier as fp16: flat [rows][W] (when given) and a ring-padded plane [n][dil H + 2][dil Wd + 2][W] at pixel (dil y, dil x):
+// dil = 1 fills the interior, dil = 2 the even positions of the stride-2 dgrad's zero-inserted plane.  One thread = 8 channels.
+__global__ __launch_bounds__(RB_THREADS) void rb_form_kernel(const float* v, int64_t rows, const float* sc, int H, int Wd, int W, int dil, half_t* flat,
+                                                             half_t* padded) {
     const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
-    if (i >= rows * 64) return;
+    const int C8 = W >> 3;
+    if (i >= rows * C8) return;
     const float mul = sc[2];
     const floatx4 v0 = *(const floatx4*)(v + i * 8), v1 = *(const floatx4*)(v + i * 8 + 4);
     half8 h;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { h[e] = (half_t)(v0[e] * mul); h[4 + e] = (half_t)(v1[e] * mul); }
-    *(half8*)(flat + i * 8) = h;
-    const int64_t m = i >> 6;
-    const int c8 = (int)(i & 63), HW = H * W;
-    const int img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / W, x = rem - y * W;
-    *(half8*)(padded + (((int64_t)img * (H + 2) + y + 1) * (W + 2) + x + 1) * RB_W + c8 * 8) = h;
+    if (flat) *(half8*)(flat + i * 8) = h;
+    const int64_t m = i / C8;
+    const int c8 = (int)(i % C8), HW = H * Wd;
+    const int img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    *(half8*)(padded + (((int64_t)img * (dil * H + 2) + dil * y + 1) * (dil * Wd + 2) + dil * x + 1) * W + c8 * 8) = h;
 }
 
-// wt [512][9 * 512]: row ci, k = tap' * 512 + co holds half(w[co][ci][8 - tap'] gamma rstd) (the window rotated by 180 degrees, the folded
-// weights transposed, rounded as the forward packs them); a zero bias row
-__global__ __launch_bounds__(RB_THREADS) void rb_pack_dgrad_kernel(const float* w, const float* gam, const float* var, float eps, half_t* wt, float* zero) {
+// wt [cin][taps * W]: row ci, k = tap' * W + co holds half(w[co][ci][taps - 1 - tap'] gamma rstd) (the window rotated by 180 degrees, the
+// folded weights transposed, rounded as the forward packs them); a zero bias row of W entries
+__global__ __launch_bounds__(RB_THREADS) void rb_pack_dgrad_kernel(const float* w, const float* gam, const float* var, float eps, int W, int cin, int taps,
+                                                                   half_t* wt, float* zero) {
     const int i = blockIdx.x * RB_THREADS + threadIdx.x;
-    if (i < RB_W * 9 * RB_W) {
-        const int ci = i / (9 * RB_W), k = i - ci * 9 * RB_W, tap = k / RB_W, co = k - tap * RB_W;
-        wt[i] = (half_t)(w[((int64_t)co * RB_W + ci) * 9 + (8 - tap)] * (gam[co] / sqrtf(var[co] + eps)));
-    } else if (i < RB_W * 9 * RB_W + RB_W) {
-        zero[i - RB_W * 9 * RB_W] = 0.f;
+    const int K = taps * W;
+    if (i < cin * K) {
+        const int ci = i / K, k = i - ci * K, tap = k / W, co = k - tap * W;
+        wt[i] = (half_t)(w[((int64_t)co * cin + ci) * taps + (taps - 1 - tap)] * (gam[co] / sqrtf(var[co] + eps)));
+    } else if (i < cin * K + W) {
+        zero[i - cin * K] = 0.f;
     }
 }
 
@@ -216,7 +238,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_param_kernel(const float* slab,
                                                               float* dbet) {
     const int c = blockIdx.x, t = threadIdx.x, K = taps * cin;
     const double rstd = 1.0 / sqrt((double)var[c] + (double)eps), inv = (double)sc[1], f = (double)gam[c] * rstd;
-    const int64_t nel = (int64_t)RB_W * K;
+    const int64_t nel = (int64_t)gridDim.x * K;
     double dot = 0.0;
     for (int k = t; k < K; k += RB_THREADS) {
         double G = 0.0;
@@ -252,6 +274,39 @@ __global__ __launch_bounds__(RB_THREADS) void rb_add_identity_kernel(float* dx, 
     *(floatx4*)(dx + i * 4) = a;
 }
 
+// the stride-2 block: dx [n][2H][2Wd][cin] (at g1's total scale) += ds^T(g2) [n][H][Wd][cin] (at g2's total scale) times g1's own
+// multiplier, a power of two, at the even (row, column) positions: the 1x1 stride-2 convolution reads no other.  One thread = 4 channels.
+__global__ __launch_bounds__(RB_THREADS) void rb_add_downsample_kernel(float* dx, const float* t, int64_t rows, int H, int Wd, int cin, const float* sc1) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    const int C4 = cin >> 2;
+    if (i >= rows * C4) return;
+    const int cq = (int)(i % C4);
+    const int64_t m = i / C4;
+    const int HW = H * Wd, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    float* d = dx + (((int64_t)img * 2 * H + 2 * y) * 2 * Wd + 2 * x) * cin + 4 * cq;
+    const float mul = sc1[2];
+    floatx4 a = *(floatx4*)d;
+    const floatx4 b = *(const floatx4*)(t + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] += b[e] * mul;
+    *(floatx4*)d = a;
+}
+
+// a [items] (times asc[0]) <- a + b (times bsc[0]) with both brought to the smaller of the two scales: every multiplier is a power of two.
+// osc = {that scale, 1 / it}.  One thread = 4 values.
+__global__ __launch_bounds__(RB_THREADS) void rb_combine_kernel(float* a, const float* asc, const float* b, const float* bsc, int64_t items4, float* osc) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    const bool first = asc[0] <= bsc[0];
+    const float so = first ? asc[0] : bsc[0], ma = so * asc[1], mb = so * bsc[1];
+    if (i == 0) { osc[0] = so; osc[1] = first ? asc[1] : bsc[1]; }
+    if (i >= items4) return;
+    const floatx4 x = *(const floatx4*)(a + i * 4), y = *(const floatx4*)(b + i * 4);
+    floatx4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = x[e] * ma + y[e] * mb;
+    *(floatx4*)(a + i * 4) = o;
+}
+
 __global__ void rb_copy_scale_kernel(const float* sc, float* out) {
     if (threadIdx.x < 2) out[threadIdx.x] = sc[threadIdx.x];
 }
@@ -281,78 +336,81 @@ ConvParams base_conv() {
     return p;
 }
 
-// a 3x3 (pad 1) or 1x1 (pad 0) convolution of a padded tap at `stride` into `M` rows of 512 columns
-ConvParams conv_of(const Geo& g, const half_t* in, int cin, int hin, int win, int ksz, int stride, const half_t* wgt, const float* bias) {
+// a 3x3 (pad 1) or 1x1 (pad 0) convolution at `stride` of a padded tap of hin x win pixels and cin channels into n x ho x wo rows of
+// `cout` columns
+ConvParams conv_of(int n, int ho, int wo, int cout, const half_t* in, int cin, int hin, int win, int ksz, int stride, const half_t* wgt,
+                   const float* bias) {
     ConvParams c = base_conv();
     c.in = in; c.wgt = wgt; c.bias = bias;
     c.cin_steps = cin / 64; c.kw = ksz; c.s_step = cin; c.r_step = (win + 2) * cin;
-    c.M = (int)g.m; c.K = ksz * ksz * cin; c.cout = RB_W; c.cout_pad = RB_W; c.ho = g.h; c.wo = g.w;
+    c.M = n * ho * wo; c.K = ksz * ksz * cin; c.cout = cout; c.cout_pad = cout; c.ho = ho; c.wo = wo;
     c.in_hp = hin + 2; c.in_wp = win + 2; c.in_c = cin; c.in_y0 = c.in_x0 = ksz == 3 ? 0 : 1; c.stride = stride;
     return c;
 }
 
 void to_padded(ConvParams& c, const Geo& g, half_t* out) {
-    c.out = out; c.out_hp = g.h + 2; c.out_wp = g.w + 2; c.out_c = RB_W; c.out_ring = 1;
+    c.out = out; c.out_hp = g.h + 2; c.out_wp = g.w + 2; c.out_c = g.width; c.out_ring = 1;
 }
 
-}  // namespace
-
-int64_t vtd_basicblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+int64_t ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode, int base) {
     Geo g;
-    if (!make_geo(n, hin, win, cin, width, stride, g) || mode < 0 || mode > 1) return -3001;
-    return mode ? bwd_layout(g).total : fwd_layout(g).total;
+    if (!make_geo(n, hin, win, cin, width, stride, base == RB_LEGACY, g) || mode < 0 || mode > 1) return base - 1;
+    return mode ? bwd_layout(g, base != RB_LEGACY && g.ds).total : fwd_layout(g).total;
 }
 
-int vtd_launch_basicblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
-                                  void* ws, void* y, hipStream_t s) {
+int launch_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws, void* y,
+                   hipStream_t s, int base) {
     Geo g;
-    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, g) || !params_ok(P, g.ds) || !(eps > 0.f)) return -3001;
-    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255)) return -3002;
+    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, base == RB_LEGACY, g) || !params_ok(P, g.ds) || !(eps > 0.f)) return base - 1;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255)) return base - 2;
     const FwdLayout L = fwd_layout(g);
+    const int W = width;
     char* w = (char*)ws;
     half_t *a1 = (half_t*)(w + L.a1), *id = (half_t*)(w + L.id), *w1 = (half_t*)(w + L.w1), *w2 = (half_t*)(w + L.w2), *wd = (half_t*)(w + L.wd);
     float* bias = (float*)(w + L.bias);
-    hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)RB_W * 9 * cin + RB_W)), dim3(RB_THREADS), 0, s, (const float*)P->conv1_w, (const float*)P->bn1_w,
-                       (const float*)P->bn1_b, (const float*)P->bn1_mean, (const float*)P->bn1_var, eps, cin, 9, w1, bias);
-    hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)RB_W * 9 * RB_W + RB_W)), dim3(RB_THREADS), 0, s, (const float*)P->conv2_w, (const float*)P->bn2_w,
-                       (const float*)P->bn2_b, (const float*)P->bn2_mean, (const float*)P->bn2_var, eps, RB_W, 9, w2, bias + RB_W);
+    hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)W * 9 * cin + W)), dim3(RB_THREADS), 0, s, (const float*)P->conv1_w, (const float*)P->bn1_w,
+                       (const float*)P->bn1_b, (const float*)P->bn1_mean, (const float*)P->bn1_var, eps, W, cin, 9, w1, bias);
+    hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)W * 9 * W + W)), dim3(RB_THREADS), 0, s, (const float*)P->conv2_w, (const float*)P->bn2_w,
+                       (const float*)P->bn2_b, (const float*)P->bn2_mean, (const float*)P->bn2_var, eps, W, W, 9, w2, bias + W);
     if (g.ds)
-        hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)RB_W * cin + RB_W)), dim3(RB_THREADS), 0, s, (const float*)P->ds_w, (const float*)P->ds_bn_w,
-                           (const float*)P->ds_bn_b, (const float*)P->ds_bn_mean, (const float*)P->ds_bn_var, eps, cin, 1, wd, bias + 2 * RB_W);
-    const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * 64);
-    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, a1, n, g.h, g.w);
-    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, (half_t*)y, n, g.h, g.w);
+        hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)W * cin + W)), dim3(RB_THREADS), 0, s, (const float*)P->ds_w, (const float*)P->ds_bn_w,
+                           (const float*)P->ds_bn_b, (const float*)P->ds_bn_mean, (const float*)P->ds_bn_var, eps, W, cin, 1, wd, bias + 2 * W);
+    const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * (W / 8));
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, a1, n, g.h, g.w, W);
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, (half_t*)y, n, g.h, g.w, W);
     VTD_HIP_CHECK(hipGetLastError());
     int rc;
-    ConvParams c = conv_of(g, (const half_t*)x, cin, hin, win, 3, stride, w1, bias);
+    ConvParams c = conv_of(n, g.h, g.w, W, (const half_t*)x, cin, hin, win, 3, stride, w1, bias);
     c.flags = EPI_RELU;
     to_padded(c, g, a1);
     if ((rc = vtd_launch_conv(c, -1, s))) return rc;
     if (g.ds) {
-        ConvParams d = conv_of(g, (const half_t*)x, cin, hin, win, 1, 2, wd, bias + 2 * RB_W);
+        ConvParams d = conv_of(n, g.h, g.w, W, (const half_t*)x, cin, hin, win, 1, 2, wd, bias + 2 * W);
         to_padded(d, g, id);
         if ((rc = vtd_launch_conv(d, -1, s))) return rc;
     }
-    ConvParams e = conv_of(g, a1, RB_W, g.h, g.w, 3, 1, w2, bias + RB_W);
+    ConvParams e = conv_of(n, g.h, g.w, W, a1, W, g.h, g.w, 3, 1, w2, bias + W);
     e.flags = EPI_RELU | EPI_RESIDUAL;
     e.res = g.ds ? id : (const half_t*)x; e.res_hp = g.h + 2; e.res_wp = g.w + 2; e.res_ring = 1; e.res_shift = 0;
     to_padded(e, g, (half_t*)y);
     return vtd_launch_conv(e, -1, s);
 }
 
-int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
-                                   const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
-                                   float* dx, float* dxscale, hipStream_t s) {
+int launch_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, const void* ws,
+                    const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch, float* dx, float* dxscale,
+                    hipStream_t s, int base) {
     Geo g;
-    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
+    const bool legacy = base == RB_LEGACY;
+    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, legacy, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
         !(eps > 0.f) || (dx && !dxscale))
-        return -3001;
-    if (dx && g.stride != 1) return -3003;
+        return base - 1;
+    if (legacy && dx && g.stride != 1) return base - 3;
     if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dy & 15) || ((uintptr_t)dscale & 7) ||
         ((uintptr_t)dx & 15) || ((uintptr_t)dxscale & 7))
-        return -3002;
+        return base - 2;
     const FwdLayout L = fwd_layout(g);
-    const BwdLayout B = bwd_layout(g);
+    const BwdLayout B = bwd_layout(g, !legacy && g.ds);
+    const int W = width;
     char* q = (char*)scratch;
     const half_t* a1 = (const half_t*)((const char*)ws + L.a1);
     float *g2 = (float*)(q + B.g2), *g1 = (float*)(q + B.g1), *zero = (float*)(q + B.zero), *pmax = (float*)(q + B.pmax), *sc = (float*)(q + B.sc),
@@ -364,53 +422,109 @@ int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int c
     int Gr = (int)((M + 255) / 256);
     Gr = Gr < 1 ? 1 : Gr > RB_MAX_RED ? RB_MAX_RED : Gr;
     const int64_t per = (M + Gr - 1) / Gr;
-    const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * 64);
+    const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * (W / 8));
     const int S = wg_slabs(M);
     int rc;
 
     auto stage = [&](const float* v, const half_t* act, float* gout, const float* in_sc, double* sum, float* out_sc, half_t* flat, half_t* padded) {
-        hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * 128)), dim3(RB_THREADS), 0, s, v, act, M, g.h, g.w, gout);
-        hipLaunchKernelGGL(rb_reduce_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, part, pmax);
-        hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(RB_THREADS), 0, s, (const double*)part, (const float*)pmax, Gr, in_sc, sum, out_sc);
-        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, padded, n, g.h, g.w);
-        hipLaunchKernelGGL(rb_form_kernel, dim3(nblk(M * 64)), dim3(RB_THREADS), 0, s, (const float*)gout, M, (const float*)out_sc, g.h, g.w, flat, padded);
+        hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, v, act, M, g.h, g.w, W, gout);
+        hipLaunchKernelGGL(rb_reduce_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, W, part, pmax);
+        hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(RB_THREADS), 0, s, (const double*)part, (const float*)pmax, Gr, W, in_sc, sum, out_sc);
+        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, padded, n, g.h, g.w, W);
+        hipLaunchKernelGGL(rb_form_kernel, dim3(nblk(M * (W / 8))), dim3(RB_THREADS), 0, s, (const float*)gout, M, (const float*)out_sc, g.h, g.w, W, 1, flat,
+                           padded);
     };
     auto wgrad = [&](const half_t* a, const half_t* xin, int xc, int hi, int wi, int ksz, int st, const float* scl, const double* sum, const float* w,
                      const float* gam, const float* mean, const float* var, float* dw, float* dgam, float* dbet) {
         WgArgs wa;
-        wa.a = a; wa.lda = RB_W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
+        wa.a = a; wa.lda = W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
         wa.slab_len = slab_rows(M, S); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
-        hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(ksz * ksz * xc / 128 * S, 4), dim3(WG_THREADS), 0, s, wa);
-        hipLaunchKernelGGL(rb_param_kernel, dim3(RB_W), dim3(RB_THREADS), 0, s, (const float*)slab, S, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
+        hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(ksz * ksz * xc / 128 * S, W / 128), dim3(WG_THREADS), 0, s, wa);
+        hipLaunchKernelGGL(rb_param_kernel, dim3(W), dim3(RB_THREADS), 0, s, (const float*)slab, S, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
                            dbet);
     };
-    auto dgrad = [&](const half_t* gp, const float* w, const float* gam, const float* var, float* out) {
-        hipLaunchKernelGGL(rb_pack_dgrad_kernel, dim3(nblk(RB_W * 9 * RB_W + RB_W)), dim3(RB_THREADS), 0, s, w, gam, var, eps, wt, zero);
-        ConvParams c = conv_of(g, gp, RB_W, g.h, g.w, 3, 1, wt, zero);
-        c.out = out; c.ldc = RB_W; c.flags = EPI_OUT_F32;
+    // conv^T of a padded gradient plane of hp x wp pixels (W channels) into [n hp wp][rows] fp32: the folded weights of a conv with `rows`
+    // input channels, rotated and transposed into `panel`
+    auto dgrad = [&](const half_t* gp, int hp, int wp, const float* w, const float* gam, const float* var, int rows, int ksz, half_t* panel, float* out) {
+        hipLaunchKernelGGL(rb_pack_dgrad_kernel, dim3(nblk(rows * ksz * ksz * W + W)), dim3(RB_THREADS), 0, s, w, gam, var, eps, W, rows, ksz * ksz, panel,
+                           zero);
+        ConvParams c = conv_of(n, hp, wp, rows, gp, W, hp, wp, ksz, 1, panel, zero);
+        c.out = out; c.ldc = rows; c.flags = EPI_OUT_F32;
         return vtd_launch_conv(c, -1, s);
     };
 
     // g2 = dy (y > 0): the gradient at bn2's output, of the downsample's BatchNorm output, and of an identity input
     stage(dy, (const half_t*)y, g2, dscale, sum2, sc2, g2h, g2p);
     VTD_HIP_CHECK(hipGetLastError());
-    wgrad(g2h, a1, RB_W, g.h, g.w, 3, 1, sc2, sum2, (const float*)P->conv2_w, (const float*)P->bn2_w, (const float*)P->bn2_mean, (const float*)P->bn2_var,
+    wgrad(g2h, a1, W, g.h, g.w, 3, 1, sc2, sum2, (const float*)P->conv2_w, (const float*)P->bn2_w, (const float*)P->bn2_mean, (const float*)P->bn2_var,
           Gp->conv2_w, Gp->bn2_w, Gp->bn2_b);
     if (g.ds)
         wgrad(g2h, (const half_t*)x, cin, hin, win, 1, 2, sc2, sum2, (const float*)P->ds_w, (const float*)P->ds_bn_w, (const float*)P->ds_bn_mean,
               (const float*)P->ds_bn_var, Gp->ds_w, Gp->ds_bn_w, Gp->ds_bn_b);
     VTD_HIP_CHECK(hipGetLastError());
     // da1 = conv2^T(g2) into the g1 buffer, masked in place by a1 > 0
-    if ((rc = dgrad(g2p, (const float*)P->conv2_w, (const float*)P->bn2_w, (const float*)P->bn2_var, g1))) return rc;
+    if ((rc = dgrad(g2p, g.h, g.w, (const float*)P->conv2_w, (const float*)P->bn2_w, (const float*)P->bn2_var, W, 3, wt, g1))) return rc;
     stage(g1, a1, g1, sc2, sum1, sc1, g1h, g1p);
     wgrad(g1h, (const half_t*)x, cin, hin, win, 3, stride, sc1, sum1, (const float*)P->conv1_w, (const float*)P->bn1_w, (const float*)P->bn1_mean,
           (const float*)P->bn1_var, Gp->conv1_w, Gp->bn1_w, Gp->bn1_b);
     VTD_HIP_CHECK(hipGetLastError());
-    if (dx) {
-        if ((rc = dgrad(g1p, (const float*)P->conv1_w, (const float*)P->bn1_w, (const float*)P->bn1_var, dx))) return rc;
-        hipLaunchKernelGGL(rb_add_identity_kernel, dim3(nblk(M * 128)), dim3(RB_THREADS), 0, s, dx, (const float*)g2, M * 128, (const float*)sc2,
+    if (dx && !g.ds) {
+        if ((rc = dgrad(g1p, g.h, g.w, (const float*)P->conv1_w, (const float*)P->bn1_w, (const float*)P->bn1_var, W, 3, wt, dx))) return rc;
+        hipLaunchKernelGGL(rb_add_identity_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g2, M * (W / 4), (const float*)sc2,
+                           (const float*)sc1);
+        hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
+    } else if (dx) {
+        // g1 at the even positions of a zeroed plane of the input's size, then the stride-1 path: see the head of this file
+        half_t *zp = (half_t*)(q + B.zp), *wdt = (half_t*)(q + B.wdt);
+        VTD_HIP_CHECK(hipMemsetAsync(zp, 0, (size_t)n * (hin + 2) * (win + 2) * W * 2, s));
+        hipLaunchKernelGGL(rb_form_kernel, dim3(nblk(M * (W / 8))), dim3(RB_THREADS), 0, s, (const float*)g1, M, (const float*)sc1, g.h, g.w, W, 2,
+                           (half_t*)nullptr, zp);
+        if ((rc = dgrad(zp, hin, win, (const float*)P->conv1_w, (const float*)P->bn1_w, (const float*)P->bn1_var, cin, 3, wt, dx))) return rc;
+        // ds^T(g2) at g2's scale into the g1 buffer (its fp32 values are in the operands by now), then onto the even positions
+        if ((rc = dgrad(g2p, g.h, g.w, (const float*)P->ds_w, (const float*)P->ds_bn_w, (const float*)P->ds_bn_var, cin, 1, wdt, g1))) return rc;
+        hipLaunchKernelGGL(rb_add_downsample_kernel, dim3(nblk(M * (cin / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g1, M, g.h, g.w, cin,
                            (const float*)sc1);
         hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
     }
+    return -(int)hipGetLastError();
+}
+
+}  // namespace
+
+int64_t vtd_basicblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(n, hin, win, cin, width, stride, mode, RB_LEGACY);
+}
+
+int vtd_launch_basicblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                  void* ws, void* y, hipStream_t s) {
+    return launch_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s, RB_LEGACY);
+}
+
+int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                   const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                   float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, RB_LEGACY);
+}
+
+// the four geometries, with the input gradient of the stride-2 blocks
+int64_t vtd_resblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(n, hin, win, cin, width, stride, mode, RB_GENERAL);
+}
+
+int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
+                                void* y, hipStream_t s) {
+    return launch_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s, RB_GENERAL);
+}
+
+int vtd_launch_resblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                 const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                 float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, RB_GENERAL);
+}
+
+int vtd_launch_resblock_combine(float* a, const float* asc, const float* b, const float* bsc, int64_t numel, float* osc, hipStream_t s) {
+    if (!a || !asc || !b || !bsc || !osc || numel <= 0 || (numel & 3) || numel >= (1ll << 40) || osc == asc || osc == bsc) return RB_GENERAL - 1;
+    if ((((uintptr_t)a | (uintptr_t)b) & 15) || (((uintptr_t)asc | (uintptr_t)bsc | (uintptr_t)osc) & 7)) return RB_GENERAL - 2;
+    hipLaunchKernelGGL(rb_combine_kernel, dim3(nblk(numel / 4)), dim3(RB_THREADS), 0, s, a, asc, b, bsc, numel / 4, osc);
     return -(int)hipGetLastError();
 }

@@ -79,6 +79,13 @@ int vtd_launch_basicblock_forward(const void* x, int n, int hin, int win, int ci
 int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
                                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
                                    float* dx, float* dxscale, hipStream_t s);
+int64_t vtd_resblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_resblock_combine(float* a, const float* asc, const float* b, const float* bsc, int64_t numel, float* osc, hipStream_t s);
+int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
+                                void* y, hipStream_t s);
+int vtd_launch_resblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                 const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                 float* dx, float* dxscale, hipStream_t s);
 int vtd_launch_fpn_unpack_tap_grad(const float* g, const float* sc, int n, int channels, int H, int W, float* out, hipStream_t s);
 int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
                                const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
@@ -1428,6 +1435,9 @@ const char* vtd_strerror(int code) {
         case -3001: return "BasicBlock training: invalid argument or unsupported geometry (built: 256 -> 512 stride 2 with even extents, 512 -> 512 stride 1)";
         case -3002: return "BasicBlock training: misaligned buffer";
         case -3003: return "BasicBlock training: the input gradient of the stride-2 block is not built (it needs a strided dgrad)";
+        case -3101: return "ResNet block training: invalid argument or unsupported geometry (built: 128 -> 256 and 256 -> 512 stride 2 with even "
+                           "extents, 256 -> 256 and 512 -> 512 stride 1)";
+        case -3102: return "ResNet block training: misaligned buffer";
         default: break;
     }
     if (code <= -1000) {
@@ -1527,6 +1537,28 @@ int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, 
                                   const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
     return vtd_launch_basicblock_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
                                           scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+// the four geometries of ResNet-18's layer3 and layer4, with the input gradient of the stride-2 blocks
+int64_t vtd_resblock_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_resblock_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_resblock_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               float eps, void* workspace_dev, void* y_dev, vtd_stream stream) {
+    return vtd_launch_resblock_forward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, (hipStream_t)stream);
+}
+
+int vtd_resblock_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
+    return vtd_launch_resblock_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
+                                        scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+int vtd_resblock_train_combine(float* a_dev, const float* ascale_dev, const float* b_dev, const float* bscale_dev, int64_t numel, float* outscale_dev,
+                               vtd_stream stream) {
+    return vtd_launch_resblock_combine(a_dev, ascale_dev, b_dev, bscale_dev, numel, outscale_dev, (hipStream_t)stream);
 }
 
 int64_t vtd_fpn_train_input_workspace_bytes(int n, int h5, int w5, int c5_channels) { return vtd_fpn_input_ws_bytes(n, h5, w5, c5_channels); }

@@ -6,7 +6,8 @@
 //   per q-tile: 4 q-tiles.
 // MODE 2 (conv 1x1, the FPN laterals): A as MODE 0, B = the centre pixel of a ring-padded tensor of xc channels (a multiple of 64),
 //   q-tile qt = channels 128 qt .. 128 qt + 127; columns at or past xc load zeros and are not stored (ResNet-18's C2 has 64 channels).
-// MODE 3 (a ResNet block's convolutions): A as MODE 0 with gridDim.y 128-column tiles (four for a 512-wide gradient), B = the ksz x ksz
+// MODE 3 (a ResNet block's convolutions): A as MODE 0 with gridDim.y = lda / 128 column tiles (four for layer4's 512-wide gradient, two for
+//   layer3's 256-wide one: the width is the launch's grid and `lda`, not a template argument), B = the ksz x ksz
 //   window (ksz = 3: pad 1, ksz = 1: pad 0) at stride `stride` of a ring-padded input of xc channels (a multiple of 128) and Hin x Win
 //   pixels; q = tap * xc + ci, q-tile qt = 128 channels of tap 128 qt / xc: ksz^2 xc / 128 q-tiles.  slab [128 gridDim.y][ksz^2 xc].
 // Workgroup = 4 waves, one (q-tile, slab); each wave a (P_T / 2) x 64 block.  Per K chunk of 32 rows every thread loads rows 8o .. 8o+7

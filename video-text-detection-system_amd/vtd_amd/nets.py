@@ -50,11 +50,15 @@ class BasicBlock(_Residual):
         if stride != 1 or cin != width:
             self.downsample = nn.Sequential(*_conv_bn(cin, width, 1, stride, 0))
 
-    def _train_operands(self, device):
-        """((cin, width, stride), eps, the learnable tensors, the running statistics) as the kernels take them, validated."""
+    def _train_operands(self, device, general=False):
+        """((cin, width, stride), eps, the learnable tensors, the running statistics) as the kernels take them, validated.  `general`: the
+        four geometries of basic_block_train (layer3's and layer4's) instead of layer4's two."""
         cin, width = self.conv1.in_channels, self.conv1.out_channels
         ds = hasattr(self, "downsample")
-        if (cin, width, self.stride, ds) not in ((256, 512, 2, True), (512, 512, 1, False)):
+        if general and (cin, width, self.stride, ds) not in _BLOCK_GEOMETRIES:
+            raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): basic_block_train is built for ResNet-18's layer3 and layer4 "
+                               "(128 -> 256 and 256 -> 512 stride 2 with downsample, 256 -> 256 and 512 -> 512 stride 1)")
+        if not general and (cin, width, self.stride, ds) not in ((256, 512, 2, True), (512, 512, 1, False)):
             raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): the HIP training kernels are built for ResNet-18's layer4 only "
                                "(256 -> 512 stride 2 with downsample, 512 -> 512 stride 1)")
         pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)] + ([(self.downsample[0], self.downsample[1])] if ds else [])
@@ -84,6 +88,29 @@ class BasicBlock(_Residual):
                                "not built; pass x.detach()")
         src = x if x.requires_grad and torch.is_grad_enabled() else None
         return _BasicBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
+
+
+_BLOCK_GEOMETRIES = ((128, 256, 2, True), (256, 256, 1, False), (256, 512, 2, True), (512, 512, 1, False))
+
+
+def basic_block_train(block, x):
+    """One BasicBlock on the HIP training kernels (csrc/resblock_train.hip, the vtd_resblock_train_* entries) as a differentiable function of
+    a CUDA NCHW tensor (fp32 or fp16), for the four blocks of ResNet-18's layer3 and layer4: 128 -> 256 and 256 -> 512 at stride 2 (with
+    downsample, even extents), 256 -> 256 and 512 -> 512 at stride 1.  Frozen-statistics BatchNorm, as ``block(x)``; returns ``[n,width,h,w]``
+    fp32, differentiable w.r.t. the block's learnable tensors and w.r.t. ``x`` for either stride (the stride-2 blocks through the strided
+    dgrad).  For layer4's blocks the output and the parameter gradients are the bits of ``block(x)``."""
+    if not isinstance(block, BasicBlock):
+        raise RuntimeError("basic_block_train is built for ResNet-18's BasicBlocks; Bottleneck training is not built")
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != block.conv1.in_channels:
+        raise ValueError(f"BasicBlock input must be a [n,{block.conv1.in_channels},H,W] tensor")
+    if not x.is_cuda:
+        raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=True)
+    n, _, hin, win = x.shape
+    if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
+        raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+    src = x if x.requires_grad and torch.is_grad_enabled() else None
+    return _ResBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
 
 
 class Bottleneck(_Residual):
@@ -192,8 +219,12 @@ class FeaturePyramidNetwork(nn.Module):
         srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None, layer4=None):
-        """With `layer4` (ResNet-18's last stage, an nn.Sequential of two BasicBlocks) and a DBHead: layer4 -> FPN -> head as ONE autograd node
+    def forward_padded(self, taps, head=None, layer4=None, layer3=None):
+        """With `layer3` too (ResNet-18's third stage, two BasicBlocks): layer3 -> layer4 -> FPN -> head as ONE autograd node on the padded taps
+        [C2, C3] (further entries are ignored: C4 and C5 are computed here), differentiable w.r.t. the thirty learnable tensors of the two
+        stages, the FPN's ten and the head's twenty.  dC4 is layer4.0's input gradient plus the FPN's dC4, added at one power-of-two scale.
+
+        With `layer4` (ResNet-18's last stage, an nn.Sequential of two BasicBlocks) and a DBHead: layer4 -> FPN -> head as ONE autograd node
         on the padded taps [C2, C3, C4] (a fourth entry is ignored: C5 is computed here from C4), differentiable w.r.t. layer4's fifteen
         learnable tensors, the FPN's ten and the head's twenty; dP2 and dC5 travel between the stages as the kernels leave them (NHWC fp32
         with their power-of-two scales), never through fp16.  Otherwise:
@@ -202,6 +233,8 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if layer3 is not None:
+            return self._forward_padded_layer3(taps, head, layer4, layer3)
         if layer4 is not None:
             return self._forward_padded_layer4(taps, head, layer4)
         if not isinstance(taps, (list, tuple)) or len(taps) != 4:
@@ -247,13 +280,65 @@ class FeaturePyramidNetwork(nn.Module):
         return {"probability": prob, "threshold": thresh}
 
 
-def _layer4_operands(layer4, c4_tap):
-    """ResNet-18's layer4 on a padded C4 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics)."""
+    def _forward_padded_layer3(self, taps, head, layer4, layer3):
+        if head is None or layer4 is None:
+            raise ValueError("forward_padded(taps, layer3=...) is the training node: it needs layer4 and the DBHead too")
+        if not isinstance(taps, (list, tuple)) or len(taps) < 2:
+            raise ValueError("padded taps must be the tensors [C2, C3]")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:2])
+        for t in taps:
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
+                raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, taps[1])
+        n, h4, w4 = g3[1][0], g3[1][1], g3[1][2]
+        c4_shape = torch.empty((n, h4 + 2, w4 + 2, 256), dtype=torch.float16, device="meta")
+        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, c4_shape, taps[1].device)
+        if eps3 != eps4:
+            raise RuntimeError("layer3 / layer4 training needs one BatchNorm eps")
+        h5, w5 = g4[1][1], g4[1][2]
+        geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps] + [(n, 256, h4, w4), (n, 512, h5, w5)])
+        params = self._live_checked(taps[0].device)
+        bns, hparams, hbuffers = head._train_operands(taps[0].device)
+        prob, thresh, _ = _Layer3Layer4FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(g3 + g4), eps3,
+                                                            tuple(stats3 + stats4), *learn3[0], *learn3[1], *learn4[0], *learn4[1], *params, *hparams)
+        if head.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
+
+
+def _layer3_operands(layer3, c3_tap):
+    """ResNet-18's layer3 on a padded C3 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics)."""
+    blocks = list(layer3)
+    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
+        raise RuntimeError("layer3 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
+    n, h3, w3 = int(c3_tap.shape[0]), int(c3_tap.shape[1]) - 2, int(c3_tap.shape[2]) - 2
+    ops = [b._train_operands(c3_tap.device, general=True) for b in blocks]
+    if [o[0] for o in ops] != [(128, 256, 2), (256, 256, 1)] or c3_tap.shape[3] != 128:
+        raise RuntimeError("layer3 training is built for ResNet-18's layer3 (128 -> 256 stride 2, then 256 -> 256 stride 1)")
+    if h3 % 2 or w3 % 2 or ops[0][1] != ops[1][1]:
+        raise RuntimeError("layer3 training needs a C3 of even extents and one BatchNorm eps")
+    geoms = [(n, h3, w3, 128, 256, 2), (n, h3 // 2, w3 // 2, 256, 256, 1)]
+    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_layer3_padded(layer3, c3_tap):
+    """ResNet-18's layer3 on a padded C3 tap with the HIP training kernels, no gradient: padded C4 [n,h4+2,w4+2,256] fp16."""
+    _, geoms, eps, learn, stats = _layer3_operands(layer3, c3_tap)
+    with torch.no_grad():
+        mid, _ = _block_forward_raw(c3_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], _RESBLOCK)
+        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], _RESBLOCK)[0]
+
+
+def _layer4_operands(layer4, c4_tap, device=None):
+    """ResNet-18's layer4 on a padded C4 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics).
+    Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
     blocks = list(layer4)
     if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
         raise RuntimeError("layer4 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
     n, h4, w4 = int(c4_tap.shape[0]), int(c4_tap.shape[1]) - 2, int(c4_tap.shape[2]) - 2
-    ops = [b._train_operands(c4_tap.device) for b in blocks]
+    ops = [b._train_operands(c4_tap.device if device is None else device) for b in blocks]
     if [o[0] for o in ops] != [(256, 512, 2), (512, 512, 1)] or c4_tap.shape[3] != 256:
         raise RuntimeError("layer4 training is built for ResNet-18's layer4 (256 -> 512 stride 2, then 512 -> 512 stride 1)")
     if h4 % 2 or w4 % 2 or ops[0][1] != ops[1][1]:
@@ -404,41 +489,56 @@ def _block_struct(learn, stats=None):
     return st
 
 
-def _block_forward_raw(tap, geom, eps, learn, stats):
-    """vtd_basicblock_train_forward on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace)."""
+_RESBLOCK = "vtd_resblock_train"   # the entry family of the four geometries; the default below is layer4's two (no strided dgrad)
+
+
+def _block_forward_raw(tap, geom, eps, learn, stats, entry="vtd_basicblock_train"):
+    """vtd_basicblock_train_forward (or `entry`'s) on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace)."""
     import ctypes as C
     from . import _native
     lib = _native.require()
     n, hin, win, cin, width, stride = geom
-    nbytes = int(lib.vtd_basicblock_train_workspace_bytes(*geom, 0))
-    _native.check(min(nbytes, 0), "vtd_basicblock_train_workspace_bytes")
+    nbytes = int(getattr(lib, entry + "_workspace_bytes")(*geom, 0))
+    _native.check(min(nbytes, 0), entry + "_workspace_bytes")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
     y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
     st = _block_struct(learn, stats)
-    _native.check(lib.vtd_basicblock_train_forward(C.c_void_p(tap.data_ptr()), *geom, C.byref(st), eps, C.c_void_p(ws.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_basicblock_train_forward")
+    _native.check(getattr(lib, entry + "_forward")(C.c_void_p(tap.data_ptr()), *geom, C.byref(st), eps, C.c_void_p(ws.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry + "_forward")
     return y, ws
 
 
-def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx):
-    """vtd_basicblock_train_backward on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale); dx is NHWC
-    fp32 [n,h,w,512] times dxscale[0], or None."""
+def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx, entry="vtd_basicblock_train"):
+    """vtd_basicblock_train_backward (or `entry`'s) on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale);
+    dx is NHWC fp32 [n,h_in,w_in,cin] times dxscale[0], or None."""
     import ctypes as C
     from . import _native
     lib = _native.require()
     n, hin, win, cin, width, stride = geom
     grads = [torch.empty_like(p) for p in learn]
-    nbytes = int(lib.vtd_basicblock_train_workspace_bytes(*geom, 1))
-    _native.check(min(nbytes, 0), "vtd_basicblock_train_workspace_bytes")
+    nbytes = int(getattr(lib, entry + "_workspace_bytes")(*geom, 1))
+    _native.check(min(nbytes, 0), entry + "_workspace_bytes")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
     st, gst = _block_struct(learn, stats), _block_struct(grads)
     dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
     dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    _native.check(lib.vtd_basicblock_train_backward(ptr(tap), *geom, C.byref(st), eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale), C.byref(gst), ptr(scratch),
+    _native.check(getattr(lib, entry + "_backward")(ptr(tap), *geom, C.byref(st), eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale), C.byref(gst), ptr(scratch),
                                                     ptr(dx), ptr(dxs), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                  "vtd_basicblock_train_backward")
+                  entry + "_backward")
     return grads, dx, dxs
+
+
+def _combine_scaled(a, ascale, b, bscale):
+    """vtd_resblock_train_combine: a <- a + b with both brought to the smaller of their two power-of-two scales; (a, that scale [2])."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    out = torch.empty(2, dtype=torch.float32, device=a.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _native.check(lib.vtd_resblock_train_combine(ptr(a), ptr(ascale), ptr(b), ptr(bscale), a.numel(), ptr(out),
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_resblock_train_combine")
+    return a, out
 
 
 class _BasicBlockTrainFn(torch.autograd.Function):
@@ -462,6 +562,30 @@ class _BasicBlockTrainFn(torch.autograd.Function):
         dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
         want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
         grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx)
+        gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
+        return (None, gsrc, None, None, None, *grads)
+
+
+class _ResBlockTrainFn(torch.autograd.Function):
+    """_BasicBlockTrainFn on the vtd_resblock_train_* entries: the four geometries, and `src` receives its gradient for either stride."""
+
+    @staticmethod
+    def forward(ctx, tap, src, geom, eps, stats, *learn):
+        y, ws = _block_forward_raw(tap, geom, eps, learn, stats, _RESBLOCK)
+        ctx.save_for_backward(tap, y, *stats, *learn)
+        ctx.ws, ctx.geom, ctx.eps, ctx.nstats = ws, geom, eps, len(stats)
+        ctx.src_dtype = None if src is None else src.dtype
+        return y[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        tap, y, *rest = ctx.saved_tensors
+        stats, learn = rest[:ctx.nstats], rest[ctx.nstats:]
+        dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
+        want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
+        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx, _RESBLOCK)
         gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
         return (None, gsrc, None, None, None, *grads)
 
@@ -644,6 +768,54 @@ class _Layer4FPNHeadTrainFn(torch.autograd.Function):
         g1, dmid, dmid_scale = _block_backward_raw(mid, ctx.bgeoms[1], ctx.beps, b1, ctx.bstats[1], ctx.bws[1], c5, dtaps[3], scales[3], True)
         g0, _, _ = _block_backward_raw(ctx.taps[2], ctx.bgeoms[0], ctx.beps, b0, ctx.bstats[0], ctx.bws[0], mid, dmid, dmid_scale, False)
         return (None,) * 9 + (*g0, *g1, *fgrads, *hgrads)
+
+
+class _Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
+    """layer3 -> layer4 -> FPN -> DB head as one node on the padded taps C2, C3.  The backward is _Layer4FPNHeadTrainFn's, continued: the FPN's
+    backward also forms dC4, layer4's first block forms its input gradient (the strided dgrad), the two are added at one power-of-two scale
+    (vtd_resblock_train_combine) and go into layer3's second block, whose dx goes into the first; layer3.0 forms no input gradient.
+    Inputs: taps, FPN geom, the head's BatchNorm mode / momentum / eps and buffers, the four blocks' geometries, eps and running statistics
+    (layer3.0, layer3.1, layer4.0, layer4.1), then the learnable tensors: 9 + 6 + 9 + 6 of the blocks, the FPN's 10, the head's 20."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
+        blocks = (params[:9], params[9:15], params[15:24], params[24:30])
+        fpn_params, head_params = params[30:40], params[40:]
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        acts, bws, x = [], [], taps[1]
+        for i in range(4):                       # acts: layer3.0's output, C4, layer4.0's output, C5
+            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _RESBLOCK)
+            acts.append(x)
+            bws.append(ws)
+        ftaps = (taps[0], taps[1], acts[1], acts[3])
+        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, *acts, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, m3, c4, m4, c5, *params = ctx.saved_tensors
+        blocks = (params[:9], params[9:15], params[15:24], params[24:30])
+        fpn_params, head_params = params[30:40], params[40:]
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        ftaps = (ctx.taps[0], ctx.taps[1], c4, c5)
+        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 4 | 8)      # dC4 and dC5
+        ins = (ctx.taps[1], m3, c4, m4)
+        outs = (m3, c4, m4, c5)
+        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
+                                                         dx, _RESBLOCK)
+        g41, d, ds = bwd(3, dtaps[3], scales[3], True)
+        g40, d, ds = bwd(2, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
+        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
+        g31, d, ds = bwd(1, d, ds, True)
+        g30, _, _ = bwd(0, d, ds, False)
+        return (None,) * 9 + (*g30, *g31, *g40, *g41, *fgrads, *hgrads)
 
 
 def pack_tap(feature):
@@ -831,10 +1003,13 @@ class DBNet(_EngineOwner, nn.Module):
         runs the trunk engine (keyed on the versions of the frozen backbone tensors only: an optimizer step on layer4, FPN or head never
         rebuilds it), takes C2..C4 from it -- the engine's own C5 comes from the layer4 weights it was built with and is ignored --, then
         runs layer4 on C4, the FPN and the head on the HIP training kernels as one autograd node.  layer4's BatchNorms, like the rest of
-        the trunk's, normalise with their running statistics, which are never written."""
-        if trainable == "head+fpn+layer4":
+        the trunk's, normalise with their running statistics, which are never written.  "head+fpn+layer4+layer3" (ResNet-18 only): one stage
+        further down -- backbone.0 .. backbone.5 stop requiring grad; backbone.6, backbone.7, fpn and head train.  The trunk engine is keyed
+        on the frozen tensors only and gives C2 and C3 (its C4 and C5 are ignored); layer3, layer4, the FPN and the head run on the HIP
+        training kernels as one autograd node.  layer4.0 forms its input gradient with the strided dgrad; dC4 is that plus the FPN's dC4."""
+        if trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3"):
             if self.backbone_name != "resnet18":
-                raise ValueError(f"trainable='head+fpn+layer4' is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
+                raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
                                  "Bottleneck training is not built")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
@@ -851,15 +1026,24 @@ class DBNet(_EngineOwner, nn.Module):
                     p.requires_grad_(False)
             for p in list(self.backbone[7].parameters()) + list(self.fpn.parameters()) + list(self.head.parameters()):
                 p.requires_grad_(True)
+        elif trainable == "head+fpn+layer4+layer3":
+            for i in range(6):
+                for p in self.backbone[i].parameters():
+                    p.requires_grad_(False)
+            for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
+                for p in m.parameters():
+                    p.requires_grad_(True)
         self._head_versions = None
         return self
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable in ("head+fpn", "head+fpn+layer4"):
+        if self.trainable in ("head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3"):
             tensors += list(self.fpn.parameters())
-        if self.trainable == "head+fpn+layer4":
+        if self.trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3"):
             tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
+        if self.trainable == "head+fpn+layer4+layer3":
+            tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
         return tuple(t._version for t in tensors)
 
     def trunk_engine(self):
@@ -870,6 +1054,8 @@ class DBNet(_EngineOwner, nn.Module):
             frozen = self.backbone.state_dict()
             if self.trainable == "head+fpn+layer4":      # the frozen tensors only: the engine's C5 (stale layer4 weights) is never read
                 frozen = {k: v for k, v in frozen.items() if not k.startswith("7.")}
+            elif self.trainable == "head+fpn+layer4+layer3":      # likewise: the engine's C4 and C5 are never read
+                frozen = {k: v for k, v in frozen.items() if not k.startswith(("6.", "7."))}
             version = tuple(t._version for t in frozen.values())
             te = self.__dict__.get("_trunk_engine")
             if te is None or self.__dict__.get("_trunk_version") != version:
@@ -912,8 +1098,10 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn", "head+fpn+layer4"):
+        if self.trainable in ("head", "head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3"):
             if self.training:
+                if self.trainable == "head+fpn+layer4+layer3":
+                    return self._forward_train_head_fpn_layer4_layer3(x)
                 if self.trainable == "head+fpn+layer4":
                     return self._forward_train_head_fpn_layer4(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
@@ -962,6 +1150,21 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)   # C5 of the engine is computed from the weights it was built with: ignored
         out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+
+    def _forward_train_head_fpn_layer4_layer3(self, x):
+        frozen = [n for i in range(6) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4+layer3'): {frozen[0]} requires grad, but backward below layer3 is not "
+                               "implemented; only layer3, layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. "
+                               "backbone.5)")
+        for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = self.trunk_engine().forward_trunk(x)   # C4 and C5 of the engine come from the weights it was built with: ignored
+        out = self.fpn.forward_padded(taps[:2], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
