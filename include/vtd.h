@@ -286,10 +286,13 @@ int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, 
                                   float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                   const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
-/* The same block on four geometries (cin, width, stride): (128, 256, 2) and (256, 256, 1), ResNet-18's layer3, and (256, 512, 2) and
- * (512, 512, 1), its layer4; stride 2 needs even h_in and w_in and the downsample's tensors.  Arguments, layouts, numerics and the
- * parameter gradients are those of vtd_basicblock_train_* (for layer4's geometries: the same bits).  dx_dev (optional) is formed for all
- * four: NHWC float32 [n][h_in][w_in][cin] times dxscale_dev[0].  For a stride-2 block dx = conv1^T(g1) + ds^T(g2) at the input's
+/* The same block on six geometries (cin, width, stride): (64, 128, 2) and (128, 128, 1), ResNet-18's layer2, (128, 256, 2) and
+ * (256, 256, 1), its layer3, and (256, 512, 2) and (512, 512, 1), its layer4; stride 2 needs even h_in and w_in and the downsample's
+ * tensors.  Arguments, layouts, numerics and the parameter gradients are those of vtd_basicblock_train_* (for layer4's geometries: the
+ * same bits).  The 128-wide blocks differ in two fixed orders: their per-channel sums add two row halves per workgroup, and each of their
+ * weight-gradient launches cuts the rows into min(ceil(512 / q-tiles), ceil(rows / 1024)) slabs (the wider blocks: min(8, ceil(rows /
+ * 4096)) for every launch); (64, 128, 2)'s weight gradients gather the 64-channel input a tap per 64-column group.  dx_dev (optional) is
+ * formed for all six: NHWC float32 [n][h_in][w_in][cin] times dxscale_dev[0].  For a stride-2 block dx = conv1^T(g1) + ds^T(g2) at the input's
  * resolution: input row i receives tap t of output row o where 2 o + t - 1 = i (even rows: the centre tap; odd rows: the two outer taps;
  * row h_in - 1 has no contribution from o = h), columns alike, computed as the stride-1 3x3 path over g1 written into the even positions
  * of a zeroed plane of the input's size (4x the multiply-adds of a phase-split form); the 1x1 stride-2 transpose lands on the even (row,
@@ -297,7 +300,8 @@ int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, 
  * ask vtd_resblock_train_workspace_bytes.  Errors: -3101 (argument / unsupported geometry), -3102 (alignment), before any launch. */
 /* vtd_resblock_train_combine: a_dev [numel] float32 (times ascale_dev[0]) <- a + b (times bscale_dev[0]), both brought to the smaller of
  * the two power-of-two scales, which is written to outscale_dev = {scale, 1 / scale} (a buffer of its own).  numel is a multiple of 4.
- * It adds two gradients of one tensor that arrive from different stages: layer4.0's input gradient and the FPN's dC4. */
+ * It adds two gradients of one tensor that arrive from different stages: layer4.0's input gradient and the FPN's dC4, layer3.0's and the
+ * FPN's dC3. */
 int64_t vtd_resblock_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
 int vtd_resblock_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
                                float eps, void* workspace_dev, void* y_dev, vtd_stream stream);

@@ -1,6 +1,7 @@
 // ResNet BasicBlock training with frozen-statistics BatchNorm (the running statistics normalise and are never written; gamma and beta
-// learn), forward and backward, for the blocks of ResNet-18's layer3 and layer4: (128 -> 256, stride 2, downsample), (256 -> 256, stride 1),
-// (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W below is the block's width (256 or 512), a launch argument.
+// learn), forward and backward, for the blocks of ResNet-18's layer2, layer3 and layer4: (64 -> 128, stride 2, downsample), (128 -> 128,
+// stride 1), (128 -> 256, stride 2, downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W
+// below is the block's width (128, 256 or 512), a launch argument.
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
 //
 // Forward:
@@ -10,8 +11,15 @@
 //                    EPI_RESIDUAL from id or x, ReLU) -> padded y.  a1 and id stay in the workspace
 // Backward from dy (NHWC fp32 times a power of two):
 //   mask             g2 = dy (y > 0) in fp32: the gradient at bn2's output and of the identity path
-//   reduce / finish  per-channel fp64 sums s_c in a fixed order, max |.|, a power-of-two scale; form: the fp16 operands (flat and ring-padded)
-//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h (W / 128 128-column tiles; 3x3 / 1x1 gather at stride 1 / 2), slabs
+//   reduce / finish  per-channel fp64 sums s_c in a fixed order, max |.|, a power-of-two scale; form: the fp16 operands (flat and ring-padded).
+//                    W = 128: the 256 threads of a workgroup are two halves of 128 channels; the lower half sums the first ceil(r / 2) of
+//                    the workgroup's r rows in row order, the upper half the rest, and the partial is lower + upper
+//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h (W / 128 128-column tiles; 3x3 / 1x1 gather at stride 1 / 2), slabs.
+//   wgrad<4>         the same over layer2.0's 64-channel input (conv1: K = 576, the downsample: K = 64): a 64-column group per tap.
+//                    Slabs: W = 256 and 512 cut the rows into min(8, ceil(rows / 4096)) slabs for every launch of a block.  W = 128 has
+//                    one column tile, so each launch takes min(ceil(512 / q-tiles), ceil(rows / 1024)) slabs: two workgroups per CU of
+//                    the 256 when the rows allow slabs of 1024 (conv2 and layer2.1's conv1, 9 q-tiles: 57; layer2.0's conv1, 5: 103; its
+//                    downsample, 1: 512)
 //   param            slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s): no division by gamma
 //   dgrad            da1 = conv2^T(g2): conv_igemm.hip on the folded weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
 //   dx (stride 1)    conv1^T(g1) the same way, plus g2 brought to the same scale
@@ -36,7 +44,7 @@ constexpr int RB_THREADS = 256;
 constexpr int RB_MAX_RED = 256;
 constexpr float RB_SCALE_TARGET = 16384.0f;
 // error bases: the vtd_basicblock_train_* entries (layer4's two geometries, no strided dgrad) answer -3001 / -3002 / -3003, the
-// vtd_resblock_train_* entries (four geometries) -3101 / -3102
+// vtd_resblock_train_* entries (six geometries) -3101 / -3102
 constexpr int RB_LEGACY = -3000, RB_GENERAL = -3100;
 
 inline int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
@@ -50,7 +58,7 @@ struct Geo {
 
 bool make_geo(int n, int hin, int win, int cin, int width, int stride, bool legacy, Geo& g) {
     if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096) return false;
-    if (width != 512 && (legacy || width != 256)) return false;
+    if (width != 512 && (legacy || (width != 256 && width != 128))) return false;
     if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
     g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.width = width; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w;
@@ -74,6 +82,12 @@ FwdLayout fwd_layout(const Geo& g) {
 }
 
 inline int wg_slabs(int64_t rows) { int64_t s = (rows + 4095) / 4096; return (int)(s < 1 ? 1 : s > 8 ? 8 : s); }
+// W = 128 (one column tile): the slabs of a launch of `nqt` q-tiles.  Shape-only: 512 workgroups when the rows allow slabs of 1024
+inline int wg_slabs128(int64_t rows, int nqt) {
+    const int64_t want = (512 + nqt - 1) / nqt, can = (rows + 1023) / 1024;
+    return (int)(want < can ? want : can < 1 ? 1 : can);
+}
+inline int wg_nqt(int ksz, int xc) { return (ksz * ksz * xc + 127) / 128; }
 inline int64_t slab_rows(int64_t rows, int s) { return ((rows + s - 1) / s + WG_KC - 1) / WG_KC * WG_KC; }
 
 // `strided`: room for the stride-2 block's input gradient (the zero-inserted plane and the downsample's transposed panel), at the end
@@ -90,7 +104,14 @@ BwdLayout bwd_layout(const Geo& g, bool strided) {
     L.part = take((int64_t)RB_MAX_RED * W * 8); L.pmax = take(RB_MAX_RED * 4);
     L.sum2 = take(W * 8); L.sum1 = take(W * 8);
     L.sc = take(2 * 4 * 4);
-    L.slab = take((int64_t)wg_slabs(g.m) * W * 9 * W * 4);
+    int64_t slab = (int64_t)wg_slabs(g.m) * W * 9 * W;
+    if (W == 128) {   // per launch: conv2, conv1, the downsample
+        slab = (int64_t)wg_slabs128(g.m, wg_nqt(3, 128)) * W * 9 * 128;
+        const int64_t c1 = (int64_t)wg_slabs128(g.m, wg_nqt(3, g.cin)) * W * 9 * g.cin, dsl = g.ds ? (int64_t)wg_slabs128(g.m, wg_nqt(1, g.cin)) * W * g.cin : 0;
+        slab = c1 > slab ? c1 : slab;
+        slab = dsl > slab ? dsl : slab;
+    }
+    L.slab = take(slab * 4);
     L.zp = take(strided ? (int64_t)g.n * (g.hin + 2) * (g.win + 2) * W * 2 : 0);
     L.wdt = take(strided ? (int64_t)g.cin * W * 2 : 0);
     L.total = o;
@@ -166,6 +187,32 @@ __global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, i
     __shared__ float shm[RB_THREADS];
     shm[t] = mx;
     __syncthreads();
+    if (t == 0) {
+        float m = shm[0];
+        for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
+        pmax[blockIdx.x] = m;
+    }
+}
+
+// v [rows][128] fp32: thread t owns channel t % 128 over one half of the workgroup's rows m0 .. m1 in row order, t < 128 the first
+// ceil((m1 - m0) / 2) rows and t >= 128 the rest; part[g][c] = the first half's sum + the second half's, fp64; pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce128_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
+    const int t = threadIdx.x, c = t & 127, hf = t >> 7;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t mid = m0 + (m1 - m0 + 1) / 2, lo = hf ? mid : m0, hi = hf ? m1 : mid;
+    double s = 0.0;
+    float mx = 0.f;
+    for (int64_t m = lo; m < hi; ++m) {
+        const float a = v[m * 128 + c], fa = fabsf(a);
+        s += (double)a;
+        mx = fa > mx || fa != fa ? fa : mx;
+    }
+    __shared__ double shs[128];
+    __shared__ float shm[RB_THREADS];
+    if (hf) shs[c] = s;
+    shm[t] = mx;
+    __syncthreads();
+    if (!hf) part[(int64_t)blockIdx.x * 128 + c] = s + shs[c];
     if (t == 0) {
         float m = shm[0];
         for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
@@ -428,7 +475,10 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
 
     auto stage = [&](const float* v, const half_t* act, float* gout, const float* in_sc, double* sum, float* out_sc, half_t* flat, half_t* padded) {
         hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, v, act, M, g.h, g.w, W, gout);
-        hipLaunchKernelGGL(rb_reduce_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, W, part, pmax);
+        if (W == 128)
+            hipLaunchKernelGGL(rb_reduce128_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, part, pmax);
+        else
+            hipLaunchKernelGGL(rb_reduce_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, W, part, pmax);
         hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(RB_THREADS), 0, s, (const double*)part, (const float*)pmax, Gr, W, in_sc, sum, out_sc);
         hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, padded, n, g.h, g.w, W);
         hipLaunchKernelGGL(rb_form_kernel, dim3(nblk(M * (W / 8))), dim3(RB_THREADS), 0, s, (const float*)gout, M, (const float*)out_sc, g.h, g.w, W, 1, flat,
@@ -438,9 +488,13 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
                      const float* gam, const float* mean, const float* var, float* dw, float* dgam, float* dbet) {
         WgArgs wa;
         wa.a = a; wa.lda = W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
-        wa.slab_len = slab_rows(M, S); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
-        hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(ksz * ksz * xc / 128 * S, W / 128), dim3(WG_THREADS), 0, s, wa);
-        hipLaunchKernelGGL(rb_param_kernel, dim3(W), dim3(RB_THREADS), 0, s, (const float*)slab, S, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
+        const int nqt = wg_nqt(ksz, xc), Sl = W == 128 ? wg_slabs128(M, nqt) : S;
+        wa.slab_len = slab_rows(M, Sl); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
+        if (xc & 127)   // layer2.0's 64-channel input: a tap per 64-column group
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<4>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
+        else
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
+        hipLaunchKernelGGL(rb_param_kernel, dim3(W), dim3(RB_THREADS), 0, s, (const float*)slab, Sl, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
                            dbet);
     };
     // conv^T of a padded gradient plane of hp x wp pixels (W channels) into [n hp wp][rows] fp32: the folded weights of a conv with `rows`
@@ -506,7 +560,7 @@ int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int c
     return launch_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, RB_LEGACY);
 }
 
-// the four geometries, with the input gradient of the stride-2 blocks
+// the six geometries, with the input gradient of the stride-2 blocks
 int64_t vtd_resblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
     return ws_bytes(n, hin, win, cin, width, stride, mode, RB_GENERAL);
 }

@@ -1539,7 +1539,7 @@ int vtd_basicblock_train_backward(const void* x_dev, int n, int h_in, int w_in, 
                                           scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 
-// the four geometries of ResNet-18's layer3 and layer4, with the input gradient of the stride-2 blocks
+// the six geometries of ResNet-18's layer2, layer3 and layer4, with the input gradient of the stride-2 blocks
 int64_t vtd_resblock_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
     return vtd_resblock_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
 }

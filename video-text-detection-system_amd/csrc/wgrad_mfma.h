@@ -10,6 +10,11 @@
 //   layer3's 256-wide one: the width is the launch's grid and `lda`, not a template argument), B = the ksz x ksz
 //   window (ksz = 3: pad 1, ksz = 1: pad 0) at stride `stride` of a ring-padded input of xc channels (a multiple of 128) and Hin x Win
 //   pixels; q = tap * xc + ci, q-tile qt = 128 channels of tap 128 qt / xc: ksz^2 xc / 128 q-tiles.  slab [128 gridDim.y][ksz^2 xc].
+// MODE 4 (a ResNet block's convolutions over a 64-channel input, layer2.0's conv1 and downsample): as MODE 3 with xc a multiple of 64 that is
+//   no multiple of 128.  Each 64-column group of a q-tile decodes its own tap, as MODE 1's `grp` does: group 2 qt + grp holds channels
+//   (128 qt + 64 grp) % xc of tap (128 qt + 64 grp) / xc, so with xc = 64 a q-tile holds two taps.  ceil(ksz^2 xc / 128) q-tiles; columns at
+//   or past ksz^2 xc (the second half of the last q-tile: K = 576 is 4.5 q-tiles, K = 64 half of one) load zeros and are not stored, as
+//   MODE 2's.  slab [128 gridDim.y][ksz^2 xc].
 // Workgroup = 4 waves, one (q-tile, slab); each wave a (P_T / 2) x 64 block.  Per K chunk of 32 rows every thread loads rows 8o .. 8o+7
 // of one column pair of A and B with 4-byte loads (the next chunk's loads are in flight during this chunk's MFMAs), transposes them into
 // LDS as [row octet][column][8] so that a fragment (8 consecutive rows of one column) is one 16-byte read, double-buffered: one barrier
@@ -32,7 +37,7 @@ struct WgArgs {
     int n, H, W;
     int64_t rows, slab_len;
     float* slab;
-    int ksz, stride, Hin, Win;   // MODE 3 only
+    int ksz, stride, Hin, Win;   // MODES 3 and 4 only
 };
 
 template <int MODE>
@@ -45,16 +50,20 @@ __device__ __forceinline__ const half_t* wg_brow(const WgArgs& A, int img, int y
         return A.x + (((int64_t)img * 2 * A.H + 2 * y + ky) * 2 * A.W + 2 * xx + kx) * 128 + b * 64;
     } else if constexpr (MODE == 2) {
         return A.x + (((int64_t)img * (A.H + 2) + y + 1) * (A.W + 2) + xx + 1) * A.xc + qt * 128 + grp * 64;
-    } else {
+    } else if constexpr (MODE == 3) {
         const int q0 = qt * 128, tap = q0 / A.xc, c0 = q0 - tap * A.xc, ky = tap / A.ksz, kx = tap - ky * A.ksz, o = 1 - (A.ksz >> 1);
         return A.x + (((int64_t)img * (A.Hin + 2) + y * A.stride + ky + o) * (A.Win + 2) + xx * A.stride + kx + o) * A.xc + c0 + grp * 64;
+    } else {
+        const int q0 = qt * 128 + grp * 64, tap = q0 / A.xc, c0 = q0 - tap * A.xc, ky = tap / A.ksz, kx = tap - ky * A.ksz, o = 1 - (A.ksz >> 1);
+        return A.x + (((int64_t)img * (A.Hin + 2) + y * A.stride + ky + o) * (A.Win + 2) + xx * A.stride + kx + o) * A.xc + c0;
     }
 }
 
 template <int MODE>
 __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const WgArgs A) {
     constexpr int PT = MODE == 1 ? 64 : 128, QT = 128, FP = PT / 32, FQ = 4;
-    const int NQT = MODE == 0 ? 18 : MODE == 1 ? 4 : MODE == 2 ? (A.xc + 127) / 128 : A.ksz * A.ksz * A.xc / 128;
+    const int NQT = MODE == 0 ? 18 : MODE == 1 ? 4 : MODE == 2 ? (A.xc + 127) / 128 : MODE == 3 ? A.ksz * A.ksz * A.xc / 128
+                                                                                       : (A.ksz * A.ksz * A.xc + 127) / 128;
     const int qt = blockIdx.x % NQT, sl = blockIdx.x / NQT, pt = blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wp = w >> 1, wq = w & 1;
     const int a_col0 = MODE == 1 ? (qt >> 1) * 128 : pt * 128;   // MODE 1: the hi half of the branch's a1 pair
@@ -69,7 +78,7 @@ __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const Wg
     const int bp = t % (QT / 2), bo = t / (QT / 2);          // bo in 0..3
     const bool a_act = ao < 4;
     const int bgrp = (2 * bp) / 64, bcol = (2 * bp) % 64;
-    const bool b_act = MODE != 2 || qt * 128 + bgrp * 64 < A.xc;
+    const bool b_act = MODE == 2 ? qt * 128 + bgrp * 64 < A.xc : MODE == 4 ? qt * 128 + bgrp * 64 < A.ksz * A.ksz * A.xc : true;
     const int HW = A.H * A.W;
 
     uint32_t ra[8], rb[8];
@@ -154,7 +163,7 @@ __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const Wg
             for (int e = 0; e < 4; ++e) {
                 const int p = p_base + wp * (PT / 2) + i * 16 + 4 * (lane >> 4) + e;
                 const int q = q_base + wq * 64 + j * 16 + (lane & 15);
-                if (MODE != 2 || q < ldq) out[(int64_t)p * ldq + q] = acc[i][j][e];
+                if ((MODE != 2 && MODE != 4) || q < ldq) out[(int64_t)p * ldq + q] = acc[i][j][e];
             }
 }
 

@@ -52,12 +52,12 @@ class BasicBlock(_Residual):
 
     def _train_operands(self, device, general=False):
         """((cin, width, stride), eps, the learnable tensors, the running statistics) as the kernels take them, validated.  `general`: the
-        four geometries of basic_block_train (layer3's and layer4's) instead of layer4's two."""
+        six geometries of basic_block_train (layer2's, layer3's and layer4's) instead of layer4's two."""
         cin, width = self.conv1.in_channels, self.conv1.out_channels
         ds = hasattr(self, "downsample")
         if general and (cin, width, self.stride, ds) not in _BLOCK_GEOMETRIES:
-            raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): basic_block_train is built for ResNet-18's layer3 and layer4 "
-                               "(128 -> 256 and 256 -> 512 stride 2 with downsample, 256 -> 256 and 512 -> 512 stride 1)")
+            raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): basic_block_train is built for ResNet-18's layer2, layer3 and layer4 "
+                               "(64 -> 128, 128 -> 256 and 256 -> 512 stride 2 with downsample, 128 -> 128, 256 -> 256 and 512 -> 512 stride 1)")
         if not general and (cin, width, self.stride, ds) not in ((256, 512, 2, True), (512, 512, 1, False)):
             raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): the HIP training kernels are built for ResNet-18's layer4 only "
                                "(256 -> 512 stride 2 with downsample, 512 -> 512 stride 1)")
@@ -90,13 +90,13 @@ class BasicBlock(_Residual):
         return _BasicBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
 
 
-_BLOCK_GEOMETRIES = ((128, 256, 2, True), (256, 256, 1, False), (256, 512, 2, True), (512, 512, 1, False))
+_BLOCK_GEOMETRIES = ((64, 128, 2, True), (128, 128, 1, False), (128, 256, 2, True), (256, 256, 1, False), (256, 512, 2, True), (512, 512, 1, False))
 
 
 def basic_block_train(block, x):
     """One BasicBlock on the HIP training kernels (csrc/resblock_train.hip, the vtd_resblock_train_* entries) as a differentiable function of
-    a CUDA NCHW tensor (fp32 or fp16), for the four blocks of ResNet-18's layer3 and layer4: 128 -> 256 and 256 -> 512 at stride 2 (with
-    downsample, even extents), 256 -> 256 and 512 -> 512 at stride 1.  Frozen-statistics BatchNorm, as ``block(x)``; returns ``[n,width,h,w]``
+    a CUDA NCHW tensor (fp32 or fp16), for the six blocks of ResNet-18's layer2, layer3 and layer4: 64 -> 128, 128 -> 256 and 256 -> 512 at
+    stride 2 (with downsample, even extents), 128 -> 128, 256 -> 256 and 512 -> 512 at stride 1.  Frozen-statistics BatchNorm, as ``block(x)``; returns ``[n,width,h,w]``
     fp32, differentiable w.r.t. the block's learnable tensors and w.r.t. ``x`` for either stride (the stride-2 blocks through the strided
     dgrad).  For layer4's blocks the output and the parameter gradients are the bits of ``block(x)``."""
     if not isinstance(block, BasicBlock):
@@ -219,8 +219,13 @@ class FeaturePyramidNetwork(nn.Module):
         srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None, layer4=None, layer3=None):
-        """With `layer3` too (ResNet-18's third stage, two BasicBlocks): layer3 -> layer4 -> FPN -> head as ONE autograd node on the padded taps
+    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None):
+        """With `layer2` too (ResNet-18's second stage): layer2 -> layer3 -> layer4 -> FPN -> head as ONE autograd node on the padded tap [C2]
+        (further entries are ignored: C3, C4 and C5 are computed here), differentiable w.r.t. the forty-five learnable tensors of the three
+        stages, the FPN's ten and the head's twenty.  dC3 is layer3.0's input gradient plus the FPN's dC3, dC4 as below; layer2.0 forms no
+        input gradient.
+
+        With `layer3` (ResNet-18's third stage, two BasicBlocks): layer3 -> layer4 -> FPN -> head as ONE autograd node on the padded taps
         [C2, C3] (further entries are ignored: C4 and C5 are computed here), differentiable w.r.t. the thirty learnable tensors of the two
         stages, the FPN's ten and the head's twenty.  dC4 is layer4.0's input gradient plus the FPN's dC4, added at one power-of-two scale.
 
@@ -233,6 +238,8 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if layer2 is not None:
+            return self._forward_padded_layer2(taps, head, layer4, layer3, layer2)
         if layer3 is not None:
             return self._forward_padded_layer3(taps, head, layer4, layer3)
         if layer4 is not None:
@@ -308,13 +315,66 @@ class FeaturePyramidNetwork(nn.Module):
         return {"probability": prob, "threshold": thresh}
 
 
-def _layer3_operands(layer3, c3_tap):
-    """ResNet-18's layer3 on a padded C3 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics)."""
+    def _forward_padded_layer2(self, taps, head, layer4, layer3, layer2):
+        if head is None or layer4 is None or layer3 is None:
+            raise ValueError("forward_padded(taps, layer2=...) is the training node: it needs layer3, layer4 and the DBHead too")
+        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
+            raise ValueError("padded taps must be the tensor [C2]")
+        c2 = taps[0].detach() if torch.is_tensor(taps[0]) else taps[0]
+        if not torch.is_tensor(c2) or not c2.is_cuda or c2.dtype != torch.float16 or not c2.is_contiguous() or c2.dim() != 4 or c2.shape[1] < 3 or c2.shape[2] < 3:
+            raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+        _, g2, eps2, learn2, stats2 = _layer2_operands(layer2, c2)
+        n, h3, w3 = g2[1][0], g2[1][1], g2[1][2]
+        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, torch.empty((n, h3 + 2, w3 + 2, 128), dtype=torch.float16, device="meta"), c2.device)
+        h4, w4 = g3[1][1], g3[1][2]
+        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, torch.empty((n, h4 + 2, w4 + 2, 256), dtype=torch.float16, device="meta"), c2.device)
+        if eps2 != eps3 or eps3 != eps4:
+            raise RuntimeError("layer2 / layer3 / layer4 training needs one BatchNorm eps")
+        h5, w5 = g4[1][1], g4[1][2]
+        geom = self._geometry([(n, c2.shape[3], c2.shape[1] - 2, c2.shape[2] - 2), (n, 128, h3, w3), (n, 256, h4, w4), (n, 512, h5, w5)])
+        params = self._live_checked(c2.device)
+        bns, hparams, hbuffers = head._train_operands(c2.device)
+        prob, thresh, _ = _Layer2Layer3Layer4FPNHeadTrainFn.apply((c2,), geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers),
+                                                                  tuple(g2 + g3 + g4), eps2, tuple(stats2 + stats3 + stats4), *learn2[0], *learn2[1],
+                                                                  *learn3[0], *learn3[1], *learn4[0], *learn4[1], *params, *hparams)
+        if head.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
+
+
+def _layer2_operands(layer2, c2_tap):
+    """ResNet-18's layer2 on a padded C2 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics)."""
+    blocks = list(layer2)
+    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
+        raise RuntimeError("layer2 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
+    n, h2, w2 = int(c2_tap.shape[0]), int(c2_tap.shape[1]) - 2, int(c2_tap.shape[2]) - 2
+    ops = [b._train_operands(c2_tap.device, general=True) for b in blocks]
+    if [o[0] for o in ops] != [(64, 128, 2), (128, 128, 1)] or c2_tap.shape[3] != 64:
+        raise RuntimeError("layer2 training is built for ResNet-18's layer2 (64 -> 128 stride 2, then 128 -> 128 stride 1)")
+    if h2 % 2 or w2 % 2 or ops[0][1] != ops[1][1]:
+        raise RuntimeError("layer2 training needs a C2 of even extents and one BatchNorm eps")
+    geoms = [(n, h2, w2, 64, 128, 2), (n, h2 // 2, w2 // 2, 128, 128, 1)]
+    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_layer2_padded(layer2, c2_tap):
+    """ResNet-18's layer2 on a padded C2 tap with the HIP training kernels, no gradient: padded C3 [n,h3+2,w3+2,128] fp16."""
+    _, geoms, eps, learn, stats = _layer2_operands(layer2, c2_tap)
+    with torch.no_grad():
+        mid, _ = _block_forward_raw(c2_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], _RESBLOCK)
+        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], _RESBLOCK)[0]
+
+
+def _layer3_operands(layer3, c3_tap, device=None):
+    """ResNet-18's layer3 on a padded C3 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics).
+    Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
     blocks = list(layer3)
     if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
         raise RuntimeError("layer3 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
     n, h3, w3 = int(c3_tap.shape[0]), int(c3_tap.shape[1]) - 2, int(c3_tap.shape[2]) - 2
-    ops = [b._train_operands(c3_tap.device, general=True) for b in blocks]
+    ops = [b._train_operands(c3_tap.device if device is None else device, general=True) for b in blocks]
     if [o[0] for o in ops] != [(128, 256, 2), (256, 256, 1)] or c3_tap.shape[3] != 128:
         raise RuntimeError("layer3 training is built for ResNet-18's layer3 (128 -> 256 stride 2, then 256 -> 256 stride 1)")
     if h3 % 2 or w3 % 2 or ops[0][1] != ops[1][1]:
@@ -489,7 +549,7 @@ def _block_struct(learn, stats=None):
     return st
 
 
-_RESBLOCK = "vtd_resblock_train"   # the entry family of the four geometries; the default below is layer4's two (no strided dgrad)
+_RESBLOCK = "vtd_resblock_train"   # the entry family of the six geometries; the default below is layer4's two (no strided dgrad)
 
 
 def _block_forward_raw(tap, geom, eps, learn, stats, entry="vtd_basicblock_train"):
@@ -567,7 +627,7 @@ class _BasicBlockTrainFn(torch.autograd.Function):
 
 
 class _ResBlockTrainFn(torch.autograd.Function):
-    """_BasicBlockTrainFn on the vtd_resblock_train_* entries: the four geometries, and `src` receives its gradient for either stride."""
+    """_BasicBlockTrainFn on the vtd_resblock_train_* entries: the six geometries, and `src` receives its gradient for either stride."""
 
     @staticmethod
     def forward(ctx, tap, src, geom, eps, stats, *learn):
@@ -818,6 +878,57 @@ class _Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
         return (None,) * 9 + (*g30, *g31, *g40, *g41, *fgrads, *hgrads)
 
 
+class _Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
+    """layer2 -> layer3 -> layer4 -> FPN -> DB head as one node on the padded tap C2.  The backward is _Layer3Layer4FPNHeadTrainFn's, continued:
+    the FPN's backward also forms dC3, layer3's first block forms its input gradient (the strided dgrad), the two are added at one
+    power-of-two scale (vtd_resblock_train_combine) and go into layer2's second block, whose dx goes into the first; layer2.0 forms no
+    input gradient.  Inputs: (C2,), FPN geom, the head's BatchNorm mode / momentum / eps and buffers, the six blocks' geometries, eps and
+    running statistics (layer2.0 .. layer4.1), then the learnable tensors: 3 x (9 + 6) of the blocks, the FPN's 10, the head's 20."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
+        blocks = (params[:9], params[9:15], params[15:24], params[24:30], params[30:39], params[39:45])
+        fpn_params, head_params = params[45:55], params[55:]
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        acts, bws, x = [], [], taps[0]
+        for i in range(6):                       # acts: layer2.0's output, C3, layer3.0's output, C4, layer4.0's output, C5
+            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _RESBLOCK)
+            acts.append(x)
+            bws.append(ws)
+        ftaps = (taps[0], acts[1], acts[3], acts[5])
+        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, *acts, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, m2, c3, m3, c4, m4, c5, *params = ctx.saved_tensors
+        blocks = (params[:9], params[9:15], params[15:24], params[24:30], params[30:39], params[39:45])
+        fpn_params, head_params = params[45:55], params[55:]
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        ftaps = (ctx.taps[0], c3, c4, c5)
+        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 2 | 4 | 8)      # dC3, dC4 and dC5
+        ins = (ctx.taps[0], m2, c3, m3, c4, m4)
+        outs = (m2, c3, m3, c4, m4, c5)
+        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
+                                                         dx, _RESBLOCK)
+        g41, d, ds = bwd(5, dtaps[3], scales[3], True)
+        g40, d, ds = bwd(4, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
+        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
+        g31, d, ds = bwd(3, d, ds, True)
+        g30, d, ds = bwd(2, d, ds, True)                      # layer3.0's share of dC3
+        d, ds = _combine_scaled(d, ds, dtaps[1], scales[1])   # + the FPN's
+        g21, d, ds = bwd(1, d, ds, True)
+        g20, _, _ = bwd(0, d, ds, False)
+        return (None,) * 9 + (*g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
+
+
 def pack_tap(feature):
     """[n,C,H,W] float32 / float16 CUDA tensor (C a multiple of 64) -> a padded tap (ring-padded NHWC fp16 [n,H+2,W+2,C]) on the device."""
     import ctypes as C
@@ -1006,8 +1117,12 @@ class DBNet(_EngineOwner, nn.Module):
         the trunk's, normalise with their running statistics, which are never written.  "head+fpn+layer4+layer3" (ResNet-18 only): one stage
         further down -- backbone.0 .. backbone.5 stop requiring grad; backbone.6, backbone.7, fpn and head train.  The trunk engine is keyed
         on the frozen tensors only and gives C2 and C3 (its C4 and C5 are ignored); layer3, layer4, the FPN and the head run on the HIP
-        training kernels as one autograd node.  layer4.0 forms its input gradient with the strided dgrad; dC4 is that plus the FPN's dC4."""
-        if trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3"):
+        training kernels as one autograd node.  layer4.0 forms its input gradient with the strided dgrad; dC4 is that plus the FPN's dC4.
+        "head+fpn+layer4+layer3+layer2" (ResNet-18 only): the usual fine-tuning recipe of a detection trunk -- the stem and layer1
+        (backbone.0 .. backbone.4) stop requiring grad; backbone.5 .. backbone.7, fpn and head train.  The trunk engine is keyed on the frozen
+        tensors only and gives C2 (its C3, C4 and C5 are ignored); layer2, layer3, layer4, the FPN and the head run on the HIP training
+        kernels as one autograd node.  dC3 is layer3.0's input gradient plus the FPN's dC3; layer2.0 forms no input gradient."""
+        if trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
             if self.backbone_name != "resnet18":
                 raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
                                  "Bottleneck training is not built")
@@ -1033,17 +1148,26 @@ class DBNet(_EngineOwner, nn.Module):
             for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
                 for p in m.parameters():
                     p.requires_grad_(True)
+        elif trainable == "head+fpn+layer4+layer3+layer2":
+            for i in range(5):
+                for p in self.backbone[i].parameters():
+                    p.requires_grad_(False)
+            for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
+                for p in m.parameters():
+                    p.requires_grad_(True)
         self._head_versions = None
         return self
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable in ("head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3"):
+        if self.trainable in ("head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
             tensors += list(self.fpn.parameters())
-        if self.trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3"):
+        if self.trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
             tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
-        if self.trainable == "head+fpn+layer4+layer3":
+        if self.trainable in ("head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
             tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
+        if self.trainable == "head+fpn+layer4+layer3+layer2":
+            tensors += list(self.backbone[5].parameters()) + list(self.backbone[5].buffers())
         return tuple(t._version for t in tensors)
 
     def trunk_engine(self):
@@ -1056,6 +1180,8 @@ class DBNet(_EngineOwner, nn.Module):
                 frozen = {k: v for k, v in frozen.items() if not k.startswith("7.")}
             elif self.trainable == "head+fpn+layer4+layer3":      # likewise: the engine's C4 and C5 are never read
                 frozen = {k: v for k, v in frozen.items() if not k.startswith(("6.", "7."))}
+            elif self.trainable == "head+fpn+layer4+layer3+layer2":      # likewise: only the engine's C2 is read
+                frozen = {k: v for k, v in frozen.items() if not k.startswith(("5.", "6.", "7."))}
             version = tuple(t._version for t in frozen.values())
             te = self.__dict__.get("_trunk_engine")
             if te is None or self.__dict__.get("_trunk_version") != version:
@@ -1098,8 +1224,10 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3"):
+        if self.trainable in ("head", "head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
             if self.training:
+                if self.trainable == "head+fpn+layer4+layer3+layer2":
+                    return self._forward_train_head_fpn_layer4_layer3_layer2(x)
                 if self.trainable == "head+fpn+layer4+layer3":
                     return self._forward_train_head_fpn_layer4_layer3(x)
                 if self.trainable == "head+fpn+layer4":
@@ -1165,6 +1293,21 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)   # C4 and C5 of the engine come from the weights it was built with: ignored
         out = self.fpn.forward_padded(taps[:2], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+
+    def _forward_train_head_fpn_layer4_layer3_layer2(self, x):
+        frozen = [n for i in range(5) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4+layer3+layer2'): {frozen[0]} requires grad, but backward below layer2 is not "
+                               "implemented; only layer2, layer3, layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. "
+                               "backbone.4)")
+        for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = self.trunk_engine().forward_trunk(x)   # C3, C4 and C5 of the engine come from the weights it was built with: ignored
+        out = self.fpn.forward_padded(taps[:1], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
