@@ -211,6 +211,9 @@ int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_de
  * array of four device pointers ordered C2, C3, C4, C5 (16-byte aligned).
  * vtd_detector_forward_trunk: the detector's ops up to the last residual stage of the current input, then a copy of the four taps into
  * caller-owned buffers.  Needs a handle finalized with "fuse_fpn_head" = 0 (the fused graph pads C2 differently): -2901 otherwise.
+ * vtd_detector_forward_pool: the detector's ops up to the pooled stem output (what layer1 reads), then a copy of that padded tap,
+ * [n][162][162][64] fp16 with a zero ring, into pool_dev (16-byte aligned).  Works on a handle of either "fuse_fpn_head" and either
+ * "fuse_stem_pool" setting; -2901 if the tap's ring is not 1, -2903 for a misaligned buffer.
  * vtd_fpn_train_pack_tap: [n][channels][H][W] NCHW float32 (dtype 0) or fp16 (dtype 1) -> a padded tap, ring included; channels % 64 == 0.
  *
  * Parameters are torch's own tensors as device pointers, float32, contiguous: inner_w[i] / inner_b[i] = fpn.inner_blocks.i
@@ -241,6 +244,7 @@ typedef struct vtd_fpn_params {
     float *layer_w, *layer_b;
 } vtd_fpn_params;
 int vtd_detector_forward_trunk(vtd_detector* d, int n, void* c2_dev, void* c3_dev, void* c4_dev, void* c5_dev, vtd_stream stream);
+int vtd_detector_forward_pool(vtd_detector* d, int n, void* pool_dev, vtd_stream stream);
 int vtd_fpn_train_pack_tap(const void* x_dev, int dtype, int n, int channels, int height, int width, void* tap_dev, vtd_stream stream);
 int64_t vtd_fpn_train_workspace_bytes(int n, int h5, int w5, int c5_channels, int mode);
 int vtd_fpn_train_forward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, void* workspace_dev,
@@ -310,6 +314,22 @@ int vtd_resblock_train_backward(const void* x_dev, int n, int h_in, int w_in, in
                                 const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 int vtd_resblock_train_combine(float* a_dev, const float* ascale_dev, const float* b_dev, const float* bscale_dev, int64_t numel, float* outscale_dev,
                                vtd_stream stream);
+
+/* The same block on ResNet-18's layer1 geometry, (cin 64, width 64, stride 1, identity: ds_* ignored), and on no other: the six geometries
+ * above and everything else are refused here, as (64, 64, 1) is refused by vtd_resblock_train_* and vtd_basicblock_train_*.  Arguments,
+ * layouts and numerics are those of vtd_resblock_train_*, argument for argument; dx_dev (optional) is NHWC float32 [n][h_in][w_in][64] times
+ * dxscale_dev[0].  Two fixed orders are the 64-wide block's own.  Its per-channel sums add four row quarters per workgroup: a workgroup's r
+ * rows are cut at ceil(k r / 4), k = 0..4, each quarter is summed in row order in fp64 and the partial is (q0 + q1) + (q2 + q3); the
+ * partials are then added in workgroup order as for every width.  Each of its two weight-gradient launches (K = 9 x 64 = 576: five q-tiles of
+ * 128 columns, a tap per 64-column group, the last group empty) cuts the rows into min(ceil(512 / 5), ceil(rows / 1024)) slabs of [64][576]
+ * floats, the 128-wide rule, summed in slab order.  There is no downsample and no strided input gradient.  No atomics, shape-only grids:
+ * bitwise repeatable.  Errors: -3201 (argument / unsupported geometry), -3202 (alignment), before any launch. */
+int64_t vtd_block64_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_block64_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                              float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_block64_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                               const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */

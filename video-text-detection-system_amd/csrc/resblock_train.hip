@@ -1,7 +1,8 @@
 // ResNet BasicBlock training with frozen-statistics BatchNorm (the running statistics normalise and are never written; gamma and beta
 // learn), forward and backward, for the blocks of ResNet-18's layer2, layer3 and layer4: (64 -> 128, stride 2, downsample), (128 -> 128,
-// stride 1), (128 -> 256, stride 2, downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W
-// below is the block's width (128, 256 or 512), a launch argument.
+// stride 1), (128 -> 256, stride 2, downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1);
+// and for layer1's (64 -> 64, stride 1) behind entries of its own (vtd_block64_train_*).  W below is the block's width (64, 128, 256 or
+// 512), a launch argument.
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
 //
 // Forward:
@@ -14,12 +15,16 @@
 //   reduce / finish  per-channel fp64 sums s_c in a fixed order, max |.|, a power-of-two scale; form: the fp16 operands (flat and ring-padded).
 //                    W = 128: the 256 threads of a workgroup are two halves of 128 channels; the lower half sums the first ceil(r / 2) of
 //                    the workgroup's r rows in row order, the upper half the rest, and the partial is lower + upper
+//                    W = 64: four quarters of 64 channels; quarter k sums rows ceil(k r / 4) .. ceil((k + 1) r / 4) - 1 of the workgroup's r
+//                    rows in row order, and the partial is (q0 + q1) + (q2 + q3)
 //   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h (W / 128 128-column tiles; 3x3 / 1x1 gather at stride 1 / 2), slabs.
 //   wgrad<4>         the same over layer2.0's 64-channel input (conv1: K = 576, the downsample: K = 64): a 64-column group per tap.
 //                    Slabs: W = 256 and 512 cut the rows into min(8, ceil(rows / 4096)) slabs for every launch of a block.  W = 128 has
 //                    one column tile, so each launch takes min(ceil(512 / q-tiles), ceil(rows / 1024)) slabs: two workgroups per CU of
 //                    the 256 when the rows allow slabs of 1024 (conv2 and layer2.1's conv1, 9 q-tiles: 57; layer2.0's conv1, 5: 103; its
 //                    downsample, 1: 512)
+//   wgrad<5>         W = 64 (layer1): the 64-row tile over the 64-channel input, K = 576 = 5 q-tiles (the last half empty), slab
+//                    [64][576]; slabs by the 128-wide rule: min(ceil(512 / 5), ceil(rows / 1024)) = min(103, .)
 //   param            slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s): no division by gamma
 //   dgrad            da1 = conv2^T(g2): conv_igemm.hip on the folded weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
 //   dx (stride 1)    conv1^T(g1) the same way, plus g2 brought to the same scale
@@ -44,8 +49,9 @@ constexpr int RB_THREADS = 256;
 constexpr int RB_MAX_RED = 256;
 constexpr float RB_SCALE_TARGET = 16384.0f;
 // error bases: the vtd_basicblock_train_* entries (layer4's two geometries, no strided dgrad) answer -3001 / -3002 / -3003, the
-// vtd_resblock_train_* entries (six geometries) -3101 / -3102
-constexpr int RB_LEGACY = -3000, RB_GENERAL = -3100;
+// vtd_resblock_train_* entries (six geometries) -3101 / -3102, the vtd_block64_train_* entries (layer1's 64 -> 64 stride 1 alone)
+// -3201 / -3202
+constexpr int RB_LEGACY = -3000, RB_GENERAL = -3100, RB_NARROW = -3200;
 
 inline int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline unsigned nblk(int64_t items) { return (unsigned)((items + RB_THREADS - 1) / RB_THREADS); }
@@ -56,9 +62,14 @@ struct Geo {
     bool ds;
 };
 
-bool make_geo(int n, int hin, int win, int cin, int width, int stride, bool legacy, Geo& g) {
+bool make_geo(int n, int hin, int win, int cin, int width, int stride, int base, Geo& g) {
+    const bool legacy = base == RB_LEGACY;
     if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096) return false;
-    if (width != 512 && (legacy || (width != 256 && width != 128))) return false;
+    if (base == RB_NARROW) {   // layer1's block and nothing else; width 64 under no other base
+        if (width != 64 || cin != 64 || stride != 1) return false;
+    } else if (width != 512 && (legacy || (width != 256 && width != 128))) {
+        return false;
+    }
     if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
     g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.width = width; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w;
@@ -105,6 +116,7 @@ BwdLayout bwd_layout(const Geo& g, bool strided) {
     L.sum2 = take(W * 8); L.sum1 = take(W * 8);
     L.sc = take(2 * 4 * 4);
     int64_t slab = (int64_t)wg_slabs(g.m) * W * 9 * W;
+    if (W == 64) slab = (int64_t)wg_slabs128(g.m, wg_nqt(3, 64)) * 64 * 9 * 64;   // conv2 and conv1 alike: 5 q-tiles, slab [64][576]
     if (W == 128) {   // per launch: conv2, conv1, the downsample
         slab = (int64_t)wg_slabs128(g.m, wg_nqt(3, 128)) * W * 9 * 128;
         const int64_t c1 = (int64_t)wg_slabs128(g.m, wg_nqt(3, g.cin)) * W * 9 * g.cin, dsl = g.ds ? (int64_t)wg_slabs128(g.m, wg_nqt(1, g.cin)) * W * g.cin : 0;
@@ -216,6 +228,32 @@ __global__ __launch_bounds__(RB_THREADS) void rb_reduce128_kernel(const float* v
     if (t == 0) {
         float m = shm[0];
         for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
+        pmax[blockIdx.x] = m;
+    }
+}
+
+// v [rows][64] fp32: thread t owns channel t % 64 over one quarter of the workgroup's rows m0 .. m1 in row order: quarter k = t / 64 takes
+// rows m0 + ceil(k r / 4) .. m0 + ceil((k + 1) r / 4) - 1 of the r = m1 - m0; part[g][c] = (q0 + q1) + (q2 + q3), fp64; pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce64_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
+    const int t = threadIdx.x, c = t & 63, k = t >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t r = m1 - m0, lo = m0 + (k * r + 3) / 4, hi = m0 + ((k + 1) * r + 3) / 4;
+    double s = 0.0;
+    float mx = 0.f;
+    for (int64_t m = lo; m < hi; ++m) {
+        const float a = v[m * 64 + c], fa = fabsf(a);
+        s += (double)a;
+        mx = fa > mx || fa != fa ? fa : mx;
+    }
+    __shared__ double shs[RB_THREADS];
+    __shared__ float shm[RB_THREADS];
+    shs[t] = s;
+    shm[t] = mx;
+    __syncthreads();
+    if (k == 0) part[(int64_t)blockIdx.x * 64 + c] = (shs[c] + shs[64 + c]) + (shs[128 + c] + shs[192 + c]);
+    if (t == 0) {
+        float m = shm[0];
+        for (int j = 1; j < RB_THREADS; ++j) m = shm[j] > m || shm[j] != shm[j] ? shm[j] : m;
         pmax[blockIdx.x] = m;
     }
 }
@@ -401,14 +439,14 @@ void to_padded(ConvParams& c, const Geo& g, half_t* out) {
 
 int64_t ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode, int base) {
     Geo g;
-    if (!make_geo(n, hin, win, cin, width, stride, base == RB_LEGACY, g) || mode < 0 || mode > 1) return base - 1;
+    if (!make_geo(n, hin, win, cin, width, stride, base, g) || mode < 0 || mode > 1) return base - 1;
     return mode ? bwd_layout(g, base != RB_LEGACY && g.ds).total : fwd_layout(g).total;
 }
 
 int launch_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws, void* y,
                    hipStream_t s, int base) {
     Geo g;
-    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, base == RB_LEGACY, g) || !params_ok(P, g.ds) || !(eps > 0.f)) return base - 1;
+    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, base, g) || !params_ok(P, g.ds) || !(eps > 0.f)) return base - 1;
     if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255)) return base - 2;
     const FwdLayout L = fwd_layout(g);
     const int W = width;
@@ -448,7 +486,7 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
                     hipStream_t s, int base) {
     Geo g;
     const bool legacy = base == RB_LEGACY;
-    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, legacy, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
+    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, base, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
         !(eps > 0.f) || (dx && !dxscale))
         return base - 1;
     if (legacy && dx && g.stride != 1) return base - 3;
@@ -475,7 +513,9 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
 
     auto stage = [&](const float* v, const half_t* act, float* gout, const float* in_sc, double* sum, float* out_sc, half_t* flat, half_t* padded) {
         hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, v, act, M, g.h, g.w, W, gout);
-        if (W == 128)
+        if (W == 64)
+            hipLaunchKernelGGL(rb_reduce64_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, part, pmax);
+        else if (W == 128)
             hipLaunchKernelGGL(rb_reduce128_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, part, pmax);
         else
             hipLaunchKernelGGL(rb_reduce_kernel, dim3(Gr), dim3(RB_THREADS), 0, s, (const float*)gout, M, per, W, part, pmax);
@@ -488,9 +528,11 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
                      const float* gam, const float* mean, const float* var, float* dw, float* dgam, float* dbet) {
         WgArgs wa;
         wa.a = a; wa.lda = W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
-        const int nqt = wg_nqt(ksz, xc), Sl = W == 128 ? wg_slabs128(M, nqt) : S;
+        const int nqt = wg_nqt(ksz, xc), Sl = W <= 128 ? wg_slabs128(M, nqt) : S;
         wa.slab_len = slab_rows(M, Sl); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
-        if (xc & 127)   // layer2.0's 64-channel input: a tap per 64-column group
+        if (W == 64)   // layer1: the 64-row tile, one column tile, slab [64][576]
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<5>, dim3(nqt * Sl, 1), dim3(WG_THREADS), 0, s, wa);
+        else if (xc & 127)   // layer2.0's 64-channel input: a tap per 64-column group
             hipLaunchKernelGGL(dbhead_train_wgrad_kernel<4>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
         else
             hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
@@ -574,6 +616,22 @@ int vtd_launch_resblock_backward(const void* x, int n, int hin, int win, int cin
                                  const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
                                  float* dx, float* dxscale, hipStream_t s) {
     return launch_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, RB_GENERAL);
+}
+
+// layer1's geometry alone: (64 -> 64, stride 1)
+int64_t vtd_block64_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(n, hin, win, cin, width, stride, mode, RB_NARROW);
+}
+
+int vtd_launch_block64_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
+                               void* y, hipStream_t s) {
+    return launch_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s, RB_NARROW);
+}
+
+int vtd_launch_block64_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, RB_NARROW);
 }
 
 int vtd_launch_resblock_combine(float* a, const float* asc, const float* b, const float* bsc, int64_t numel, float* osc, hipStream_t s) {

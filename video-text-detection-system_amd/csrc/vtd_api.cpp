@@ -80,6 +80,12 @@ int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int c
                                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
                                    float* dx, float* dxscale, hipStream_t s);
 int64_t vtd_resblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int64_t vtd_block64_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_block64_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
+                               void* y, hipStream_t s);
+int vtd_launch_block64_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                float* dx, float* dxscale, hipStream_t s);
 int vtd_launch_resblock_combine(float* a, const float* asc, const float* b, const float* bsc, int64_t numel, float* osc, hipStream_t s);
 int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
                                 void* y, hipStream_t s);
@@ -602,6 +608,7 @@ struct vtd_detector : vtd::ModelBase {
     bool fuse_stem_pool = true;  // conv7x7/s2 + BN + ReLU + maxpool3x3/s2 in one kernel (the 320x320x64 map is never written)
     bool fuse_fpn_head = true;  // compose FPN lateral(C2) + top-down add + P2 smooth + head conv into one classed conv
     bool fuse_downsample = true;  // a downsample block's 1x1 projection rides in the block's last conv as extra K-steps (attach_second_segment)
+    size_t pool_ops = 0;  // ops up to and including the one that writes the pooled stem output (vtd_detector_forward_pool)
     size_t trunk_ops = 0;  // ops up to and including the last residual stage (vtd_detector_forward_trunk)
     size_t p2_ops = 0;  // unfused graph: ops up to and including the one that writes P2 (vtd_detector_forward_features)
     // optional per-op HIP-event timing (bench / roofline accounting)
@@ -1155,6 +1162,7 @@ static int build_detector_graph(vtd_detector* d) {
         d->ops.push_back(o);
     }
     d->taps["pool"] = x;
+    d->pool_ops = d->ops.size();
 
     // residual stages
     TensorDesc tapsC[4];
@@ -1438,6 +1446,8 @@ const char* vtd_strerror(int code) {
         case -3101: return "ResNet block training: invalid argument or unsupported geometry (built: 128 -> 256 and 256 -> 512 stride 2 with even "
                            "extents, 256 -> 256 and 512 -> 512 stride 1)";
         case -3102: return "ResNet block training: misaligned buffer";
+        case -3201: return "64-wide block training: invalid argument or unsupported geometry (built: 64 -> 64 stride 1, ResNet-18's layer1)";
+        case -3202: return "64-wide block training: misaligned buffer";
         default: break;
     }
     if (code <= -1000) {
@@ -1559,6 +1569,22 @@ int vtd_resblock_train_backward(const void* x_dev, int n, int h_in, int w_in, in
 int vtd_resblock_train_combine(float* a_dev, const float* ascale_dev, const float* b_dev, const float* bscale_dev, int64_t numel, float* outscale_dev,
                                vtd_stream stream) {
     return vtd_launch_resblock_combine(a_dev, ascale_dev, b_dev, bscale_dev, numel, outscale_dev, (hipStream_t)stream);
+}
+
+int64_t vtd_block64_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_block64_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_block64_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                              float eps, void* workspace_dev, void* y_dev, vtd_stream stream) {
+    return vtd_launch_block64_forward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, (hipStream_t)stream);
+}
+
+int vtd_block64_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                               const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
+    return vtd_launch_block64_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
+                                       scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 
 int64_t vtd_fpn_train_input_workspace_bytes(int n, int h5, int w5, int c5_channels) { return vtd_fpn_input_ws_bytes(n, h5, w5, c5_channels); }
@@ -1737,6 +1763,22 @@ int vtd_detector_forward_trunk(vtd_detector* d, int n, void* c2_dev, void* c3_de
         const TensorDesc& t = d->taps[names[i]];
         VTD_HIP_CHECK(hipMemcpyAsync(dst[i], t.ptr, (size_t)n * t.hp * t.wp * t.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
     }
+    return 0;
+}
+
+// the stem and its max-pool only, then a copy of the n frames' ring-padded pooled map (what layer1 reads: [n][162][162][64] fp16)
+int vtd_detector_forward_pool(vtd_detector* d, int n, void* pool_dev, vtd_stream stream) {
+    if (!d || !pool_dev) return ERR_ARG;
+    if (!d->finalized) return ERR_NOT_FINALIZED;
+    if (n <= 0 || n > d->max_batch) return ERR_BATCH;
+    auto it = d->taps.find("pool");
+    if (!d->pool_ops || it == d->taps.end() || it->second.ring != 1) return -2901;
+    if ((uintptr_t)pool_dev & 15) return -2903;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_detector_ops(d, n, nullptr, nullptr, s, d->pool_ops);
+    if (rc) return rc;
+    const TensorDesc& t = it->second;
+    VTD_HIP_CHECK(hipMemcpyAsync(pool_dev, t.ptr, (size_t)n * t.hp * t.wp * t.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

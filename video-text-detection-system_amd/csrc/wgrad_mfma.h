@@ -15,6 +15,9 @@
 //   (128 qt + 64 grp) % xc of tap (128 qt + 64 grp) / xc, so with xc = 64 a q-tile holds two taps.  ceil(ksz^2 xc / 128) q-tiles; columns at
 //   or past ksz^2 xc (the second half of the last q-tile: K = 576 is 4.5 q-tiles, K = 64 half of one) load zeros and are not stored, as
 //   MODE 2's.  slab [128 gridDim.y][ksz^2 xc].
+// MODE 5 (a 64-wide ResNet block's 3x3 convolutions, layer1's): A = the 64 columns of a 64-wide gradient (lda = 64, gridDim.y = 1) on
+//   MODE 1's 64-row tile (P_T = 64), B decoded as MODE 4's (xc = 64: a tap per 64-column group, K = 576 = 4.5 q-tiles, columns at or
+//   past K load zeros and are not stored).  slab [64][ksz^2 xc]: the slab stride is 64 rows, not 128 gridDim.y.
 // Workgroup = 4 waves, one (q-tile, slab); each wave a (P_T / 2) x 64 block.  Per K chunk of 32 rows every thread loads rows 8o .. 8o+7
 // of one column pair of A and B with 4-byte loads (the next chunk's loads are in flight during this chunk's MFMAs), transposes them into
 // LDS as [row octet][column][8] so that a fragment (8 consecutive rows of one column) is one 16-byte read, double-buffered: one barrier
@@ -37,7 +40,7 @@ struct WgArgs {
     int n, H, W;
     int64_t rows, slab_len;
     float* slab;
-    int ksz, stride, Hin, Win;   // MODES 3 and 4 only
+    int ksz, stride, Hin, Win;   // MODES 3, 4 and 5 only
 };
 
 template <int MODE>
@@ -53,7 +56,7 @@ __device__ __forceinline__ const half_t* wg_brow(const WgArgs& A, int img, int y
     } else if constexpr (MODE == 3) {
         const int q0 = qt * 128, tap = q0 / A.xc, c0 = q0 - tap * A.xc, ky = tap / A.ksz, kx = tap - ky * A.ksz, o = 1 - (A.ksz >> 1);
         return A.x + (((int64_t)img * (A.Hin + 2) + y * A.stride + ky + o) * (A.Win + 2) + xx * A.stride + kx + o) * A.xc + c0 + grp * 64;
-    } else {
+    } else {   // MODES 4 and 5
         const int q0 = qt * 128 + grp * 64, tap = q0 / A.xc, c0 = q0 - tap * A.xc, ky = tap / A.ksz, kx = tap - ky * A.ksz, o = 1 - (A.ksz >> 1);
         return A.x + (((int64_t)img * (A.Hin + 2) + y * A.stride + ky + o) * (A.Win + 2) + xx * A.stride + kx + o) * A.xc + c0;
     }
@@ -61,12 +64,12 @@ __device__ __forceinline__ const half_t* wg_brow(const WgArgs& A, int img, int y
 
 template <int MODE>
 __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const WgArgs A) {
-    constexpr int PT = MODE == 1 ? 64 : 128, QT = 128, FP = PT / 32, FQ = 4;
+    constexpr int PT = (MODE == 1 || MODE == 5) ? 64 : 128, QT = 128, FP = PT / 32, FQ = 4;
     const int NQT = MODE == 0 ? 18 : MODE == 1 ? 4 : MODE == 2 ? (A.xc + 127) / 128 : MODE == 3 ? A.ksz * A.ksz * A.xc / 128
                                                                                        : (A.ksz * A.ksz * A.xc + 127) / 128;
     const int qt = blockIdx.x % NQT, sl = blockIdx.x / NQT, pt = blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wp = w >> 1, wq = w & 1;
-    const int a_col0 = MODE == 1 ? (qt >> 1) * 128 : pt * 128;   // MODE 1: the hi half of the branch's a1 pair
+    const int a_col0 = MODE == 1 ? (qt >> 1) * 128 : MODE == 5 ? 0 : pt * 128;   // MODE 1: the hi half of the branch's a1 pair
     __shared__ __attribute__((aligned(16))) half_t lds[2][4 * (PT + QT) * 8];
 
     const int64_t r0 = (int64_t)sl * A.slab_len;
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const Wg
     const int bp = t % (QT / 2), bo = t / (QT / 2);          // bo in 0..3
     const bool a_act = ao < 4;
     const int bgrp = (2 * bp) / 64, bcol = (2 * bp) % 64;
-    const bool b_act = MODE == 2 ? qt * 128 + bgrp * 64 < A.xc : MODE == 4 ? qt * 128 + bgrp * 64 < A.ksz * A.ksz * A.xc : true;
+    const bool b_act = MODE == 2 ? qt * 128 + bgrp * 64 < A.xc : (MODE == 4 || MODE == 5) ? qt * 128 + bgrp * 64 < A.ksz * A.ksz * A.xc : true;
     const int HW = A.H * A.W;
 
     uint32_t ra[8], rb[8];
@@ -151,9 +154,9 @@ __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const Wg
 
     // C row p = wp * PT/2 + i*16 + 4*(lane>>4) + e, column q = wq*64 + j*16 + (lane&15)
     const int ldq = MODE == 0 ? 2304 : MODE == 1 ? 256 : MODE == 2 ? A.xc : A.ksz * A.ksz * A.xc;
-    const int64_t slab_elems = MODE == 1 ? 2 * 64 * 256 : (int64_t)gridDim.y * 128 * ldq;
+    const int64_t slab_elems = MODE == 1 ? 2 * 64 * 256 : MODE == 5 ? (int64_t)64 * ldq : (int64_t)gridDim.y * 128 * ldq;
     float* out = A.slab + (int64_t)sl * slab_elems;
-    const int p_base = MODE == 1 ? (qt >> 1) * 64 : pt * 128;
+    const int p_base = MODE == 1 ? (qt >> 1) * 64 : MODE == 5 ? 0 : pt * 128;
     const int q_base = MODE == 1 ? (qt & 1) * 128 : qt * 128;
 #pragma unroll
     for (int i = 0; i < FP; ++i)
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(WG_THREADS) void dbhead_train_wgrad_kernel(const Wg
             for (int e = 0; e < 4; ++e) {
                 const int p = p_base + wp * (PT / 2) + i * 16 + 4 * (lane >> 4) + e;
                 const int q = q_base + wq * 64 + j * 16 + (lane & 15);
-                if ((MODE != 2 && MODE != 4) || q < ldq) out[(int64_t)p * ldq + q] = acc[i][j][e];
+                if ((MODE != 2 && MODE != 4 && MODE != 5) || q < ldq) out[(int64_t)p * ldq + q] = acc[i][j][e];
             }
 }
 

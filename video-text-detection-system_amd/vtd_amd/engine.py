@@ -240,6 +240,17 @@ class DetectorEngine(_Tunable):
             del keep
             return taps
 
+    def forward_pool(self, x):
+        """The pooled stem output of the input (what ResNet's layer1 reads) as a new padded-tap tensor, ring-padded NHWC fp16
+        [n,162,162,64] with a zero ring (include/vtd.h vtd_detector_forward_pool).  Only the stem runs."""
+        with self.lock:
+            n, keep = self._set_input(x)
+            tap = torch.empty((n, 162, 162, 64), dtype=torch.float16, device="cuda")
+            _native.check(self.lib.vtd_detector_forward_pool(self.handle, n, C.c_void_p(tap.data_ptr()), _stream_ptr()),
+                          "vtd_detector_forward_pool")
+            del keep
+            return tap
+
     def read_tap(self, name, n):
         shapes = {"input": (3, 640, 640), "stem": (64, 320, 320), "pool": (64, 160, 160), "p2": (256, 160, 160), "head1": (64, 160, 160),
                   "head2": (64, 320, 320)}

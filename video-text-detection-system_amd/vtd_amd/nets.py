@@ -50,15 +50,18 @@ class BasicBlock(_Residual):
         if stride != 1 or cin != width:
             self.downsample = nn.Sequential(*_conv_bn(cin, width, 1, stride, 0))
 
-    def _train_operands(self, device, general=False):
+    def _train_operands(self, device, general=False, narrow=False):
         """((cin, width, stride), eps, the learnable tensors, the running statistics) as the kernels take them, validated.  `general`: the
-        six geometries of basic_block_train (layer2's, layer3's and layer4's) instead of layer4's two."""
+        six geometries of the vtd_resblock_train_* entries (layer2's, layer3's and layer4's) instead of layer4's two.  `narrow`: layer1's
+        64 -> 64 stride-1 block (the vtd_block64_train_* entries) is admitted too; every other geometry is judged as without it."""
         cin, width = self.conv1.in_channels, self.conv1.out_channels
         ds = hasattr(self, "downsample")
-        if general and (cin, width, self.stride, ds) not in _BLOCK_GEOMETRIES:
+        if narrow and (cin, width, self.stride, ds) == _BLOCK64_GEOMETRY:
+            pass
+        elif general and (cin, width, self.stride, ds) not in _BLOCK_GEOMETRIES:
             raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): basic_block_train is built for ResNet-18's layer2, layer3 and layer4 "
                                "(64 -> 128, 128 -> 256 and 256 -> 512 stride 2 with downsample, 128 -> 128, 256 -> 256 and 512 -> 512 stride 1)")
-        if not general and (cin, width, self.stride, ds) not in ((256, 512, 2, True), (512, 512, 1, False)):
+        elif not general and (cin, width, self.stride, ds) not in ((256, 512, 2, True), (512, 512, 1, False)):
             raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {self.stride}): the HIP training kernels are built for ResNet-18's layer4 only "
                                "(256 -> 512 stride 2 with downsample, 512 -> 512 stride 1)")
         pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)] + ([(self.downsample[0], self.downsample[1])] if ds else [])
@@ -91,21 +94,23 @@ class BasicBlock(_Residual):
 
 
 _BLOCK_GEOMETRIES = ((64, 128, 2, True), (128, 128, 1, False), (128, 256, 2, True), (256, 256, 1, False), (256, 512, 2, True), (512, 512, 1, False))
+_BLOCK64_GEOMETRY = (64, 64, 1, False)   # layer1's, behind entries of its own
 
 
 def basic_block_train(block, x):
-    """One BasicBlock on the HIP training kernels (csrc/resblock_train.hip, the vtd_resblock_train_* entries) as a differentiable function of
-    a CUDA NCHW tensor (fp32 or fp16), for the six blocks of ResNet-18's layer2, layer3 and layer4: 64 -> 128, 128 -> 256 and 256 -> 512 at
-    stride 2 (with downsample, even extents), 128 -> 128, 256 -> 256 and 512 -> 512 at stride 1.  Frozen-statistics BatchNorm, as ``block(x)``; returns ``[n,width,h,w]``
-    fp32, differentiable w.r.t. the block's learnable tensors and w.r.t. ``x`` for either stride (the stride-2 blocks through the strided
-    dgrad).  For layer4's blocks the output and the parameter gradients are the bits of ``block(x)``."""
+    """One BasicBlock on the HIP training kernels (csrc/resblock_train.hip) as a differentiable function of a CUDA NCHW tensor (fp32 or
+    fp16), for the seven blocks of ResNet-18's four stages: 64 -> 64 at stride 1 (layer1's, on the vtd_block64_train_* entries), and on the
+    vtd_resblock_train_* entries 64 -> 128, 128 -> 256 and 256 -> 512 at stride 2 (with downsample, even extents), 128 -> 128, 256 -> 256
+    and 512 -> 512 at stride 1.  Frozen-statistics BatchNorm, as ``block(x)``; returns ``[n,width,h,w]`` fp32, differentiable w.r.t. the
+    block's learnable tensors and w.r.t. ``x`` for either stride (the stride-2 blocks through the strided dgrad).  For layer4's blocks the
+    output and the parameter gradients are the bits of ``block(x)``."""
     if not isinstance(block, BasicBlock):
         raise RuntimeError("basic_block_train is built for ResNet-18's BasicBlocks; Bottleneck training is not built")
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != block.conv1.in_channels:
         raise ValueError(f"BasicBlock input must be a [n,{block.conv1.in_channels},H,W] tensor")
     if not x.is_cuda:
         raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
-    (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=True)
+    (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=True, narrow=True)
     n, _, hin, win = x.shape
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
         raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
@@ -219,8 +224,13 @@ class FeaturePyramidNetwork(nn.Module):
         srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None):
-        """With `layer2` too (ResNet-18's second stage): layer2 -> layer3 -> layer4 -> FPN -> head as ONE autograd node on the padded tap [C2]
+    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None):
+        """With `layer1` too (ResNet-18's first stage, two 64 -> 64 BasicBlocks): layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head as ONE
+        autograd node on the padded tap [pool] (the pooled stem output, e.g. DetectorEngine.forward_pool; C2..C5 are computed here),
+        differentiable w.r.t. layer1's twelve learnable tensors, the forty-five of the three stages above, the FPN's ten and the head's
+        twenty.  dC2 is layer2.0's input gradient (the strided dgrad) plus the FPN's dC2; layer1.0 forms no input gradient.
+
+        With `layer2` too (ResNet-18's second stage): layer2 -> layer3 -> layer4 -> FPN -> head as ONE autograd node on the padded tap [C2]
         (further entries are ignored: C3, C4 and C5 are computed here), differentiable w.r.t. the forty-five learnable tensors of the three
         stages, the FPN's ten and the head's twenty.  dC3 is layer3.0's input gradient plus the FPN's dC3, dC4 as below; layer2.0 forms no
         input gradient.
@@ -238,6 +248,8 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if layer1 is not None:
+            return self._forward_padded_layer1(taps, head, layer4, layer3, layer2, layer1)
         if layer2 is not None:
             return self._forward_padded_layer2(taps, head, layer4, layer3, layer2)
         if layer3 is not None:
@@ -344,13 +356,74 @@ class FeaturePyramidNetwork(nn.Module):
         return {"probability": prob, "threshold": thresh}
 
 
-def _layer2_operands(layer2, c2_tap):
-    """ResNet-18's layer2 on a padded C2 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics)."""
+    def _forward_padded_layer1(self, taps, head, layer4, layer3, layer2, layer1):
+        if head is None or layer4 is None or layer3 is None or layer2 is None:
+            raise ValueError("forward_padded(taps, layer1=...) is the training node: it needs layer2, layer3, layer4 and the DBHead too")
+        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
+            raise ValueError("padded taps must be the tensor [pool]")
+        pool = taps[0].detach() if torch.is_tensor(taps[0]) else taps[0]
+        if (not torch.is_tensor(pool) or not pool.is_cuda or pool.dtype != torch.float16 or not pool.is_contiguous() or pool.dim() != 4 or pool.shape[1] < 3
+                or pool.shape[2] < 3):
+            raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+        dev = pool.device
+        meta = lambda n, h, w, c: torch.empty((n, h + 2, w + 2, c), dtype=torch.float16, device="meta")  # noqa: E731
+        _, g1, eps1, learn1, stats1 = _layer1_operands(layer1, pool)
+        n, h2, w2 = g1[0][0], g1[0][1], g1[0][2]
+        _, g2, eps2, learn2, stats2 = _layer2_operands(layer2, meta(n, h2, w2, 64), dev)
+        h3, w3 = g2[1][1], g2[1][2]
+        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, meta(n, h3, w3, 128), dev)
+        h4, w4 = g3[1][1], g3[1][2]
+        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, meta(n, h4, w4, 256), dev)
+        if eps1 != eps2 or eps2 != eps3 or eps3 != eps4:
+            raise RuntimeError("layer1 / layer2 / layer3 / layer4 training needs one BatchNorm eps")
+        h5, w5 = g4[1][1], g4[1][2]
+        geom = self._geometry([(n, 64, h2, w2), (n, 128, h3, w3), (n, 256, h4, w4), (n, 512, h5, w5)])
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        prob, thresh, _ = _Layer1Layer2Layer3Layer4FPNHeadTrainFn.apply((pool,), geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers),
+                                                                        tuple(g1 + g2 + g3 + g4), eps1, tuple(stats1 + stats2 + stats3 + stats4),
+                                                                        *learn1[0], *learn1[1], *learn2[0], *learn2[1], *learn3[0], *learn3[1],
+                                                                        *learn4[0], *learn4[1], *params, *hparams)
+        if head.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
+
+
+def _layer1_operands(layer1, pool_tap):
+    """ResNet-18's layer1 on a padded tap of the pooled stem output: (the two blocks, their geometries, eps, their learnable tensors, their
+    running statistics)."""
+    blocks = list(layer1)
+    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
+        raise RuntimeError("layer1 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
+    n, h, w = int(pool_tap.shape[0]), int(pool_tap.shape[1]) - 2, int(pool_tap.shape[2]) - 2
+    ops = [b._train_operands(pool_tap.device, general=True, narrow=True) for b in blocks]
+    if [o[0] for o in ops] != [(64, 64, 1), (64, 64, 1)] or pool_tap.shape[3] != 64:
+        raise RuntimeError("layer1 training is built for ResNet-18's layer1 (64 -> 64 stride 1, twice)")
+    if ops[0][1] != ops[1][1]:
+        raise RuntimeError("layer1 training needs one BatchNorm eps")
+    geoms = [(n, h, w, 64, 64, 1), (n, h, w, 64, 64, 1)]
+    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_layer1_padded(layer1, pool_tap):
+    """ResNet-18's layer1 on a padded tap of the pooled stem output with the HIP training kernels, no gradient: padded C2
+    [n,h+2,w+2,64] fp16."""
+    _, geoms, eps, learn, stats = _layer1_operands(layer1, pool_tap)
+    with torch.no_grad():
+        mid, _ = _block_forward_raw(pool_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], _BLOCK64)
+        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], _BLOCK64)[0]
+
+
+def _layer2_operands(layer2, c2_tap, device=None):
+    """ResNet-18's layer2 on a padded C2 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics).
+    Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
     blocks = list(layer2)
     if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
         raise RuntimeError("layer2 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
     n, h2, w2 = int(c2_tap.shape[0]), int(c2_tap.shape[1]) - 2, int(c2_tap.shape[2]) - 2
-    ops = [b._train_operands(c2_tap.device, general=True) for b in blocks]
+    ops = [b._train_operands(c2_tap.device if device is None else device, general=True) for b in blocks]
     if [o[0] for o in ops] != [(64, 128, 2), (128, 128, 1)] or c2_tap.shape[3] != 64:
         raise RuntimeError("layer2 training is built for ResNet-18's layer2 (64 -> 128 stride 2, then 128 -> 128 stride 1)")
     if h2 % 2 or w2 % 2 or ops[0][1] != ops[1][1]:
@@ -550,6 +623,12 @@ def _block_struct(learn, stats=None):
 
 
 _RESBLOCK = "vtd_resblock_train"   # the entry family of the six geometries; the default below is layer4's two (no strided dgrad)
+_BLOCK64 = "vtd_block64_train"     # the entry family of layer1's 64 -> 64 block
+
+
+def _block_entry(geom):
+    """The entry family of a block of basic_block_train's seven, by its width."""
+    return _BLOCK64 if geom[4] == 64 else _RESBLOCK
 
 
 def _block_forward_raw(tap, geom, eps, learn, stats, entry="vtd_basicblock_train"):
@@ -627,11 +706,12 @@ class _BasicBlockTrainFn(torch.autograd.Function):
 
 
 class _ResBlockTrainFn(torch.autograd.Function):
-    """_BasicBlockTrainFn on the vtd_resblock_train_* entries: the six geometries, and `src` receives its gradient for either stride."""
+    """_BasicBlockTrainFn on the vtd_resblock_train_* entries (the 64-wide block: vtd_block64_train_*): the seven geometries, and `src`
+    receives its gradient for either stride."""
 
     @staticmethod
     def forward(ctx, tap, src, geom, eps, stats, *learn):
-        y, ws = _block_forward_raw(tap, geom, eps, learn, stats, _RESBLOCK)
+        y, ws = _block_forward_raw(tap, geom, eps, learn, stats, _block_entry(geom))
         ctx.save_for_backward(tap, y, *stats, *learn)
         ctx.ws, ctx.geom, ctx.eps, ctx.nstats = ws, geom, eps, len(stats)
         ctx.src_dtype = None if src is None else src.dtype
@@ -645,7 +725,7 @@ class _ResBlockTrainFn(torch.autograd.Function):
         dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
         dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
         want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
-        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx, _RESBLOCK)
+        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx, _block_entry(ctx.geom))
         gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
         return (None, gsrc, None, None, None, *grads)
 
@@ -929,6 +1009,64 @@ class _Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
         return (None,) * 9 + (*g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
 
 
+class _Layer1Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
+    """layer1 -> layer2 -> layer3 -> layer4 -> FPN -> DB head as one node on the padded tap of the pooled stem output.  The backward is
+    _Layer2Layer3Layer4FPNHeadTrainFn's, continued: the FPN's backward also forms dC2, layer2's first block forms its input gradient (the
+    strided dgrad, 64 channels at C2's size), the two are added at one power-of-two scale (vtd_resblock_train_combine) and go into layer1's
+    second block, whose dx goes into the first; layer1.0 forms no input gradient (the stem is frozen).  Inputs: (pool,), FPN geom, the
+    head's BatchNorm mode / momentum / eps and buffers, the eight blocks' geometries, eps and running statistics (layer1.0 .. layer4.1),
+    then the learnable tensors: 6 + 6 of layer1's blocks, 3 x (9 + 6) of the others, the FPN's 10, the head's 20."""
+
+    CUTS = (0, 6, 12, 21, 27, 36, 42, 51, 57)
+
+    @classmethod
+    def _split(cls, params):
+        return tuple(params[a:b] for a, b in zip(cls.CUTS[:-1], cls.CUTS[1:])), params[57:67], params[67:]
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
+        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(params)
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        acts, bws, x = [], [], taps[0]
+        for i in range(8):                       # acts: layer1.0's output, C2, layer2.0's output, C3, layer3.0's, C4, layer4.0's, C5
+            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _block_entry(bgeoms[i]))
+            acts.append(x)
+            bws.append(ws)
+        ftaps = (acts[1], acts[3], acts[5], acts[7])
+        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, *acts, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, m1, c2, m2, c3, m3, c4, m4, c5, *params = ctx.saved_tensors
+        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(params)
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        fgrads, dtaps, scales = _fpn_backward_raw((c2, c3, c4, c5), ctx.geom, fpn_params, ctx.fws, dp2, dscale, 1 | 2 | 4 | 8)      # dC2 .. dC5
+        ins = (ctx.taps[0], m1, c2, m2, c3, m3, c4, m4)
+        outs = (m1, c2, m2, c3, m3, c4, m4, c5)
+        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
+                                                         dx, _block_entry(ctx.bgeoms[i]))
+        g41, d, ds = bwd(7, dtaps[3], scales[3], True)
+        g40, d, ds = bwd(6, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
+        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
+        g31, d, ds = bwd(5, d, ds, True)
+        g30, d, ds = bwd(4, d, ds, True)                      # layer3.0's share of dC3
+        d, ds = _combine_scaled(d, ds, dtaps[1], scales[1])   # + the FPN's
+        g21, d, ds = bwd(3, d, ds, True)
+        g20, d, ds = bwd(2, d, ds, True)                      # layer2.0's share of dC2: 64 channels at C2's size
+        d, ds = _combine_scaled(d, ds, dtaps[0], scales[0])   # + the FPN's
+        g11, d, ds = bwd(1, d, ds, True)
+        g10, _, _ = bwd(0, d, ds, False)
+        return (None,) * 9 + (*g10, *g11, *g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
+
+
 def pack_tap(feature):
     """[n,C,H,W] float32 / float16 CUDA tensor (C a multiple of 64) -> a padded tap (ring-padded NHWC fp16 [n,H+2,W+2,C]) on the device."""
     import ctypes as C
@@ -1076,6 +1214,10 @@ class _EngineOwner:
         self._version += 1
 
 
+# the modes that train residual stages, each one stage further down than the one before (ResNet-18 only)
+_STAGE_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2", "head+fpn+layer4+layer3+layer2+layer1")
+
+
 class DBNet(_EngineOwner, nn.Module):
     """DBNet detector network (text_detector.py:12-29), compute on the HIP engine.
 
@@ -1121,8 +1263,12 @@ class DBNet(_EngineOwner, nn.Module):
         "head+fpn+layer4+layer3+layer2" (ResNet-18 only): the usual fine-tuning recipe of a detection trunk -- the stem and layer1
         (backbone.0 .. backbone.4) stop requiring grad; backbone.5 .. backbone.7, fpn and head train.  The trunk engine is keyed on the frozen
         tensors only and gives C2 (its C3, C4 and C5 are ignored); layer2, layer3, layer4, the FPN and the head run on the HIP training
-        kernels as one autograd node.  dC3 is layer3.0's input gradient plus the FPN's dC3; layer2.0 forms no input gradient."""
-        if trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
+        kernels as one autograd node.  dC3 is layer3.0's input gradient plus the FPN's dC3; layer2.0 forms no input gradient.
+        "head+fpn+layer4+layer3+layer2+layer1" (ResNet-18 only): every residual stage -- only the stem (backbone.0, backbone.1) stops requiring
+        grad; backbone.4 .. backbone.7, fpn and head train (87 tensors).  The trunk engine is keyed on the frozen tensors only and gives the
+        pooled stem output (engine.DetectorEngine.forward_pool: the stem alone runs); layer1 .. layer4, the FPN and the head run on the HIP
+        training kernels as one autograd node.  dC2 is layer2.0's input gradient plus the FPN's dC2; layer1.0 forms no input gradient."""
+        if trainable in _STAGE_MODES:
             if self.backbone_name != "resnet18":
                 raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
                                  "Bottleneck training is not built")
@@ -1155,19 +1301,23 @@ class DBNet(_EngineOwner, nn.Module):
             for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
                 for p in m.parameters():
                     p.requires_grad_(True)
+        elif trainable == "head+fpn+layer4+layer3+layer2+layer1":
+            for i in range(4):
+                for p in self.backbone[i].parameters():
+                    p.requires_grad_(False)
+            for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
+                for p in m.parameters():
+                    p.requires_grad_(True)
         self._head_versions = None
         return self
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable in ("head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
+        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES:
             tensors += list(self.fpn.parameters())
-        if self.trainable in ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
-            tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
-        if self.trainable in ("head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
-            tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
-        if self.trainable == "head+fpn+layer4+layer3+layer2":
-            tensors += list(self.backbone[5].parameters()) + list(self.backbone[5].buffers())
+        if self.trainable in _STAGE_MODES:      # the stages the mode trains, from layer4 down
+            for i in range(_STAGE_MODES.index(self.trainable) + 1):
+                tensors += list(self.backbone[7 - i].parameters()) + list(self.backbone[7 - i].buffers())
         return tuple(t._version for t in tensors)
 
     def trunk_engine(self):
@@ -1182,6 +1332,8 @@ class DBNet(_EngineOwner, nn.Module):
                 frozen = {k: v for k, v in frozen.items() if not k.startswith(("6.", "7."))}
             elif self.trainable == "head+fpn+layer4+layer3+layer2":      # likewise: only the engine's C2 is read
                 frozen = {k: v for k, v in frozen.items() if not k.startswith(("5.", "6.", "7."))}
+            elif self.trainable == "head+fpn+layer4+layer3+layer2+layer1":      # likewise: only the pooled stem output is read (forward_pool)
+                frozen = {k: v for k, v in frozen.items() if not k.startswith(("4.", "5.", "6.", "7."))}
             version = tuple(t._version for t in frozen.values())
             te = self.__dict__.get("_trunk_engine")
             if te is None or self.__dict__.get("_trunk_version") != version:
@@ -1224,8 +1376,10 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn", "head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2"):
+        if self.trainable in ("head", "head+fpn") + _STAGE_MODES:
             if self.training:
+                if self.trainable == "head+fpn+layer4+layer3+layer2+layer1":
+                    return self._forward_train_head_fpn_layer4_layer3_layer2_layer1(x)
                 if self.trainable == "head+fpn+layer4+layer3+layer2":
                     return self._forward_train_head_fpn_layer4_layer3_layer2(x)
                 if self.trainable == "head+fpn+layer4+layer3":
@@ -1308,6 +1462,22 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)   # C3, C4 and C5 of the engine come from the weights it was built with: ignored
         out = self.fpn.forward_padded(taps[:1], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+
+    def _forward_train_head_fpn_layer4_layer3_layer2_layer1(self, x):
+        frozen = [n for i in range(4) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4+layer3+layer2+layer1'): {frozen[0]} requires grad, but backward below layer1 is not "
+                               "implemented; only layer1 .. layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 and "
+                               "backbone.1)")
+        for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        pool = self.trunk_engine().forward_pool(x)   # the stem alone runs: the engine's stages come from the weights it was built with
+        out = self.fpn.forward_padded([pool], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5],
+                                      layer1=self.backbone[4])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
