@@ -331,6 +331,38 @@ int vtd_block64_train_backward(const void* x_dev, int n, int h_in, int w_in, int
                                float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- ResNet stem training with frozen-statistics BatchNorm (csrc/stem_train.hip): pool = maxpool3x3/s2/p1(relu(bn(conv7x7/s2/p3(x)))) on an
+ * image x [n,3,height,width]; height and width are the image's, even and at least 2 (the product's 640 is not built in).  hc x wc = height / 2
+ * x width / 2 is the conv map, hp x wp = ceil(hc / 2) x ceil(wc / 2) the pooled map.  The running statistics normalise and are never written;
+ * w, gamma and beta learn.  No gradient of the image is formed.
+ * vtd_stem_train_pack_input: x_dev NCHW float32 (dtype 0) or fp16 (dtype 1) -> tap_dev, the stem's input layout [n][height+6][width+6][4]
+ * fp16 (ring 3, a zero fourth channel, a zero ring).
+ * vtd_stem_train_workspace_bytes: mode 0 = the forward's workspace (the folded weights and bias: it does not depend on the shape; kept for
+ * the backward), mode 1 = the backward's scratch.
+ * vtd_stem_train_forward: one launch behind the fold (half(w gamma rstd), bias = beta - mean gamma rstd, on the device, every call): conv +
+ * bias + ReLU as fp16 in LDS, pooled from there.  pool_tap_dev receives the padded tap [n][hp+2][wp+2][64] fp16 with a zero ring (what
+ * vtd_block64_train_forward reads), idx_dev one byte per pooled element [n][hp][wp][64]: the window position 3 ky + kx of the first maximum
+ * in scan order (ky, then kx), the element torch's CPU max_pool2d backward routes to; only in-image positions win.  Where the pooled value
+ * is 0 the byte is unspecified.  The conv map is not written.
+ * vtd_stem_train_backward: dpool_dev is NHWC float32 [n][hp][wp][64] times dscale_dev[0] (a power of two; dscale_dev = {scale, 1 / scale}):
+ * what vtd_block64_train_backward leaves in dx_dev / dxscale_dev.  m = dpool (pool > 0); s = the channel sums of m in fp64 (at most 256
+ * workgroups of consecutive pooled pixels, each four row quarters added as (q0 + q1) + (q2 + q3), the partials in workgroup order); dZ
+ * [n hc wc][64] fp16 is gathered: a conv pixel takes m, times a power of two chosen from max |m| with a factor 4 of headroom, of each of its
+ * 1, 2 or 4 windows whose idx names it.  G[c][q] = sum dZ[row][c] X[row][q] on v_mfma_f32_16x16x32_f16 with q = 32 ky + 4 kx + ci (224
+ * columns, 147 kept), rows cut into min(512, ceil(rows / 1024)) slabs, summed in slab order in fp64.  grads->w = gamma rstd G, grads->beta = s,
+ * grads->gamma = rstd (sum_k w G - mean s): nothing divides by gamma (grads->mean / var are ignored).  Gradients are written, not accumulated.
+ * No atomics, shape-only grids: bitwise repeatable.  Errors: -3301 (argument / unsupported geometry), -3302 (alignment), before any launch. */
+typedef struct vtd_stem_params {
+    float *w, *gamma, *beta, *mean, *var;
+} vtd_stem_params;
+int vtd_stem_train_pack_input(const void* x_dev, int dtype, int n, int height, int width, void* tap_dev, vtd_stream stream);
+int64_t vtd_stem_train_workspace_bytes(int n, int height, int width, int mode);
+int vtd_stem_train_forward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, float eps, void* workspace_dev,
+                           void* pool_tap_dev, void* idx_dev, vtd_stream stream);
+int vtd_stem_train_backward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, float eps, const void* workspace_dev,
+                            const void* pool_tap_dev, const void* idx_dev, const float* dpool_dev, const float* dscale_dev, const vtd_stem_params* grads,
+                            void* scratch_dev, vtd_stream stream);
+
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */
 int vtd_recognizer_create(int vocab_size, int max_crops, vtd_recognizer** out);

@@ -87,6 +87,11 @@ int vtd_launch_block64_backward(const void* x, int n, int hin, int win, int cin,
                                 const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
                                 float* dx, float* dxscale, hipStream_t s);
 int vtd_launch_resblock_combine(float* a, const float* asc, const float* b, const float* bsc, int64_t numel, float* osc, hipStream_t s);
+int vtd_launch_stem_pack_input(const void* x, int dtype, int n, int H, int W, void* tap, hipStream_t s);
+int64_t vtd_stem_ws_bytes(int n, int H, int W, int mode);
+int vtd_launch_stem_forward(const void* x, int n, int H, int W, const vtd_stem_params* P, float eps, void* ws, void* pool, void* idx, hipStream_t s);
+int vtd_launch_stem_backward(const void* x, int n, int H, int W, const vtd_stem_params* P, float eps, const void* ws, const void* pool, const void* idx,
+                             const float* dpool, const float* dscale, const vtd_stem_params* Gp, void* scratch, hipStream_t s);
 int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
                                 void* y, hipStream_t s);
 int vtd_launch_resblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
@@ -1448,6 +1453,8 @@ const char* vtd_strerror(int code) {
         case -3102: return "ResNet block training: misaligned buffer";
         case -3201: return "64-wide block training: invalid argument or unsupported geometry (built: 64 -> 64 stride 1, ResNet-18's layer1)";
         case -3202: return "64-wide block training: misaligned buffer";
+        case -3301: return "stem training: invalid argument or unsupported geometry (built: n >= 1, even image height and width >= 2)";
+        case -3302: return "stem training: misaligned buffer";
         default: break;
     }
     if (code <= -1000) {
@@ -1585,6 +1592,24 @@ int vtd_block64_train_backward(const void* x_dev, int n, int h_in, int w_in, int
                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
     return vtd_launch_block64_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
                                        scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+int vtd_stem_train_pack_input(const void* x_dev, int dtype, int n, int height, int width, void* tap_dev, vtd_stream stream) {
+    return vtd_launch_stem_pack_input(x_dev, dtype, n, height, width, tap_dev, (hipStream_t)stream);
+}
+
+int64_t vtd_stem_train_workspace_bytes(int n, int height, int width, int mode) { return vtd_stem_ws_bytes(n, height, width, mode); }
+
+int vtd_stem_train_forward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, float eps, void* workspace_dev,
+                           void* pool_tap_dev, void* idx_dev, vtd_stream stream) {
+    return vtd_launch_stem_forward(x_tap_dev, n, height, width, params, eps, workspace_dev, pool_tap_dev, idx_dev, (hipStream_t)stream);
+}
+
+int vtd_stem_train_backward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, float eps, const void* workspace_dev,
+                            const void* pool_tap_dev, const void* idx_dev, const float* dpool_dev, const float* dscale_dev, const vtd_stem_params* grads,
+                            void* scratch_dev, vtd_stream stream) {
+    return vtd_launch_stem_backward(x_tap_dev, n, height, width, params, eps, workspace_dev, pool_tap_dev, idx_dev, dpool_dev, dscale_dev, grads,
+                                    scratch_dev, (hipStream_t)stream);
 }
 
 int64_t vtd_fpn_train_input_workspace_bytes(int n, int h5, int w5, int c5_channels) { return vtd_fpn_input_ws_bytes(n, h5, w5, c5_channels); }

@@ -57,6 +57,11 @@ class BasicBlockParams(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in BLOCK_FIELDS]
 
 
+class StemParams(C.Structure):
+    """vtd_stem_params of include/vtd.h: device pointers to the stem's fp32 tensors (conv weight, BatchNorm gamma, beta, running mean, var)"""
+    _fields_ = [(k, C.c_void_p) for k in ("w", "gamma", "beta", "mean", "var")]
+
+
 FpnTaps = C.c_void_p * 4   # padded taps C2, C3, C4, C5
 
 
@@ -150,6 +155,12 @@ SIGNATURES = {
     "vtd_block64_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.POINTER(BasicBlockParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_stem_train_pack_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_stem_train_workspace_bytes": (C.c_int64, [C.c_int] * 4),
+    "vtd_stem_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "vtd_stem_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(StemParams), C.c_void_p, C.c_void_p]),
     "vtd_detector_forward_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_fpn_train_input_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtd_fpn_train_backward_input": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_int, C.POINTER(FpnTaps),

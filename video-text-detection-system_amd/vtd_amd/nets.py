@@ -224,8 +224,13 @@ class FeaturePyramidNetwork(nn.Module):
         srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None):
-        """With `layer1` too (ResNet-18's first stage, two 64 -> 64 BasicBlocks): layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head as ONE
+    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None):
+        """With `stem` too (the pair (conv 7x7/s2, BatchNorm) of ResNet's stem): stem -> layer1 -> .. -> layer4 -> FPN -> head as ONE autograd
+        node on the image tap [image] (nets.pack_image: [n,H+6,W+6,4] fp16), differentiable w.r.t. the stem's three learnable tensors and the
+        eighty-seven below.  layer1.0 forms its input gradient and that gradient is the stem's dpool; the other eighty-seven gradients are the
+        bits of the node without `stem` on the pooled tap the stem produced.  No gradient of the image is formed.
+
+        With `layer1` too (ResNet-18's first stage, two 64 -> 64 BasicBlocks): layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head as ONE
         autograd node on the padded tap [pool] (the pooled stem output, e.g. DetectorEngine.forward_pool; C2..C5 are computed here),
         differentiable w.r.t. layer1's twelve learnable tensors, the forty-five of the three stages above, the FPN's ten and the head's
         twenty.  dC2 is layer2.0's input gradient (the strided dgrad) plus the FPN's dC2; layer1.0 forms no input gradient.
@@ -248,6 +253,8 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if stem is not None:
+            return self._forward_padded_stem(taps, head, layer4, layer3, layer2, layer1, stem)
         if layer1 is not None:
             return self._forward_padded_layer1(taps, head, layer4, layer3, layer2, layer1)
         if layer2 is not None:
@@ -391,14 +398,179 @@ class FeaturePyramidNetwork(nn.Module):
         return {"probability": prob, "threshold": thresh}
 
 
-def _layer1_operands(layer1, pool_tap):
+    def _forward_padded_stem(self, taps, head, layer4, layer3, layer2, layer1, stem):
+        if head is None or layer4 is None or layer3 is None or layer2 is None or layer1 is None:
+            raise ValueError("forward_padded(taps, stem=...) is the training node: it needs layer1, layer2, layer3, layer4 and the DBHead too")
+        if not isinstance(stem, (list, tuple)) or len(stem) != 2:
+            raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
+        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
+            raise ValueError("padded taps must be the tensor [image]")
+        image = taps[0].detach() if torch.is_tensor(taps[0]) else taps[0]
+        sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], image)
+        dev = image.device
+        n, hp, wp = sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2
+        meta = lambda n, h, w, c: torch.empty((n, h + 2, w + 2, c), dtype=torch.float16, device="meta")  # noqa: E731
+        _, g1, eps1, learn1, stats1 = _layer1_operands(layer1, meta(n, hp, wp, 64), dev)
+        _, g2, eps2, learn2, stats2 = _layer2_operands(layer2, meta(n, hp, wp, 64), dev)
+        h3, w3 = g2[1][1], g2[1][2]
+        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, meta(n, h3, w3, 128), dev)
+        h4, w4 = g3[1][1], g3[1][2]
+        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, meta(n, h4, w4, 256), dev)
+        if eps1 != eps2 or eps2 != eps3 or eps3 != eps4:
+            raise RuntimeError("layer1 / layer2 / layer3 / layer4 training needs one BatchNorm eps")
+        h5, w5 = g4[1][1], g4[1][2]
+        geom = self._geometry([(n, 64, hp, wp), (n, 128, h3, w3), (n, 256, h4, w4), (n, 512, h5, w5)])
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        prob, thresh, _ = _StemLayer1Layer2Layer3Layer4FPNHeadTrainFn.apply((image,), geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers),
+                                                                            sgeom, seps, tuple(sstats), tuple(g1 + g2 + g3 + g4), eps1,
+                                                                            tuple(stats1 + stats2 + stats3 + stats4), *slearn, *learn1[0], *learn1[1],
+                                                                            *learn2[0], *learn2[1], *learn3[0], *learn3[1], *learn4[0], *learn4[1],
+                                                                            *params, *hparams)
+        if head.training:
+            with torch.no_grad():
+                for bn in bns:
+                    bn.num_batches_tracked.add_(1)
+        return {"probability": prob, "threshold": thresh}
+
+
+def _stem_operands(conv, bn, image_tap):
+    """ResNet's stem (conv 7x7/s2/p3 3 -> 64 without bias, BatchNorm(64)) on an image tap [n,H+6,W+6,4] fp16: ((n, H, W), eps, the learnable
+    tensors [conv.weight, bn.weight, bn.bias], the running statistics (mean, var)), validated."""
+    if (not isinstance(conv, nn.Conv2d) or not isinstance(bn, nn.BatchNorm2d) or conv.bias is not None or tuple(conv.weight.shape) != (64, 3, 7, 7)
+            or conv.stride != (2, 2) or conv.padding != (3, 3) or conv.dilation != (1, 1) or conv.groups != 1 or bn.num_features != 64
+            or not bn.affine or not bn.track_running_stats):
+        raise RuntimeError("stem training is built for ResNet's stem: Conv2d(3, 64, 7, stride 2, padding 3, no bias) and BatchNorm2d(64) with "
+                           "running statistics")
+    t = image_tap
+    if (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[3] != 4 or t.shape[0] < 1
+            or t.shape[1] < 8 or t.shape[2] < 8 or t.shape[1] % 2 or t.shape[2] % 2):
+        raise ValueError("the image tap must be a contiguous float16 CUDA tensor [n,H+6,W+6,4] with even H and W (nets.pack_image)")
+    learn, stats = [conv.weight, bn.weight, bn.bias], (bn.running_mean, bn.running_var)
+    for p in learn + list(stats):
+        if not p.is_cuda or p.device != t.device or p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError("stem parameters and buffers must be contiguous float32 CUDA tensors on the input's device (call .cuda() on the model)")
+    return (int(t.shape[0]), int(t.shape[1]) - 6, int(t.shape[2]) - 6), float(bn.eps), learn, stats
+
+
+def _stem_struct(learn, stats=None):
+    import ctypes as C
+    from . import _native
+    st = _native.StemParams()
+    for field, t in zip(("w", "gamma", "beta"), learn):
+        setattr(st, field, C.c_void_p(t.data_ptr()))
+    if stats is not None:
+        st.mean, st.var = C.c_void_p(stats[0].data_ptr()), C.c_void_p(stats[1].data_ptr())
+    return st
+
+
+def _stem_forward_raw(tap, geom, eps, learn, stats):
+    """vtd_stem_train_forward on an image tap: (the pooled padded tap [n,hp+2,wp+2,64] fp16, idx [n,hp,wp,64] uint8, workspace)."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, H, W = geom
+    hp, wp = (H // 2 + 1) // 2, (W // 2 + 1) // 2
+    nbytes = int(lib.vtd_stem_train_workspace_bytes(n, H, W, 0))
+    _native.check(min(nbytes, 0), "vtd_stem_train_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    pool = torch.empty((n, hp + 2, wp + 2, 64), dtype=torch.float16, device=tap.device)
+    idx = torch.empty((n, hp, wp, 64), dtype=torch.uint8, device=tap.device)
+    st = _stem_struct(learn, stats)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _native.check(lib.vtd_stem_train_forward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_stem_train_forward")
+    return pool, idx, ws
+
+
+def _stem_backward_raw(tap, geom, eps, learn, stats, ws, pool, idx, dpool, dscale):
+    """vtd_stem_train_backward on dpool as NHWC fp32 [n,hp,wp,64] times dscale[0]: the gradients of [conv.weight, bn.weight, bn.bias]."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, H, W = geom
+    grads = [torch.empty_like(p) for p in learn]
+    nbytes = int(lib.vtd_stem_train_workspace_bytes(n, H, W, 1))
+    _native.check(min(nbytes, 0), "vtd_stem_train_workspace_bytes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    st, gst = _stem_struct(learn, stats), _stem_struct(grads)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _native.check(lib.vtd_stem_train_backward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx), ptr(dpool), ptr(dscale), C.byref(gst),
+                                              ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_stem_train_backward")
+    return grads
+
+
+class _StemTrainFn(torch.autograd.Function):
+    """The stem on the HIP training kernels (csrc/stem_train.hip): image tap in, the pooled map [n,64,hp,wp] fp32 out, differentiable w.r.t.
+    the convolution's weight and the BatchNorm's gamma and beta.  No gradient of the image is formed."""
+
+    @staticmethod
+    def forward(ctx, tap, geom, eps, stats, *learn):
+        pool, idx, ws = _stem_forward_raw(tap, geom, eps, learn, stats)
+        ctx.save_for_backward(tap, pool, idx, *stats, *learn)
+        ctx.ws, ctx.geom, ctx.eps = ws, geom, eps
+        return pool[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        tap, pool, idx, mean, var, *learn = ctx.saved_tensors
+        dpool = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        dscale = torch.ones(2, dtype=torch.float32, device=dpool.device)
+        grads = _stem_backward_raw(tap, ctx.geom, ctx.eps, learn, (mean, var), ctx.ws, pool, idx, dpool, dscale)
+        return (None, None, None, None, *grads)
+
+
+def pack_image(x):
+    """[n,3,H,W] float32 / float16 CUDA tensor (H and W even) -> the stem's input layout on the device: ring-padded NHWC fp16 [n,H+6,W+6,4]
+    with ring 3, a zero fourth channel and a zero ring."""
+    import ctypes as C
+    from . import _native
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("the stem's input must be a [n,3,H,W] tensor")
+    if not x.is_cuda:
+        raise ValueError("the stem runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    lib = _native.require()
+    x = x.detach()
+    if x.dtype not in (torch.float32, torch.float16):
+        x = x.float()
+    x = x.contiguous()
+    n, _, H, W = x.shape
+    if n < 1 or H < 2 or W < 2 or H % 2 or W % 2:
+        raise RuntimeError(f"the stem's HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+    out = torch.empty((n, H + 6, W + 6, 4), dtype=torch.float16, device=x.device)
+    _native.check(lib.vtd_stem_train_pack_input(C.c_void_p(x.data_ptr()), 0 if x.dtype == torch.float32 else 1, n, H, W, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_stem_train_pack_input")
+    return out
+
+
+def stem_train(conv, bn, x):
+    """ResNet's stem -- max-pool 3x3/s2/p1 of relu(bn(conv 7x7/s2/p3(x))) -- on the HIP training kernels (csrc/stem_train.hip) as a
+    differentiable function of the stem's learnable tensors, the counterpart of ``basic_block_train``: ``x`` is a CUDA ``[n,3,H,W]`` tensor
+    (fp32 or fp16, H and W even), the result ``[n,64,ceil(H/4),ceil(W/4)]`` fp32 that requires grad.  Frozen-statistics BatchNorm: the running
+    statistics normalise and are never written.  The backward fills ``conv.weight.grad``, ``bn.weight.grad`` and ``bn.bias.grad``; the
+    gradient for ``x`` is None."""
+    tap = pack_image(x)
+    geom, eps, learn, stats = _stem_operands(conv, bn, tap)
+    return _StemTrainFn.apply(tap, geom, eps, tuple(stats), *learn)
+
+
+def forward_stem_padded(conv, bn, image_tap):
+    """ResNet's stem on an image tap (nets.pack_image) with the HIP training kernels, no gradient: the pooled padded tap [n,hp+2,wp+2,64]
+    fp16 with a zero ring, what forward_layer1_padded reads."""
+    geom, eps, learn, stats = _stem_operands(conv, bn, image_tap)
+    with torch.no_grad():
+        return _stem_forward_raw(image_tap.detach(), geom, eps, [t.detach() for t in learn], stats)[0]
+
+
+def _layer1_operands(layer1, pool_tap, device=None):
     """ResNet-18's layer1 on a padded tap of the pooled stem output: (the two blocks, their geometries, eps, their learnable tensors, their
-    running statistics)."""
+    running statistics).  Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
     blocks = list(layer1)
     if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
         raise RuntimeError("layer1 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
     n, h, w = int(pool_tap.shape[0]), int(pool_tap.shape[1]) - 2, int(pool_tap.shape[2]) - 2
-    ops = [b._train_operands(pool_tap.device, general=True, narrow=True) for b in blocks]
+    ops = [b._train_operands(pool_tap.device if device is None else device, general=True, narrow=True) for b in blocks]
     if [o[0] for o in ops] != [(64, 64, 1), (64, 64, 1)] or pool_tap.shape[3] != 64:
         raise RuntimeError("layer1 training is built for ResNet-18's layer1 (64 -> 64 stride 1, twice)")
     if ops[0][1] != ops[1][1]:
@@ -1067,6 +1239,64 @@ class _Layer1Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
         return (None,) * 9 + (*g10, *g11, *g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
 
 
+class _StemLayer1Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
+    """stem -> layer1 -> layer2 -> layer3 -> layer4 -> FPN -> DB head as one node on the image tap.  The forward is the stem's launch
+    (csrc/stem_train.hip), then _Layer1Layer2Layer3Layer4FPNHeadTrainFn's on the pooled tap it wrote; the backward is that node's,
+    continued: layer1.0 forms its input gradient too, and that gradient (NHWC fp32 with its power-of-two scale) is the stem's dpool.  The
+    parameter gradients of a block do not depend on whether its dx is formed, so the eighty-seven gradients below the stem are the bits of
+    the node without it.  Inputs: (image tap,), FPN geom, the head's BatchNorm mode / momentum / eps and buffers, the stem's geometry, eps
+    and running statistics, the eight blocks' geometries, eps and running statistics, then the learnable tensors: the stem's 3, 6 + 6 of
+    layer1's blocks, 3 x (9 + 6) of the others, the FPN's 10, the head's 20."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, sgeom, seps, sstats, bgeoms, beps, bstats, *params):
+        slearn, rest = params[:3], params[3:]
+        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(rest)
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        pool, idx, sws = _stem_forward_raw(taps[0], sgeom, seps, slearn, sstats)
+        acts, bws, x = [], [], pool
+        for i in range(8):                       # acts: layer1.0's output, C2, layer2.0's output, C3, layer3.0's, C4, layer4.0's, C5
+            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _block_entry(bgeoms[i]))
+            acts.append(x)
+            bws.append(ws)
+        ftaps = (acts[1], acts[3], acts[5], acts[7])
+        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, pool, idx, *acts, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.sgeom, ctx.seps, ctx.sstats, ctx.sws = sgeom, seps, sstats, sws
+        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, pool, idx, m1, c2, m2, c3, m3, c4, m4, c5, *params = ctx.saved_tensors
+        slearn, rest = params[:3], params[3:]
+        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(rest)
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        fgrads, dtaps, scales = _fpn_backward_raw((c2, c3, c4, c5), ctx.geom, fpn_params, ctx.fws, dp2, dscale, 1 | 2 | 4 | 8)      # dC2 .. dC5
+        ins = (pool, m1, c2, m2, c3, m3, c4, m4)
+        outs = (m1, c2, m2, c3, m3, c4, m4, c5)
+        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
+                                                         dx, _block_entry(ctx.bgeoms[i]))
+        g41, d, ds = bwd(7, dtaps[3], scales[3], True)
+        g40, d, ds = bwd(6, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
+        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
+        g31, d, ds = bwd(5, d, ds, True)
+        g30, d, ds = bwd(4, d, ds, True)                      # layer3.0's share of dC3
+        d, ds = _combine_scaled(d, ds, dtaps[1], scales[1])   # + the FPN's
+        g21, d, ds = bwd(3, d, ds, True)
+        g20, d, ds = bwd(2, d, ds, True)                      # layer2.0's share of dC2: 64 channels at C2's size
+        d, ds = _combine_scaled(d, ds, dtaps[0], scales[0])   # + the FPN's
+        g11, d, ds = bwd(1, d, ds, True)
+        g10, d, ds = bwd(0, d, ds, True)                      # layer1.0's input gradient: the stem's dpool
+        gs = _stem_backward_raw(ctx.taps[0], ctx.sgeom, ctx.seps, slearn, ctx.sstats, ctx.sws, pool, idx, d, ds)
+        return (None,) * 12 + (*gs, *g10, *g11, *g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
+
+
 def pack_tap(feature):
     """[n,C,H,W] float32 / float16 CUDA tensor (C a multiple of 64) -> a padded tap (ring-padded NHWC fp16 [n,H+2,W+2,C]) on the device."""
     import ctypes as C
@@ -1216,6 +1446,8 @@ class _EngineOwner:
 
 # the modes that train residual stages, each one stage further down than the one before (ResNet-18 only)
 _STAGE_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2", "head+fpn+layer4+layer3+layer2+layer1")
+# the whole detector: the four stages and the stem (ResNet-18 only); nothing is frozen and the train-mode forward needs no trunk engine
+_BACKBONE_MODE = "head+fpn+backbone"
 
 
 class DBNet(_EngineOwner, nn.Module):
@@ -1267,8 +1499,13 @@ class DBNet(_EngineOwner, nn.Module):
         "head+fpn+layer4+layer3+layer2+layer1" (ResNet-18 only): every residual stage -- only the stem (backbone.0, backbone.1) stops requiring
         grad; backbone.4 .. backbone.7, fpn and head train (87 tensors).  The trunk engine is keyed on the frozen tensors only and gives the
         pooled stem output (engine.DetectorEngine.forward_pool: the stem alone runs); layer1 .. layer4, the FPN and the head run on the HIP
-        training kernels as one autograd node.  dC2 is layer2.0's input gradient plus the FPN's dC2; layer1.0 forms no input gradient."""
-        if trainable in _STAGE_MODES:
+        training kernels as one autograd node.  dC2 is layer2.0's input gradient plus the FPN's dC2; layer1.0 forms no input gradient.
+        "head+fpn+backbone" (ResNet-18 only): the whole detector, as the reference's trainer hands every parameter to its optimizer -- nothing
+        is frozen, 90 tensors train.  A forward in train mode packs the image (nets.pack_image) and runs the stem (csrc/stem_train.hip),
+        layer1 .. layer4, the FPN and the head on the HIP training kernels as one autograd node; no trunk engine is built or read.  layer1.0
+        forms its input gradient, which is the stem's upstream gradient; the stem's BatchNorm, like every trunk BatchNorm, normalises with
+        its running statistics, which are never written.  No gradient of the image is formed."""
+        if trainable in _STAGE_MODES or trainable == _BACKBONE_MODE:
             if self.backbone_name != "resnet18":
                 raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
                                  "Bottleneck training is not built")
@@ -1308,13 +1545,19 @@ class DBNet(_EngineOwner, nn.Module):
             for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
                 for p in m.parameters():
                     p.requires_grad_(True)
+        elif trainable == _BACKBONE_MODE:
+            for p in self.parameters():
+                p.requires_grad_(True)
         self._head_versions = None
         return self
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES:
+        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable == _BACKBONE_MODE:
             tensors += list(self.fpn.parameters())
+        if self.trainable == _BACKBONE_MODE:      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
+            for i in (7, 6, 5, 4, 0, 1):
+                tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
         if self.trainable in _STAGE_MODES:      # the stages the mode trains, from layer4 down
             for i in range(_STAGE_MODES.index(self.trainable) + 1):
                 tensors += list(self.backbone[7 - i].parameters()) + list(self.backbone[7 - i].buffers())
@@ -1376,8 +1619,10 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn") + _STAGE_MODES:
+        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE) + _STAGE_MODES:
             if self.training:
+                if self.trainable == _BACKBONE_MODE:
+                    return self._forward_train_backbone(x)
                 if self.trainable == "head+fpn+layer4+layer3+layer2+layer1":
                     return self._forward_train_head_fpn_layer4_layer3_layer2_layer1(x)
                 if self.trainable == "head+fpn+layer4+layer3+layer2":
@@ -1478,6 +1723,24 @@ class DBNet(_EngineOwner, nn.Module):
         pool = self.trunk_engine().forward_pool(x)   # the stem alone runs: the engine's stages come from the weights it was built with
         out = self.fpn.forward_padded([pool], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5],
                                       layer1=self.backbone[4])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+
+    def _forward_train_backbone(self, x):
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("DBNet(trainable='head+fpn+backbone'): the train-mode forward takes a float [n,3,H,W] tensor")
+        frozen = [n for n, p in self.named_parameters() if not p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable='head+fpn+backbone'): {frozen[0]} does not require grad, but this mode trains every tensor "
+                               "(pick a narrower mode with set_trainable to freeze a part)")
+        for m in (self.backbone, self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        dev = next(self.head.parameters()).device
+        image = pack_image(x if x.is_cuda else x.to(dev))   # no trunk engine: the stem runs on the training kernels too
+        out = self.fpn.forward_padded([image], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5],
+                                      layer1=self.backbone[4], stem=(self.backbone[0], self.backbone[1]))
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
