@@ -331,6 +331,41 @@ int vtd_block64_train_backward(const void* x_dev, int n, int h_in, int w_in, int
                                float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- ResNet BasicBlock training with batch-statistics BatchNorm (csrc/resblock_bn_train.hip): the same block as torch's train() mode
+ * computes it.  Tensors, layouts, the vtd_basicblock_params struct, the power-of-two gradient scales and the "written, not accumulated" rule
+ * are those of vtd_basicblock_train_*.  Two geometries are built, ResNet-18's layer4: (cin 256, width 512, stride 2, even h_in and w_in, with
+ * downsample) and (cin 512, width 512, stride 1, identity: ds_* ignored); every other geometry is refused with -3401.
+ * vtd_resblock_bn_train_workspace_bytes: mode 0 = the forward's workspace (kept for the backward), mode 1 = the backward's scratch; each
+ * serves either value of `training`.
+ * training = 0: the running statistics normalise and nothing is written (stats_dev included).  The call is handed to
+ * vtd_basicblock_train_forward / _backward: y, the parameter gradients and dx are their bits.
+ * training = 1, forward, per convolution + BatchNorm pair (conv1 / bn1, conv2 / bn2, the downsample): the raw weights are rounded to fp16 on
+ * the device in every call (no fold); the convolution writes z, float32 [n h w][width], kept in the workspace.  Per-channel statistics are
+ * (count, mean, M2) partials in fp64 -- min(256, ceil(n h w / 256)) workgroups of ceil(n h w / workgroups) consecutive rows, each summing the
+ * first ceil(r / 2) of its r rows in row order, then the rest, lower + upper -- combined in workgroup order (Chan) into the batch mean mu and
+ * the biased variance sigma^2.  The running values in `params` are updated in place: mean <- (1 - momentum) mean + momentum mu, var <-
+ * (1 - momentum) var + momentum sigma^2 M / (M - 1), M = n h w.  stats_dev (optional) receives float32 [3][2][width]: mu and sigma^2 of bn1,
+ * bn2 and the downsample's BatchNorm (the third row is untouched without a downsample).  a1 = relu(((z1 - mu) rstd) gamma + beta), the
+ * downsample's normalised output (no ReLU) and y = relu(((z2 - mu) rstd) gamma + beta + id) are stored as ring-padded fp16 taps.  The caller
+ * advances num_batches_tracked.
+ * training = 1, backward: g2 = dy (y > 0).  Per pair, with g the gradient at the BatchNorm output (g2 for bn2 and the downsample, conv2^T(dz2)
+ * (a1 > 0) for bn1) and xh = (z - mu) rstd recomputed from the saved z: s1 = sum g and s2 = sum g xh in fp64, rows and workgroups in the
+ * forward's order; dbeta = s1, dgamma = s2; dz = gamma rstd (g - s1 / M - xh s2 / M) in float32, then times a power of two taken from the bound
+ * max_c |gamma rstd| (max |g| + |s1| / M + max |xh| |s2| / M) and rounded to fp16; dW = dz^T im2col(input) (MFMA, min(8, ceil(M / 4096)) slabs
+ * summed in order in fp64): dz carries gamma rstd, no factor follows.  Exact for gamma = 0 and gamma < 0: nothing divides by gamma or sigma.
+ * dx_dev (optional, the stride-1 block only): conv1^T(dz1) + g2 as NHWC float32 [n][h][w][512] times dxscale_dev[0].  LIMITATION: a non-NULL
+ * dx_dev on the stride-2 block is refused with -3403.  The statistics are not fused into the convolution's epilogue: z makes one round trip
+ * through HBM per pair and direction.
+ * No atomics, shape-only grids: bitwise repeatable; a dy scaled by a power of two gives the same gradient bits, scaled.
+ * Errors, before any launch: -3401 (argument / unsupported geometry / training = 1 with n h w < 2 / momentum outside [0, 1]), -3402
+ * (alignment), -3403 (input gradient of the stride-2 block). */
+int64_t vtd_resblock_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_resblock_bn_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                  int training, float momentum, float eps, void* workspace_dev, void* y_dev, float* stats_dev, vtd_stream stream);
+int vtd_resblock_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                   int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                   const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
 /* ---- ResNet stem training with frozen-statistics BatchNorm (csrc/stem_train.hip): pool = maxpool3x3/s2/p1(relu(bn(conv7x7/s2/p3(x)))) on an
  * image x [n,3,height,width]; height and width are the image's, even and at least 2 (the product's 640 is not built in).  hc x wc = height / 2
  * x width / 2 is the conv map, hp x wp = ceil(hc / 2) x ceil(wc / 2) the pooled map.  The running statistics normalise and are never written;

@@ -97,8 +97,31 @@ _BLOCK_GEOMETRIES = ((64, 128, 2, True), (128, 128, 1, False), (128, 256, 2, Tru
 _BLOCK64_GEOMETRY = (64, 64, 1, False)   # layer1's, behind entries of its own
 
 
-def basic_block_train(block, x):
-    """One BasicBlock on the HIP training kernels (csrc/resblock_train.hip) as a differentiable function of a CUDA NCHW tensor (fp32 or
+# the geometries with train-mode (batch-statistics) BatchNorm built (csrc/resblock_bn_train.hip): ResNet-18's layer4
+_BN_TRAIN_GEOMETRIES = ((256, 512, 2, True), (512, 512, 1, False))
+_BN_TRAIN_BUILT = ("train-mode (batch-statistics) BatchNorm is built for the BasicBlocks of ResNet-18's layer4 only (256 -> 512 stride 2 with "
+                   "downsample, 512 -> 512 stride 1); layer3, layer2, layer1, the stem and Bottleneck blocks keep frozen statistics")
+
+
+def _block_bn_check(block):
+    """The BatchNorms of a BasicBlock that vtd_resblock_bn_train_* can run in train mode (bn1, bn2, the downsample's), validated."""
+    cin, width, ds = block.conv1.in_channels, block.conv1.out_channels, hasattr(block, "downsample")
+    if (cin, width, block.stride, ds) not in _BN_TRAIN_GEOMETRIES:
+        raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {block.stride}): " + _BN_TRAIN_BUILT)
+    bns = [block.bn1, block.bn2] + ([block.downsample[1]] if ds else [])
+    if any(bn.momentum is None or bn.momentum != bns[0].momentum for bn in bns):
+        raise ValueError("the HIP batch-statistics BasicBlock kernels need one fixed momentum on all of the block's BatchNorms "
+                         "(momentum=None, the cumulative average, is not built)")
+    return bns
+
+
+def basic_block_train(block, x, batch_stats=False):
+    """With ``batch_stats=True`` (layer4's two geometries only, csrc/resblock_bn_train.hip) the block's BatchNorms behave as torch's
+    modules do: in ``block.training`` mode the statistics of the batch normalise, the running statistics are updated in place and
+    ``num_batches_tracked`` advances on each of the block's BatchNorms; in ``eval()`` mode the frozen path below runs, the same bits.  The
+    stride-2 block forms no input gradient on this path: an input that requires grad is refused.
+
+    One BasicBlock on the HIP training kernels (csrc/resblock_train.hip) as a differentiable function of a CUDA NCHW tensor (fp32 or
     fp16), for the seven blocks of ResNet-18's four stages: 64 -> 64 at stride 1 (layer1's, on the vtd_block64_train_* entries), and on the
     vtd_resblock_train_* entries 64 -> 128, 128 -> 256 and 256 -> 512 at stride 2 (with downsample, even extents), 128 -> 128, 256 -> 256
     and 512 -> 512 at stride 1.  Frozen-statistics BatchNorm, as ``block(x)``; returns ``[n,width,h,w]`` fp32, differentiable w.r.t. the
@@ -108,14 +131,37 @@ def basic_block_train(block, x):
         raise RuntimeError("basic_block_train is built for ResNet-18's BasicBlocks; Bottleneck training is not built")
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != block.conv1.in_channels:
         raise ValueError(f"BasicBlock input must be a [n,{block.conv1.in_channels},H,W] tensor")
+    bns = _block_bn_check(block) if batch_stats else None   # what is built, before anything about the device
     if not x.is_cuda:
         raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    if batch_stats:
+        return _basic_block_bn_train(block, x, bns)
     (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=True, narrow=True)
     n, _, hin, win = x.shape
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
         raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
     src = x if x.requires_grad and torch.is_grad_enabled() else None
     return _ResBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
+
+
+def _basic_block_bn_train(block, x, bns):
+    (cin, width, stride), eps, learn, stats = block._train_operands(x.device)
+    n, _, hin, win = x.shape
+    if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
+        raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+    if block.training and n * (hin // stride) * (win // stride) < 2:
+        raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got an output of {n} x {hin // stride} x {win // stride}")
+    if stride != 1 and x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("BasicBlock(stride 2, batch_stats=True): the input requires grad, but the input gradient of the stride-2 block is not "
+                           "built with batch-statistics BatchNorm; pass x.detach()")
+    src = x if x.requires_grad and torch.is_grad_enabled() else None
+    out = _BasicBlockBNTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), bool(block.training), float(bns[0].momentum),
+                                     eps, tuple(stats), *learn)
+    if block.training:
+        with torch.no_grad():
+            for bn in bns:
+                bn.num_batches_tracked.add_(1)
+    return out
 
 
 class Bottleneck(_Residual):
@@ -224,8 +270,13 @@ class FeaturePyramidNetwork(nn.Module):
         srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None):
-        """With `stem` too (the pair (conv 7x7/s2, BatchNorm) of ResNet's stem): stem -> layer1 -> .. -> layer4 -> FPN -> head as ONE autograd
+    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False):
+        """With `trunk_batch_stats=True` (the layer4 -> FPN -> head node only: passing it with `layer3` or a lower stage raises ValueError)
+        layer4 runs on the vtd_resblock_bn_train_* entries: while layer4 is in training mode its five BatchNorms normalise with the statistics
+        of the batch, their running statistics are updated in place and their num_batches_tracked advance; in eval() mode the frozen path
+        runs, the same bits as without the flag.
+
+        With `stem` too (the pair (conv 7x7/s2, BatchNorm) of ResNet's stem): stem -> layer1 -> .. -> layer4 -> FPN -> head as ONE autograd
         node on the image tap [image] (nets.pack_image: [n,H+6,W+6,4] fp16), differentiable w.r.t. the stem's three learnable tensors and the
         eighty-seven below.  layer1.0 forms its input gradient and that gradient is the stem's dpool; the other eighty-seven gradients are the
         bits of the node without `stem` on the pooled tap the stem produced.  No gradient of the image is formed.
@@ -253,6 +304,10 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
+        if trunk_batch_stats:
+            if layer4 is None or any(m is not None for m in (layer3, layer2, layer1, stem)):
+                raise ValueError("forward_padded(..., trunk_batch_stats=True) is the layer4 -> FPN -> head node: " + _BN_TRAIN_BUILT)
+            return self._forward_padded_layer4(taps, head, layer4, trunk_batch_stats=True)
         if stem is not None:
             return self._forward_padded_stem(taps, head, layer4, layer3, layer2, layer1, stem)
         if layer1 is not None:
@@ -283,7 +338,7 @@ class FeaturePyramidNetwork(nn.Module):
         return {"probability": prob, "threshold": thresh}
 
 
-    def _forward_padded_layer4(self, taps, head, layer4):
+    def _forward_padded_layer4(self, taps, head, layer4, trunk_batch_stats=False):
         if head is None:
             raise ValueError("forward_padded(taps, layer4=...) is the training node: it needs the DBHead too")
         if not isinstance(taps, (list, tuple)) or len(taps) < 3:
@@ -297,8 +352,22 @@ class FeaturePyramidNetwork(nn.Module):
         geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps] + [(n, 512, h5, w5)])
         params = self._live_checked(taps[0].device)
         bns, hparams, hbuffers = head._train_operands(taps[0].device)
-        prob, thresh, _ = _Layer4FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(bgeoms), beps,
-                                                      tuple(bstats), *blearn[0], *blearn[1], *params, *hparams)
+        if trunk_batch_stats:
+            bbns = [bn for b in blocks for bn in _block_bn_check(b)]
+            if blocks[0].training != blocks[1].training or any(bn.momentum != bbns[0].momentum for bn in bbns):
+                raise ValueError("layer4's two blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
+            btraining = bool(blocks[0].training)
+            if btraining and n * h5 * w5 < 2:
+                raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a C5 of {n} x {h5} x {w5}")
+            prob, thresh, _ = _Layer4BNFPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(bgeoms), beps,
+                                                            tuple(bstats), btraining, float(bbns[0].momentum), *blearn[0], *blearn[1], *params, *hparams)
+            if btraining:
+                with torch.no_grad():
+                    for bn in bbns:
+                        bn.num_batches_tracked.add_(1)
+        else:
+            prob, thresh, _ = _Layer4FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(bgeoms), beps,
+                                                          tuple(bstats), *blearn[0], *blearn[1], *params, *hparams)
         if head.training:
             with torch.no_grad():
                 for bn in bns:
@@ -840,6 +909,47 @@ def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx
     return grads, dx, dxs
 
 
+def _block_bn_forward_raw(tap, geom, training, momentum, eps, learn, stats):
+    """vtd_resblock_bn_train_forward on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace, batch statistics [3,2,width] fp32 -- mu and
+    the biased variance of bn1, bn2 and the downsample's BatchNorm; rows the call does not write are NaN).  In training mode the running
+    statistics in `stats` are updated in place."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, hin, win, cin, width, stride = geom
+    nbytes = int(lib.vtd_resblock_bn_train_workspace_bytes(*geom, 0))
+    _native.check(min(nbytes, 0), "vtd_resblock_bn_train_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
+    bstats = torch.full((3, 2, width), float("nan"), dtype=torch.float32, device=tap.device)
+    st = _block_struct(learn, stats)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _native.check(lib.vtd_resblock_bn_train_forward(ptr(tap), *geom, C.byref(st), 1 if training else 0, float(momentum), eps, ptr(ws), ptr(y), ptr(bstats),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_resblock_bn_train_forward")
+    return y, ws, bstats
+
+
+def _block_bn_backward_raw(tap, geom, training, eps, learn, stats, ws, y, dy, dscale, want_dx):
+    """vtd_resblock_bn_train_backward on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale); dx (the
+    stride-1 block only) is NHWC fp32 [n,h,w,512] times dxscale[0], or None."""
+    import ctypes as C
+    from . import _native
+    lib = _native.require()
+    n, hin, win, cin, width, stride = geom
+    grads = [torch.empty_like(p) for p in learn]
+    nbytes = int(lib.vtd_resblock_bn_train_workspace_bytes(*geom, 1))
+    _native.check(min(nbytes, 0), "vtd_resblock_bn_train_workspace_bytes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    st, gst = _block_struct(learn, stats), _block_struct(grads)
+    dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
+    dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _native.check(lib.vtd_resblock_bn_train_backward(ptr(tap), *geom, C.byref(st), 1 if training else 0, eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale),
+                                                     C.byref(gst), ptr(scratch), ptr(dx), ptr(dxs), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "vtd_resblock_bn_train_backward")
+    return grads, dx, dxs
+
+
 def _combine_scaled(a, ascale, b, bscale):
     """vtd_resblock_train_combine: a <- a + b with both brought to the smaller of their two power-of-two scales; (a, that scale [2])."""
     import ctypes as C
@@ -875,6 +985,31 @@ class _BasicBlockTrainFn(torch.autograd.Function):
         grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx)
         gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
         return (None, gsrc, None, None, None, *grads)
+
+
+class _BasicBlockBNTrainFn(torch.autograd.Function):
+    """_BasicBlockTrainFn on the vtd_resblock_bn_train_* entries (csrc/resblock_bn_train.hip): `training` selects batch statistics (the
+    running statistics in `stats` are then updated in place) or the frozen path."""
+
+    @staticmethod
+    def forward(ctx, tap, src, geom, training, momentum, eps, stats, *learn):
+        y, ws, _ = _block_bn_forward_raw(tap, geom, training, momentum, eps, learn, stats)
+        ctx.save_for_backward(tap, y, *stats, *learn)
+        ctx.ws, ctx.geom, ctx.eps, ctx.nstats, ctx.training = ws, geom, eps, len(stats), bool(training)
+        ctx.src_dtype = None if src is None else src.dtype
+        return y[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        tap, y, *rest = ctx.saved_tensors
+        stats, learn = rest[:ctx.nstats], rest[ctx.nstats:]
+        dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
+        want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
+        grads, dx, dxs = _block_bn_backward_raw(tap, ctx.geom, ctx.training, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx)
+        gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
+        return (None, gsrc, None, None, None, None, None, *grads)
 
 
 class _ResBlockTrainFn(torch.autograd.Function):
@@ -1080,6 +1215,42 @@ class _Layer4FPNHeadTrainFn(torch.autograd.Function):
         g1, dmid, dmid_scale = _block_backward_raw(mid, ctx.bgeoms[1], ctx.beps, b1, ctx.bstats[1], ctx.bws[1], c5, dtaps[3], scales[3], True)
         g0, _, _ = _block_backward_raw(ctx.taps[2], ctx.bgeoms[0], ctx.beps, b0, ctx.bstats[0], ctx.bws[0], mid, dmid, dmid_scale, False)
         return (None,) * 9 + (*g0, *g1, *fgrads, *hgrads)
+
+
+class _Layer4BNFPNHeadTrainFn(torch.autograd.Function):
+    """_Layer4FPNHeadTrainFn with layer4 on the vtd_resblock_bn_train_* entries: `btraining` selects batch statistics for layer4's five
+    BatchNorms (their running statistics in `bstats` are then updated in place, with `bmomentum`) or the frozen path.  The first block
+    forms no input gradient."""
+
+    @staticmethod
+    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, btraining, bmomentum, *params):
+        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
+        n, h5, w5, _ = geom
+        hw = (8 * h5, 8 * w5)
+        mid, bws0, _ = _block_bn_forward_raw(taps[2], bgeoms[0], btraining, bmomentum, beps, b0, bstats[0])
+        c5, bws1, _ = _block_bn_forward_raw(mid, bgeoms[1], btraining, bmomentum, beps, b1, bstats[1])
+        ftaps = (taps[0], taps[1], taps[2], c5)
+        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
+        ctx.save_for_backward(p2p, prob, thresh, mid, c5, *params)
+        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
+        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws, ctx.btraining = bgeoms, beps, bstats, (bws0, bws1), bool(btraining)
+        ctx.mark_non_differentiable(stats)
+        return prob, thresh, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
+        p2p, prob, thresh, mid, c5, *params = ctx.saved_tensors
+        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        ftaps = (ctx.taps[0], ctx.taps[1], ctx.taps[2], c5)
+        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 8)
+        g1, dmid, dmid_scale = _block_bn_backward_raw(mid, ctx.bgeoms[1], ctx.btraining, ctx.beps, b1, ctx.bstats[1], ctx.bws[1], c5, dtaps[3],
+                                                      scales[3], True)
+        g0, _, _ = _block_bn_backward_raw(ctx.taps[2], ctx.bgeoms[0], ctx.btraining, ctx.beps, b0, ctx.bstats[0], ctx.bws[0], mid, dmid, dmid_scale,
+                                          False)
+        return (None,) * 11 + (*g0, *g1, *fgrads, *hgrads)
 
 
 class _Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
@@ -1459,7 +1630,7 @@ class DBNet(_EngineOwner, nn.Module):
     ``{'probability': [B,1,640,640] f32 cuda tensor, 'threshold': same or None}``.
     """
 
-    def __init__(self, backbone="resnet50", pretrained=False, compute_threshold=False, trainable=None):
+    def __init__(self, backbone="resnet50", pretrained=False, compute_threshold=False, trainable=None, trunk_bn="frozen"):
         super().__init__()
         if backbone not in _PLANS:
             raise ValueError(f"unknown backbone {backbone!r}; expected one of {sorted(_PLANS)}")
@@ -1472,10 +1643,19 @@ class DBNet(_EngineOwner, nn.Module):
         self.compute_threshold = compute_threshold
         self._init_engine_state()
         self.trainable = None
-        self.set_trainable(trainable)
+        self.trunk_bn = "frozen"
+        self.set_trainable(trainable, trunk_bn)
 
-    def set_trainable(self, trainable):
-        """None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
+    def set_trainable(self, trainable, trunk_bn=None):
+        """`trunk_bn` ("frozen", the default, or "batch"; None keeps the current value) is the mode of the trained trunk stages' BatchNorms.
+        "frozen": as described below, the running statistics normalise and are never written.  "batch" (accepted only with
+        trainable="head+fpn+layer4" on resnet18; every other combination raises ValueError): a forward in train mode runs the frozen trunk
+        engine for C2..C4 exactly as with "frozen", then layer4 on csrc/resblock_bn_train.hip -- backbone.7's five BatchNorms normalise with
+        the statistics of the batch, as the reference's model.train() step does, and their running statistics and num_batches_tracked move
+        every step; a following eval() forward rebuilds the inference engine on the new statistics.  The state dict is the same in
+        either mode.
+
+        None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
         FPN -- their parameters stop requiring grad, and a forward in train mode runs trunk + FPN on a separate features engine (built
         with fuse_fpn_head=0, rebuilt only when trunk / FPN weights change) and the head on the HIP training kernels, differentiable
         w.r.t. the head's parameters.  "head+fpn": fine-tune the FPN and the head over a frozen trunk -- the backbone's parameters stop
@@ -1511,6 +1691,13 @@ class DBNet(_EngineOwner, nn.Module):
                                  "Bottleneck training is not built")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
+        bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
+        if bn_mode not in ("frozen", "batch"):
+            raise ValueError(f"trunk_bn must be 'frozen' or 'batch', got {bn_mode!r}")
+        if bn_mode == "batch" and trainable != "head+fpn+layer4":
+            raise ValueError(f"trunk_bn='batch' with trainable={trainable!r}: train-mode (batch-statistics) trunk BatchNorm is built for layer4 only, "
+                             "that is for trainable='head+fpn+layer4' on resnet18; layer3, layer2, layer1 and the stem keep frozen statistics")
+        self.trunk_bn = bn_mode
         self.trainable = trainable
         if trainable == "head":
             for p in list(self.backbone.parameters()) + list(self.fpn.parameters()):
@@ -1676,7 +1863,10 @@ class DBNet(_EngineOwner, nn.Module):
             if not next(m.parameters()).is_cuda:
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)   # C5 of the engine is computed from the weights it was built with: ignored
-        out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7])
+        if getattr(self, "trunk_bn", "frozen") == "batch":   # layer4's running statistics move too; mark_dirty below covers them
+            out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7], trunk_batch_stats=True)
+        else:
+            out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
