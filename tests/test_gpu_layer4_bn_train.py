@@ -78,8 +78,8 @@ def _block_case(blk, cin, stride, size, want_dx):
     probe = copy.deepcopy(blk)
     (c_in, width, st), eps, learn, stats = probe._train_operands(torch.device("cuda", torch.cuda.current_device()))
     with torch.no_grad():
-        _, _, bstats = nets._block_bn_forward_raw(nets.pack_tap(x.cuda()), (2, h * stride, w * stride, c_in, width, st), True, probe.bn1.momentum, eps,
-                                                  learn, stats)
+        _, _, bstats = nets._block_forward_raw(nets.pack_tap(x.cuda()), (2, h * stride, w * stride, c_in, width, st), eps, learn, stats,
+                                               bn=(True, probe.bn1.momentum))
     e_stats = max(_rel(bstats[i, j].double().cpu().numpy(), seen[i][j].numpy()) for i in range(len(seen)) for j in range(2))
     if len(seen) == 2:
         assert bool(torch.isnan(bstats[2]).all()), "the third statistics row was written without a downsample"
@@ -201,10 +201,10 @@ def test_chain_layer4_fpn_head_loss_against_fp64(hip):
     rl4 = copy.deepcopy(l4).to(device="cpu", dtype=torch.float64)
     rfpn, rhead = frozen._rounded_fpn(fpn), neck._rounded_head(head).train()
     probe = copy.deepcopy(l4)      # C5 as the kernels store it, from the same starting buffers
-    _, geoms, eps, learn, stats = nets._layer4_operands(probe, padded[2])
+    _, geoms, eps, learn, stats = nets._stage_operands(nets._STAGES[3], probe, padded[2])
     with torch.no_grad():
-        midp, _, _ = nets._block_bn_forward_raw(padded[2], geoms[0], True, 0.1, eps, learn[0], stats[0])
-        c5p, _, _ = nets._block_bn_forward_raw(midp, geoms[1], True, 0.1, eps, learn[1], stats[1])
+        midp, _, _ = nets._block_forward_raw(padded[2], geoms[0], eps, learn[0], stats[0], bn=(True, 0.1))
+        c5p, _, _ = nets._block_forward_raw(midp, geoms[1], eps, learn[1], stats[1], bn=(True, 0.1))
     out, ups = _chain_step(l4, fpn, head, padded, targets)
     p2p = fpn.forward_padded(padded + [c5p])
     x = p2p[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double().cpu().contiguous().requires_grad_(True)

@@ -142,7 +142,7 @@ def test_python_refusals_old_and_new():
     with pytest.raises(RuntimeError, match="layer4 only"):
         nets.BasicBlock(128, 256, 2)._train_operands(torch.device("cpu"))
     with pytest.raises(RuntimeError, match="Bottleneck training is not built"):
-        nets._layer3_operands(nets.make_trunk("resnet50")[6], torch.zeros((1, 6, 6, 128)))
+        nets._stage_operands(nets._STAGES[2], nets.make_trunk("resnet50")[6], torch.zeros((1, 6, 6, 128)))
     with pytest.raises(RuntimeError, match="Bottleneck training is not built"):
         nets.forward_layer3_padded(nets.make_trunk("resnet50")[6], torch.zeros((1, 6, 6, 128)))
     with pytest.raises(ValueError, match="needs layer4 and the DBHead"):

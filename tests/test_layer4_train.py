@@ -340,4 +340,4 @@ def test_head_fpn_layer4_mode():
     with pytest.raises(RuntimeError, match="backward below layer4 is not"):
         net.train()(torch.zeros((1, 3, 640, 640)))
     with pytest.raises(RuntimeError, match="Bottleneck training is not built"):
-        nets._layer4_operands(nets.make_trunk("resnet50")[7], torch.zeros((1, 4, 4, 256)))
+        nets._stage_operands(nets._STAGES[3], nets.make_trunk("resnet50")[7], torch.zeros((1, 4, 4, 256)))

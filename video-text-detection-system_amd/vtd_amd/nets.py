@@ -11,7 +11,7 @@ hold *parameters only*: ``forward`` hands the work to the HIP engine
 Repairs relative to the as-shipped reference: the
 ``'resnet18'`` channel plan exists (A2) and nothing is fetched from the network (A3).
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import os
 import threading
@@ -23,6 +23,17 @@ from torch.autograd.function import once_differentiable
 
 def _conv_bn(cin, cout, k, stride, pad):
     return nn.Conv2d(cin, cout, k, stride, pad, bias=False), nn.BatchNorm2d(cout)
+
+
+def _native_workspace(query, args, device):
+    """The preamble of the raw wrappers of the training kernels: (ctypes, _native, the loaded library, a byte buffer on `device` of the size
+    the library's `query`(*args) asks for).  A negative size is the library's refusal of the arguments and raises its text."""
+    import ctypes
+    from . import _native
+    lib = _native.require()
+    nbytes = int(getattr(lib, query)(*args))
+    _native.check(min(nbytes, 0), query)
+    return ctypes, _native, lib, torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 class _Residual(nn.Module):
@@ -90,7 +101,7 @@ class BasicBlock(_Residual):
             raise RuntimeError("BasicBlock(stride 2): the input requires grad, but the input gradient of the stride-2 block (a strided dgrad) is "
                                "not built; pass x.detach()")
         src = x if x.requires_grad and torch.is_grad_enabled() else None
-        return _BasicBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
+        return _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _BASICBLOCK, None, *learn)
 
 
 _BLOCK_GEOMETRIES = ((64, 128, 2, True), (128, 128, 1, False), (128, 256, 2, True), (256, 256, 1, False), (256, 512, 2, True), (512, 512, 1, False))
@@ -141,7 +152,8 @@ def basic_block_train(block, x, batch_stats=False):
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
         raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
     src = x if x.requires_grad and torch.is_grad_enabled() else None
-    return _ResBlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), *learn)
+    geom = (int(n), int(hin), int(win), cin, width, stride)
+    return _BlockTrainFn.apply(pack_tap(x), src, geom, eps, tuple(stats), _block_entry(geom), None, *learn)
 
 
 def _basic_block_bn_train(block, x, bns):
@@ -155,8 +167,8 @@ def _basic_block_bn_train(block, x, bns):
         raise RuntimeError("BasicBlock(stride 2, batch_stats=True): the input requires grad, but the input gradient of the stride-2 block is not "
                            "built with batch-statistics BatchNorm; pass x.detach()")
     src = x if x.requires_grad and torch.is_grad_enabled() else None
-    out = _BasicBlockBNTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), bool(block.training), float(bns[0].momentum),
-                                     eps, tuple(stats), *learn)
+    out = _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _RESBLOCK_BN,
+                              (bool(block.training), float(bns[0].momentum)), *learn)
     if block.training:
         with torch.no_grad():
             for bn in bns:
@@ -304,203 +316,106 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
-        if trunk_batch_stats:
-            if layer4 is None or any(m is not None for m in (layer3, layer2, layer1, stem)):
-                raise ValueError("forward_padded(..., trunk_batch_stats=True) is the layer4 -> FPN -> head node: " + _BN_TRAIN_BUILT)
-            return self._forward_padded_layer4(taps, head, layer4, trunk_batch_stats=True)
-        if stem is not None:
-            return self._forward_padded_stem(taps, head, layer4, layer3, layer2, layer1, stem)
-        if layer1 is not None:
-            return self._forward_padded_layer1(taps, head, layer4, layer3, layer2, layer1)
-        if layer2 is not None:
-            return self._forward_padded_layer2(taps, head, layer4, layer3, layer2)
-        if layer3 is not None:
-            return self._forward_padded_layer3(taps, head, layer4, layer3)
-        if layer4 is not None:
-            return self._forward_padded_layer4(taps, head, layer4)
+        layers = (layer1, layer2, layer3, layer4)
+        if trunk_batch_stats and (layer4 is None or any(m is not None for m in (layer3, layer2, layer1, stem))):
+            raise ValueError("forward_padded(..., trunk_batch_stats=True) is the layer4 -> FPN -> head node: " + _BN_TRAIN_BUILT)
+        if stem is not None or any(m is not None for m in layers):
+            return self._forward_padded_trunk(taps, head, layers, stem, trunk_batch_stats)
         if not isinstance(taps, (list, tuple)) or len(taps) != 4:
             raise ValueError("padded taps must be the four tensors [C2, C3, C4, C5]")
-        for t in taps:
-            # the kernels trust the buffers' extents: a mismatch here would be a device-side out-of-bounds read
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
-                raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-        geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps])
+        _check_padded_taps(taps)
+        geom = self._geometry([_tap_nchw(t) for t in taps])
         params = self._live_checked(taps[0].device)
         taps = tuple(t.detach() for t in taps)
         if head is None:
             return _fpn_forward_raw(taps, geom, [p.detach() for p in params])[0]
         bns, hparams, hbuffers = head._train_operands(taps[0].device)
-        prob, thresh, _ = _FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), *params, *hparams)
-        if head.training:
-            with torch.no_grad():
-                for bn in bns:
-                    bn.num_batches_tracked.add_(1)
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, (), None, None)      # no trunk stage
+        return self._run_node(head, bns, plan, *params, *hparams)
+
+    @staticmethod
+    def _run_node(head, bns, plan, *learn):
+        prob, thresh, _ = _TrunkFPNHeadTrainFn.apply(plan, *learn)
+        head._batches_seen(bns)
         return {"probability": prob, "threshold": thresh}
 
-
-    def _forward_padded_layer4(self, taps, head, layer4, trunk_batch_stats=False):
-        if head is None:
-            raise ValueError("forward_padded(taps, layer4=...) is the training node: it needs the DBHead too")
-        if not isinstance(taps, (list, tuple)) or len(taps) < 3:
-            raise ValueError("padded taps must be the tensors [C2, C3, C4]")
-        taps = tuple(t.detach() for t in taps[:3])
-        for t in taps:
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
-                raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-        blocks, bgeoms, beps, blearn, bstats = _layer4_operands(layer4, taps[2])
-        n, h5, w5 = bgeoms[1][0], bgeoms[1][1], bgeoms[1][2]
-        geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps] + [(n, 512, h5, w5)])
-        params = self._live_checked(taps[0].device)
-        bns, hparams, hbuffers = head._train_operands(taps[0].device)
-        if trunk_batch_stats:
-            bbns = [bn for b in blocks for bn in _block_bn_check(b)]
-            if blocks[0].training != blocks[1].training or any(bn.momentum != bbns[0].momentum for bn in bbns):
-                raise ValueError("layer4's two blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
-            btraining = bool(blocks[0].training)
-            if btraining and n * h5 * w5 < 2:
-                raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a C5 of {n} x {h5} x {w5}")
-            prob, thresh, _ = _Layer4BNFPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(bgeoms), beps,
-                                                            tuple(bstats), btraining, float(bbns[0].momentum), *blearn[0], *blearn[1], *params, *hparams)
-            if btraining:
-                with torch.no_grad():
-                    for bn in bbns:
-                        bn.num_batches_tracked.add_(1)
-        else:
-            prob, thresh, _ = _Layer4FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(bgeoms), beps,
-                                                          tuple(bstats), *blearn[0], *blearn[1], *params, *hparams)
-        if head.training:
-            with torch.no_grad():
-                for bn in bns:
-                    bn.num_batches_tracked.add_(1)
-        return {"probability": prob, "threshold": thresh}
-
-
-    def _forward_padded_layer3(self, taps, head, layer4, layer3):
-        if head is None or layer4 is None:
-            raise ValueError("forward_padded(taps, layer3=...) is the training node: it needs layer4 and the DBHead too")
-        if not isinstance(taps, (list, tuple)) or len(taps) < 2:
-            raise ValueError("padded taps must be the tensors [C2, C3]")
-        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:2])
-        for t in taps:
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
-                raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, taps[1])
-        n, h4, w4 = g3[1][0], g3[1][1], g3[1][2]
-        c4_shape = torch.empty((n, h4 + 2, w4 + 2, 256), dtype=torch.float16, device="meta")
-        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, c4_shape, taps[1].device)
-        if eps3 != eps4:
-            raise RuntimeError("layer3 / layer4 training needs one BatchNorm eps")
-        h5, w5 = g4[1][1], g4[1][2]
-        geom = self._geometry([(t.shape[0], t.shape[3], t.shape[1] - 2, t.shape[2] - 2) for t in taps] + [(n, 256, h4, w4), (n, 512, h5, w5)])
-        params = self._live_checked(taps[0].device)
-        bns, hparams, hbuffers = head._train_operands(taps[0].device)
-        prob, thresh, _ = _Layer3Layer4FPNHeadTrainFn.apply(taps, geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers), tuple(g3 + g4), eps3,
-                                                            tuple(stats3 + stats4), *learn3[0], *learn3[1], *learn4[0], *learn4[1], *params, *hparams)
-        if head.training:
-            with torch.no_grad():
-                for bn in bns:
-                    bn.num_batches_tracked.add_(1)
-        return {"probability": prob, "threshold": thresh}
-
-
-    def _forward_padded_layer2(self, taps, head, layer4, layer3, layer2):
-        if head is None or layer4 is None or layer3 is None:
-            raise ValueError("forward_padded(taps, layer2=...) is the training node: it needs layer3, layer4 and the DBHead too")
-        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
-            raise ValueError("padded taps must be the tensor [C2]")
-        c2 = taps[0].detach() if torch.is_tensor(taps[0]) else taps[0]
-        if not torch.is_tensor(c2) or not c2.is_cuda or c2.dtype != torch.float16 or not c2.is_contiguous() or c2.dim() != 4 or c2.shape[1] < 3 or c2.shape[2] < 3:
-            raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-        _, g2, eps2, learn2, stats2 = _layer2_operands(layer2, c2)
-        n, h3, w3 = g2[1][0], g2[1][1], g2[1][2]
-        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, torch.empty((n, h3 + 2, w3 + 2, 128), dtype=torch.float16, device="meta"), c2.device)
-        h4, w4 = g3[1][1], g3[1][2]
-        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, torch.empty((n, h4 + 2, w4 + 2, 256), dtype=torch.float16, device="meta"), c2.device)
-        if eps2 != eps3 or eps3 != eps4:
-            raise RuntimeError("layer2 / layer3 / layer4 training needs one BatchNorm eps")
-        h5, w5 = g4[1][1], g4[1][2]
-        geom = self._geometry([(n, c2.shape[3], c2.shape[1] - 2, c2.shape[2] - 2), (n, 128, h3, w3), (n, 256, h4, w4), (n, 512, h5, w5)])
-        params = self._live_checked(c2.device)
-        bns, hparams, hbuffers = head._train_operands(c2.device)
-        prob, thresh, _ = _Layer2Layer3Layer4FPNHeadTrainFn.apply((c2,), geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers),
-                                                                  tuple(g2 + g3 + g4), eps2, tuple(stats2 + stats3 + stats4), *learn2[0], *learn2[1],
-                                                                  *learn3[0], *learn3[1], *learn4[0], *learn4[1], *params, *hparams)
-        if head.training:
-            with torch.no_grad():
-                for bn in bns:
-                    bn.num_batches_tracked.add_(1)
-        return {"probability": prob, "threshold": thresh}
-
-
-    def _forward_padded_layer1(self, taps, head, layer4, layer3, layer2, layer1):
-        if head is None or layer4 is None or layer3 is None or layer2 is None:
-            raise ValueError("forward_padded(taps, layer1=...) is the training node: it needs layer2, layer3, layer4 and the DBHead too")
-        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
-            raise ValueError("padded taps must be the tensor [pool]")
-        pool = taps[0].detach() if torch.is_tensor(taps[0]) else taps[0]
-        if (not torch.is_tensor(pool) or not pool.is_cuda or pool.dtype != torch.float16 or not pool.is_contiguous() or pool.dim() != 4 or pool.shape[1] < 3
-                or pool.shape[2] < 3):
-            raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-        dev = pool.device
-        meta = lambda n, h, w, c: torch.empty((n, h + 2, w + 2, c), dtype=torch.float16, device="meta")  # noqa: E731
-        _, g1, eps1, learn1, stats1 = _layer1_operands(layer1, pool)
-        n, h2, w2 = g1[0][0], g1[0][1], g1[0][2]
-        _, g2, eps2, learn2, stats2 = _layer2_operands(layer2, meta(n, h2, w2, 64), dev)
-        h3, w3 = g2[1][1], g2[1][2]
-        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, meta(n, h3, w3, 128), dev)
-        h4, w4 = g3[1][1], g3[1][2]
-        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, meta(n, h4, w4, 256), dev)
-        if eps1 != eps2 or eps2 != eps3 or eps3 != eps4:
-            raise RuntimeError("layer1 / layer2 / layer3 / layer4 training needs one BatchNorm eps")
-        h5, w5 = g4[1][1], g4[1][2]
-        geom = self._geometry([(n, 64, h2, w2), (n, 128, h3, w3), (n, 256, h4, w4), (n, 512, h5, w5)])
-        params = self._live_checked(dev)
-        bns, hparams, hbuffers = head._train_operands(dev)
-        prob, thresh, _ = _Layer1Layer2Layer3Layer4FPNHeadTrainFn.apply((pool,), geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers),
-                                                                        tuple(g1 + g2 + g3 + g4), eps1, tuple(stats1 + stats2 + stats3 + stats4),
-                                                                        *learn1[0], *learn1[1], *learn2[0], *learn2[1], *learn3[0], *learn3[1],
-                                                                        *learn4[0], *learn4[1], *params, *hparams)
-        if head.training:
-            with torch.no_grad():
-                for bn in bns:
-                    bn.num_batches_tracked.add_(1)
-        return {"probability": prob, "threshold": thresh}
-
-
-    def _forward_padded_stem(self, taps, head, layer4, layer3, layer2, layer1, stem):
-        if head is None or layer4 is None or layer3 is None or layer2 is None or layer1 is None:
-            raise ValueError("forward_padded(taps, stem=...) is the training node: it needs layer1, layer2, layer3, layer4 and the DBHead too")
-        if not isinstance(stem, (list, tuple)) or len(stem) != 2:
+    def _forward_padded_trunk(self, taps, head, layers, stem, trunk_batch_stats):
+        """forward_padded with trunk stages: `layers` is (layer1, layer2, layer3, layer4), the node starts at the lowest one given (with `stem`:
+        at the stem) and needs every stage above it and the head."""
+        low = 0 if stem is not None else next(i for i, m in enumerate(layers) if m is not None)
+        above = _STAGES[0 if stem is not None else low + 1:]
+        if head is None or any(m is None for m in layers[4 - len(above):]):
+            raise ValueError(f"forward_padded(taps, {'stem' if stem is not None else _STAGES[low].name}=...) is the training node: it needs "
+                             + ", ".join(st.name for st in above) + (" and " if above else "") + "the DBHead too")
+        if stem is not None and (not isinstance(stem, (list, tuple)) or len(stem) != 2):
             raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
-        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
-            raise ValueError("padded taps must be the tensor [image]")
-        image = taps[0].detach() if torch.is_tensor(taps[0]) else taps[0]
-        sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], image)
-        dev = image.device
-        n, hp, wp = sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2
-        meta = lambda n, h, w, c: torch.empty((n, h + 2, w + 2, c), dtype=torch.float16, device="meta")  # noqa: E731
-        _, g1, eps1, learn1, stats1 = _layer1_operands(layer1, meta(n, hp, wp, 64), dev)
-        _, g2, eps2, learn2, stats2 = _layer2_operands(layer2, meta(n, hp, wp, 64), dev)
-        h3, w3 = g2[1][1], g2[1][2]
-        _, g3, eps3, learn3, stats3 = _layer3_operands(layer3, meta(n, h3, w3, 128), dev)
-        h4, w4 = g3[1][1], g3[1][2]
-        _, g4, eps4, learn4, stats4 = _layer4_operands(layer4, meta(n, h4, w4, 256), dev)
-        if eps1 != eps2 or eps2 != eps3 or eps3 != eps4:
-            raise RuntimeError("layer1 / layer2 / layer3 / layer4 training needs one BatchNorm eps")
-        h5, w5 = g4[1][1], g4[1][2]
-        geom = self._geometry([(n, 64, hp, wp), (n, 128, h3, w3), (n, 256, h4, w4), (n, 512, h5, w5)])
+        # the taps the node reads: the FPN levels below the lowest stage's output, the last of them that stage's input; layer1 reads the pooled
+        # stem output and the stem the image, neither an FPN level
+        names = ["image"] if stem is not None else [st.tap for st in _STAGES[1:low + 1]] or [_STAGES[0].tap]
+        if not isinstance(taps, (list, tuple)) or len(taps) < len(names):
+            raise ValueError(f"padded taps must be the tensor{'s' if len(names) > 1 else ''} [{', '.join(names)}]")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:len(names)])
+        slearn, splan = [], None
+        if stem is None:
+            _check_padded_taps(taps)
+            x = taps[-1]
+        else:
+            sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], taps[0])
+            splan = (sgeom, seps, tuple(sstats))
+            x = _meta_tap(sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2, 64)
+        dev = taps[-1].device
+        ops, outs = [], []      # per stage: _stage_operands' result, and its output C(k) as (n, C, h, w)
+        for st, layer in zip(_STAGES[low:], layers[low:]):      # each stage's output shape is the next one's input
+            ops.append(_stage_operands(st, layer, x, dev))
+            n, h, w = ops[-1][1][1][:3]      # the extent the stage's second block runs at
+            outs.append((n, st.width, h, w))
+            x = _meta_tap(n, h, w, st.width)
+        beps = ops[0][2]
+        if any(o[2] != beps for o in ops):
+            raise RuntimeError(" / ".join(st.name for st in _STAGES[low:]) + " training needs one BatchNorm eps")
+        geom = self._geometry(([_tap_nchw(t) for t in taps] + outs)[-4:])      # C2 .. C5: the last four (the image and the pooled tap fall out)
         params = self._live_checked(dev)
         bns, hparams, hbuffers = head._train_operands(dev)
-        prob, thresh, _ = _StemLayer1Layer2Layer3Layer4FPNHeadTrainFn.apply((image,), geom, head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers),
-                                                                            sgeom, seps, tuple(sstats), tuple(g1 + g2 + g3 + g4), eps1,
-                                                                            tuple(stats1 + stats2 + stats3 + stats4), *slearn, *learn1[0], *learn1[1],
-                                                                            *learn2[0], *learn2[1], *learn3[0], *learn3[1], *learn4[0], *learn4[1],
-                                                                            *params, *hparams)
-        if head.training:
+        bn, bbns = None, []
+        if trunk_batch_stats:
+            blocks = ops[-1][0]
+            bbns = [b for blk in blocks for b in _block_bn_check(blk)]
+            if blocks[0].training != blocks[1].training or any(b.momentum != bbns[0].momentum for b in bbns):
+                raise ValueError("layer4's two blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
+            n, _, h5, w5 = outs[-1]
+            if blocks[0].training and n * h5 * w5 < 2:
+                raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a C5 of {n} x {h5} x {w5}")
+            bn = (bool(blocks[0].training), float(bbns[0].momentum))
+        blocks = []
+        for _, geoms, _, learn, stats in ops:
+            for g, lr, s in zip(geoms, learn, stats):
+                # a node of one stage runs on that stage's own entry family, as forward_<stage>_padded does; a deeper one on the block's by width
+                entry = _RESBLOCK_BN if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
+                blocks.append((_BlockPlan(g, s, entry, len(lr)), lr))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, tuple(b for b, _ in blocks), beps, bn)
+        out = self._run_node(head, bns, plan, *slearn, *(t for _, lr in blocks for t in lr), *params, *hparams)
+        if bn is not None and bn[0]:
             with torch.no_grad():
-                for bn in bns:
-                    bn.num_batches_tracked.add_(1)
-        return {"probability": prob, "threshold": thresh}
+                for b in bbns:
+                    b.num_batches_tracked.add_(1)
+        return out
+
+
+def _check_padded_taps(taps):
+    for t in taps:
+        # the kernels trust the buffers' extents: a mismatch here would be a device-side out-of-bounds read
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3:
+            raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+
+
+def _tap_nchw(tap):
+    """The (n, C, h, w) a padded tap [n,h+2,w+2,C] holds."""
+    return (tap.shape[0], tap.shape[3], tap.shape[1] - 2, tap.shape[2] - 2)
+
+
+def _meta_tap(n, h, w, c):
+    """A shape-only stand-in for the padded tap [n,h+2,w+2,c] that a stage of the node will produce."""
+    return torch.empty((n, h + 2, w + 2, c), dtype=torch.float16, device="meta")
 
 
 def _stem_operands(conv, bn, image_tap):
@@ -535,14 +450,9 @@ def _stem_struct(learn, stats=None):
 
 def _stem_forward_raw(tap, geom, eps, learn, stats):
     """vtd_stem_train_forward on an image tap: (the pooled padded tap [n,hp+2,wp+2,64] fp16, idx [n,hp,wp,64] uint8, workspace)."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
     n, H, W = geom
     hp, wp = (H // 2 + 1) // 2, (W // 2 + 1) // 2
-    nbytes = int(lib.vtd_stem_train_workspace_bytes(n, H, W, 0))
-    _native.check(min(nbytes, 0), "vtd_stem_train_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    C, _native, lib, ws = _native_workspace("vtd_stem_train_workspace_bytes", (n, H, W, 0), tap.device)
     pool = torch.empty((n, hp + 2, wp + 2, 64), dtype=torch.float16, device=tap.device)
     idx = torch.empty((n, hp, wp, 64), dtype=torch.uint8, device=tap.device)
     st = _stem_struct(learn, stats)
@@ -554,14 +464,9 @@ def _stem_forward_raw(tap, geom, eps, learn, stats):
 
 def _stem_backward_raw(tap, geom, eps, learn, stats, ws, pool, idx, dpool, dscale):
     """vtd_stem_train_backward on dpool as NHWC fp32 [n,hp,wp,64] times dscale[0]: the gradients of [conv.weight, bn.weight, bn.bias]."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
     n, H, W = geom
     grads = [torch.empty_like(p) for p in learn]
-    nbytes = int(lib.vtd_stem_train_workspace_bytes(n, H, W, 1))
-    _native.check(min(nbytes, 0), "vtd_stem_train_workspace_bytes")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    C, _native, lib, scratch = _native_workspace("vtd_stem_train_workspace_bytes", (n, H, W, 1), tap.device)
     st, gst = _stem_struct(learn, stats), _stem_struct(grads)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     _native.check(lib.vtd_stem_train_backward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx), ptr(dpool), ptr(dscale), C.byref(gst),
@@ -632,101 +537,60 @@ def forward_stem_padded(conv, bn, image_tap):
         return _stem_forward_raw(image_tap.detach(), geom, eps, [t.detach() for t in learn], stats)[0]
 
 
-def _layer1_operands(layer1, pool_tap, device=None):
-    """ResNet-18's layer1 on a padded tap of the pooled stem output: (the two blocks, their geometries, eps, their learnable tensors, their
+# ResNet-18's four residual stages, two BasicBlocks each (the first cin -> width at `stride`, the second width -> width at stride 1): `tap` names
+# the stage's input, `operands` are the keywords of BasicBlock._train_operands that admit its geometries, `entry` is the entry family the stage
+# runs on when it runs alone (forward_<stage>_padded, and the training node of layer4 alone)
+_Stage = namedtuple("_Stage", "name cin width stride tap operands entry")
+_STAGES = (_Stage("layer1", 64, 64, 1, "pool", {"general": True, "narrow": True}, "vtd_block64_train"),
+           _Stage("layer2", 64, 128, 2, "C2", {"general": True}, "vtd_resblock_train"),
+           _Stage("layer3", 128, 256, 2, "C3", {"general": True}, "vtd_resblock_train"),
+           _Stage("layer4", 256, 512, 2, "C4", {}, "vtd_basicblock_train"))
+
+
+def _stage_operands(stage, layer, tap, device=None):
+    """One stage (a row of _STAGES) on a padded tap of its input: (the two blocks, their geometries, eps, their learnable tensors, their
     running statistics).  Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
-    blocks = list(layer1)
+    name, cin, width, stride = stage.name, stage.cin, stage.width, stage.stride
+    blocks = list(layer)
     if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
-        raise RuntimeError("layer1 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
-    n, h, w = int(pool_tap.shape[0]), int(pool_tap.shape[1]) - 2, int(pool_tap.shape[2]) - 2
-    ops = [b._train_operands(pool_tap.device if device is None else device, general=True, narrow=True) for b in blocks]
-    if [o[0] for o in ops] != [(64, 64, 1), (64, 64, 1)] or pool_tap.shape[3] != 64:
-        raise RuntimeError("layer1 training is built for ResNet-18's layer1 (64 -> 64 stride 1, twice)")
-    if ops[0][1] != ops[1][1]:
-        raise RuntimeError("layer1 training needs one BatchNorm eps")
-    geoms = [(n, h, w, 64, 64, 1), (n, h, w, 64, 64, 1)]
+        raise RuntimeError(f"{name} training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
+    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
+    ops = [b._train_operands(tap.device if device is None else device, **stage.operands) for b in blocks]
+    if [o[0] for o in ops] != [(cin, width, stride), (width, width, 1)] or tap.shape[3] != cin:
+        built = f"{cin} -> {width} stride 1, twice" if stride == 1 else f"{cin} -> {width} stride {stride}, then {width} -> {width} stride 1"
+        raise RuntimeError(f"{name} training is built for ResNet-18's {name} ({built})")
+    if (stride == 2 and (h % 2 or w % 2)) or ops[0][1] != ops[1][1]:
+        raise RuntimeError(f"{name} training needs " + (f"a {stage.tap} of even extents and " if stride == 2 else "") + "one BatchNorm eps")
+    geoms = [(n, h, w, cin, width, stride), (n, h // stride, w // stride, width, width, 1)]
     return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def _forward_stage_padded(stage, layer, tap):
+    _, geoms, eps, learn, stats = _stage_operands(stage, layer, tap)
+    with torch.no_grad():
+        mid, _ = _block_forward_raw(tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], stage.entry)
+        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], stage.entry)[0]
 
 
 def forward_layer1_padded(layer1, pool_tap):
     """ResNet-18's layer1 on a padded tap of the pooled stem output with the HIP training kernels, no gradient: padded C2
     [n,h+2,w+2,64] fp16."""
-    _, geoms, eps, learn, stats = _layer1_operands(layer1, pool_tap)
-    with torch.no_grad():
-        mid, _ = _block_forward_raw(pool_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], _BLOCK64)
-        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], _BLOCK64)[0]
-
-
-def _layer2_operands(layer2, c2_tap, device=None):
-    """ResNet-18's layer2 on a padded C2 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics).
-    Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
-    blocks = list(layer2)
-    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
-        raise RuntimeError("layer2 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
-    n, h2, w2 = int(c2_tap.shape[0]), int(c2_tap.shape[1]) - 2, int(c2_tap.shape[2]) - 2
-    ops = [b._train_operands(c2_tap.device if device is None else device, general=True) for b in blocks]
-    if [o[0] for o in ops] != [(64, 128, 2), (128, 128, 1)] or c2_tap.shape[3] != 64:
-        raise RuntimeError("layer2 training is built for ResNet-18's layer2 (64 -> 128 stride 2, then 128 -> 128 stride 1)")
-    if h2 % 2 or w2 % 2 or ops[0][1] != ops[1][1]:
-        raise RuntimeError("layer2 training needs a C2 of even extents and one BatchNorm eps")
-    geoms = [(n, h2, w2, 64, 128, 2), (n, h2 // 2, w2 // 2, 128, 128, 1)]
-    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+    return _forward_stage_padded(_STAGES[0], layer1, pool_tap)
 
 
 def forward_layer2_padded(layer2, c2_tap):
     """ResNet-18's layer2 on a padded C2 tap with the HIP training kernels, no gradient: padded C3 [n,h3+2,w3+2,128] fp16."""
-    _, geoms, eps, learn, stats = _layer2_operands(layer2, c2_tap)
-    with torch.no_grad():
-        mid, _ = _block_forward_raw(c2_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], _RESBLOCK)
-        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], _RESBLOCK)[0]
-
-
-def _layer3_operands(layer3, c3_tap, device=None):
-    """ResNet-18's layer3 on a padded C3 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics).
-    Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
-    blocks = list(layer3)
-    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
-        raise RuntimeError("layer3 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
-    n, h3, w3 = int(c3_tap.shape[0]), int(c3_tap.shape[1]) - 2, int(c3_tap.shape[2]) - 2
-    ops = [b._train_operands(c3_tap.device if device is None else device, general=True) for b in blocks]
-    if [o[0] for o in ops] != [(128, 256, 2), (256, 256, 1)] or c3_tap.shape[3] != 128:
-        raise RuntimeError("layer3 training is built for ResNet-18's layer3 (128 -> 256 stride 2, then 256 -> 256 stride 1)")
-    if h3 % 2 or w3 % 2 or ops[0][1] != ops[1][1]:
-        raise RuntimeError("layer3 training needs a C3 of even extents and one BatchNorm eps")
-    geoms = [(n, h3, w3, 128, 256, 2), (n, h3 // 2, w3 // 2, 256, 256, 1)]
-    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+    return _forward_stage_padded(_STAGES[1], layer2, c2_tap)
 
 
 def forward_layer3_padded(layer3, c3_tap):
     """ResNet-18's layer3 on a padded C3 tap with the HIP training kernels, no gradient: padded C4 [n,h4+2,w4+2,256] fp16."""
-    _, geoms, eps, learn, stats = _layer3_operands(layer3, c3_tap)
-    with torch.no_grad():
-        mid, _ = _block_forward_raw(c3_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0], _RESBLOCK)
-        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1], _RESBLOCK)[0]
-
-
-def _layer4_operands(layer4, c4_tap, device=None):
-    """ResNet-18's layer4 on a padded C4 tap: (the two blocks, their geometries, eps, their learnable tensors, their running statistics).
-    Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
-    blocks = list(layer4)
-    if len(blocks) != 2 or not all(isinstance(b, BasicBlock) for b in blocks):
-        raise RuntimeError("layer4 training is built for ResNet-18's two BasicBlocks; Bottleneck training is not built")
-    n, h4, w4 = int(c4_tap.shape[0]), int(c4_tap.shape[1]) - 2, int(c4_tap.shape[2]) - 2
-    ops = [b._train_operands(c4_tap.device if device is None else device) for b in blocks]
-    if [o[0] for o in ops] != [(256, 512, 2), (512, 512, 1)] or c4_tap.shape[3] != 256:
-        raise RuntimeError("layer4 training is built for ResNet-18's layer4 (256 -> 512 stride 2, then 512 -> 512 stride 1)")
-    if h4 % 2 or w4 % 2 or ops[0][1] != ops[1][1]:
-        raise RuntimeError("layer4 training needs a C4 of even extents and one BatchNorm eps")
-    geoms = [(n, h4, w4, 256, 512, 2), (n, h4 // 2, w4 // 2, 512, 512, 1)]
-    return blocks, geoms, ops[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+    return _forward_stage_padded(_STAGES[2], layer3, c3_tap)
 
 
 def forward_layer4_padded(layer4, c4_tap):
     """ResNet-18's layer4 on a padded C4 tap with the HIP training kernels, no gradient: padded C5 [n,h5+2,w5+2,512] fp16."""
-    _, geoms, eps, learn, stats = _layer4_operands(layer4, c4_tap)
-    with torch.no_grad():
-        mid, _ = _block_forward_raw(c4_tap.detach(), geoms[0], eps, [t.detach() for t in learn[0]], stats[0])
-        return _block_forward_raw(mid, geoms[1], eps, [t.detach() for t in learn[1]], stats[1])[0]
+    return _forward_stage_padded(_STAGES[3], layer4, c4_tap)
 
 
 def _db_branch(c):
@@ -771,13 +635,10 @@ def _head_structs(params, buffers=None, grads=None):
 
 def _head_forward_raw(feats, hw, training, momentum, eps, buffers, params):
     """vtd_dbhead_train_forward on padded features: (workspace, prob, thresh, stats)."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
     n, (H, W) = feats.shape[0], hw
     st, _ = _head_structs(params, buffers)
     dev = feats.device
-    ws = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 0)), dtype=torch.uint8, device=dev)
+    C, _native, lib, ws = _native_workspace("vtd_dbhead_train_workspace_bytes", (n, H, W, 0), dev)
     prob = torch.empty((n, 1, 4 * H, 4 * W), dtype=torch.float32, device=dev)
     thresh = torch.empty_like(prob)
     stats = torch.empty((4, 2, 64), dtype=torch.float32, device=dev)
@@ -790,13 +651,10 @@ def _head_forward_raw(feats, hw, training, momentum, eps, buffers, params):
 
 def _head_backward_raw(feats, hw, training, ws, prob, thresh, params, grad_prob, grad_thresh, want_input):
     """vtd_dbhead_train_backward (+ _backward_input): (the 20 gradients, dfeats, dscale); dfeats is NHWC fp32 [n,H,W,256] times dscale[0]."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
     n, (H, W) = feats.shape[0], hw
     grads = [torch.empty_like(p) for p in params]
     st, gst = _head_structs(params, None, grads)
-    scratch = torch.empty(int(lib.vtd_dbhead_train_workspace_bytes(n, H, W, 2 if want_input else 1)), dtype=torch.uint8, device=feats.device)
+    C, _native, lib, scratch = _native_workspace("vtd_dbhead_train_workspace_bytes", (n, H, W, 2 if want_input else 1), feats.device)
     g = [None if t is None else t.to(torch.float32).contiguous() for t in (grad_prob, grad_thresh)]
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -863,8 +721,10 @@ def _block_struct(learn, stats=None):
     return st
 
 
-_RESBLOCK = "vtd_resblock_train"   # the entry family of the six geometries; the default below is layer4's two (no strided dgrad)
-_BLOCK64 = "vtd_block64_train"     # the entry family of layer1's 64 -> 64 block
+_BASICBLOCK = "vtd_basicblock_train"   # the entry family of layer4's two geometries (no strided dgrad)
+_RESBLOCK = "vtd_resblock_train"       # the entry family of the six geometries of layer2, layer3 and layer4
+_BLOCK64 = "vtd_block64_train"         # the entry family of layer1's 64 -> 64 block
+_RESBLOCK_BN = "vtd_resblock_bn_train"   # layer4's two geometries with batch-statistics BatchNorm (csrc/resblock_bn_train.hip)
 
 
 def _block_entry(geom):
@@ -872,81 +732,40 @@ def _block_entry(geom):
     return _BLOCK64 if geom[4] == 64 else _RESBLOCK
 
 
-def _block_forward_raw(tap, geom, eps, learn, stats, entry="vtd_basicblock_train"):
-    """vtd_basicblock_train_forward (or `entry`'s) on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace)."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
+def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None):
+    """vtd_basicblock_train_forward (or `entry`'s) on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace).  With `bn` = (training,
+    momentum) it is vtd_resblock_bn_train_forward, which takes the two after the parameters, and the result has a third member: the batch
+    statistics [3,2,width] fp32 -- mu and the biased variance of bn1, bn2 and the downsample's BatchNorm; rows the call does not write are
+    NaN.  In training mode the running statistics in `stats` are then updated in place."""
+    entry = _RESBLOCK_BN if bn is not None else entry
+    C, _native, lib, ws = _native_workspace(entry + "_workspace_bytes", (*geom, 0), tap.device)
     n, hin, win, cin, width, stride = geom
-    nbytes = int(getattr(lib, entry + "_workspace_bytes")(*geom, 0))
-    _native.check(min(nbytes, 0), entry + "_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
     y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
-    st = _block_struct(learn, stats)
-    _native.check(getattr(lib, entry + "_forward")(C.c_void_p(tap.data_ptr()), *geom, C.byref(st), eps, C.c_void_p(ws.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry + "_forward")
-    return y, ws
-
-
-def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx, entry="vtd_basicblock_train"):
-    """vtd_basicblock_train_backward (or `entry`'s) on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale);
-    dx is NHWC fp32 [n,h_in,w_in,cin] times dxscale[0], or None."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
-    n, hin, win, cin, width, stride = geom
-    grads = [torch.empty_like(p) for p in learn]
-    nbytes = int(getattr(lib, entry + "_workspace_bytes")(*geom, 1))
-    _native.check(min(nbytes, 0), entry + "_workspace_bytes")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
-    st, gst = _block_struct(learn, stats), _block_struct(grads)
-    dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
-    dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    _native.check(getattr(lib, entry + "_backward")(ptr(tap), *geom, C.byref(st), eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale), C.byref(gst), ptr(scratch),
-                                                    ptr(dx), ptr(dxs), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                  entry + "_backward")
-    return grads, dx, dxs
-
-
-def _block_bn_forward_raw(tap, geom, training, momentum, eps, learn, stats):
-    """vtd_resblock_bn_train_forward on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace, batch statistics [3,2,width] fp32 -- mu and
-    the biased variance of bn1, bn2 and the downsample's BatchNorm; rows the call does not write are NaN).  In training mode the running
-    statistics in `stats` are updated in place."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
-    n, hin, win, cin, width, stride = geom
-    nbytes = int(lib.vtd_resblock_bn_train_workspace_bytes(*geom, 0))
-    _native.check(min(nbytes, 0), "vtd_resblock_bn_train_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
-    y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
-    bstats = torch.full((3, 2, width), float("nan"), dtype=torch.float32, device=tap.device)
+    mode = () if bn is None else (1 if bn[0] else 0, float(bn[1]))
+    bstats = () if bn is None else (torch.full((3, 2, width), float("nan"), dtype=torch.float32, device=tap.device),)
     st = _block_struct(learn, stats)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    _native.check(lib.vtd_resblock_bn_train_forward(ptr(tap), *geom, C.byref(st), 1 if training else 0, float(momentum), eps, ptr(ws), ptr(y), ptr(bstats),
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_resblock_bn_train_forward")
-    return y, ws, bstats
+    _native.check(getattr(lib, entry + "_forward")(ptr(tap), *geom, C.byref(st), *mode, eps, ptr(ws), ptr(y), *map(ptr, bstats),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry + "_forward")
+    return (y, ws, *bstats)
 
 
-def _block_bn_backward_raw(tap, geom, training, eps, learn, stats, ws, y, dy, dscale, want_dx):
-    """vtd_resblock_bn_train_backward on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale); dx (the
-    stride-1 block only) is NHWC fp32 [n,h,w,512] times dxscale[0], or None."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
-    n, hin, win, cin, width, stride = geom
+def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx, entry=_BASICBLOCK, bn=None):
+    """vtd_basicblock_train_backward (or `entry`'s) on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale);
+    dx is NHWC fp32 [n,h_in,w_in,cin] times dxscale[0], or None.  With `bn` = (training, momentum) it is vtd_resblock_bn_train_backward,
+    which takes the mode after the parameters and forms dx for the stride-1 block only."""
+    entry = _RESBLOCK_BN if bn is not None else entry
     grads = [torch.empty_like(p) for p in learn]
-    nbytes = int(lib.vtd_resblock_bn_train_workspace_bytes(*geom, 1))
-    _native.check(min(nbytes, 0), "vtd_resblock_bn_train_workspace_bytes")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=tap.device)
+    C, _native, lib, scratch = _native_workspace(entry + "_workspace_bytes", (*geom, 1), tap.device)
+    n, hin, win, cin, width, stride = geom
     st, gst = _block_struct(learn, stats), _block_struct(grads)
     dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
     dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
+    mode = () if bn is None else (1 if bn[0] else 0,)
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    _native.check(lib.vtd_resblock_bn_train_backward(ptr(tap), *geom, C.byref(st), 1 if training else 0, eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale),
-                                                     C.byref(gst), ptr(scratch), ptr(dx), ptr(dxs), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                  "vtd_resblock_bn_train_backward")
+    _native.check(getattr(lib, entry + "_backward")(ptr(tap), *geom, C.byref(st), *mode, eps, ptr(ws), ptr(y), ptr(dy), ptr(dscale), C.byref(gst),
+                                                    ptr(scratch), ptr(dx), ptr(dxs), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  entry + "_backward")
     return grads, dx, dxs
 
 
@@ -962,15 +781,18 @@ def _combine_scaled(a, ascale, b, bscale):
     return a, out
 
 
-class _BasicBlockTrainFn(torch.autograd.Function):
-    """One BasicBlock on the HIP training kernels: padded tap in, [n,width,h,w] fp32 out.  `src` is None or the NCHW tensor the tap was packed
-    from (stride-1 block only): when it requires grad it receives the input gradient in its own dtype."""
+class _BlockTrainFn(torch.autograd.Function):
+    """One BasicBlock on the HIP training kernels: padded tap in, [n,width,h,w] fp32 out.  `entry` is the entry family: vtd_basicblock_train
+    (layer4's two geometries; `src` for the stride-1 block only), vtd_resblock_train or vtd_block64_train (the seven geometries, `src` for
+    either stride), or with `bn` = (training, momentum) vtd_resblock_bn_train (csrc/resblock_bn_train.hip): `training` selects batch
+    statistics (the running statistics in `stats` are then updated in place) or the frozen path.  `src` is None or the NCHW tensor the tap
+    was packed from: when it requires grad it receives the input gradient in its own dtype."""
 
     @staticmethod
-    def forward(ctx, tap, src, geom, eps, stats, *learn):
-        y, ws = _block_forward_raw(tap, geom, eps, learn, stats)
+    def forward(ctx, tap, src, geom, eps, stats, entry, bn, *learn):
+        y, ws = _block_forward_raw(tap, geom, eps, learn, stats, entry, bn)[:2]
         ctx.save_for_backward(tap, y, *stats, *learn)
-        ctx.ws, ctx.geom, ctx.eps, ctx.nstats = ws, geom, eps, len(stats)
+        ctx.ws, ctx.geom, ctx.eps, ctx.nstats, ctx.entry, ctx.bn = ws, geom, eps, len(stats), entry, bn
         ctx.src_dtype = None if src is None else src.dtype
         return y[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
 
@@ -982,59 +804,9 @@ class _BasicBlockTrainFn(torch.autograd.Function):
         dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
         dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
         want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
-        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx)
-        gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
-        return (None, gsrc, None, None, None, *grads)
-
-
-class _BasicBlockBNTrainFn(torch.autograd.Function):
-    """_BasicBlockTrainFn on the vtd_resblock_bn_train_* entries (csrc/resblock_bn_train.hip): `training` selects batch statistics (the
-    running statistics in `stats` are then updated in place) or the frozen path."""
-
-    @staticmethod
-    def forward(ctx, tap, src, geom, training, momentum, eps, stats, *learn):
-        y, ws, _ = _block_bn_forward_raw(tap, geom, training, momentum, eps, learn, stats)
-        ctx.save_for_backward(tap, y, *stats, *learn)
-        ctx.ws, ctx.geom, ctx.eps, ctx.nstats, ctx.training = ws, geom, eps, len(stats), bool(training)
-        ctx.src_dtype = None if src is None else src.dtype
-        return y[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        tap, y, *rest = ctx.saved_tensors
-        stats, learn = rest[:ctx.nstats], rest[ctx.nstats:]
-        dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
-        dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
-        want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
-        grads, dx, dxs = _block_bn_backward_raw(tap, ctx.geom, ctx.training, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx)
+        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx, ctx.entry, ctx.bn)
         gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
         return (None, gsrc, None, None, None, None, None, *grads)
-
-
-class _ResBlockTrainFn(torch.autograd.Function):
-    """_BasicBlockTrainFn on the vtd_resblock_train_* entries (the 64-wide block: vtd_block64_train_*): the seven geometries, and `src`
-    receives its gradient for either stride."""
-
-    @staticmethod
-    def forward(ctx, tap, src, geom, eps, stats, *learn):
-        y, ws = _block_forward_raw(tap, geom, eps, learn, stats, _block_entry(geom))
-        ctx.save_for_backward(tap, y, *stats, *learn)
-        ctx.ws, ctx.geom, ctx.eps, ctx.nstats = ws, geom, eps, len(stats)
-        ctx.src_dtype = None if src is None else src.dtype
-        return y[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        tap, y, *rest = ctx.saved_tensors
-        stats, learn = rest[:ctx.nstats], rest[ctx.nstats:]
-        dy = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
-        dscale = torch.ones(2, dtype=torch.float32, device=dy.device)
-        want_dx = ctx.src_dtype is not None and ctx.needs_input_grad[1]
-        grads, dx, dxs = _block_backward_raw(tap, ctx.geom, ctx.eps, learn, stats, ctx.ws, y, dy, dscale, want_dx, _block_entry(ctx.geom))
-        gsrc = _fpn_unpack_tap_grad(dx, dxs).to(ctx.src_dtype) if want_dx else None
-        return (None, gsrc, None, None, None, *grads)
 
 
 # ---- FPN training (csrc/fpn_train.hip).  geom = (n, h5, w5, c5 channels); taps = padded taps C2..C5; params = the ten live tensors:
@@ -1059,14 +831,9 @@ def _fpn_taps(taps):
 
 def _fpn_forward_raw(taps, geom, params):
     """vtd_fpn_train_forward: (padded P2 [n,8 h5 + 2,8 w5 + 2,256] fp16, workspace)."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
     n, h5, w5, c5 = geom
     dev = taps[0].device
-    nbytes = int(lib.vtd_fpn_train_workspace_bytes(n, h5, w5, c5, 0))
-    _native.check(min(nbytes, 0), "vtd_fpn_train_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    C, _native, lib, ws = _native_workspace("vtd_fpn_train_workspace_bytes", (n, h5, w5, c5, 0), dev)
     p2 = torch.empty((n, 8 * h5 + 2, 8 * w5 + 2, 256), dtype=torch.float16, device=dev)
     st, tp = _fpn_struct(params), _fpn_taps(taps)
     _native.check(lib.vtd_fpn_train_forward(C.byref(tp), n, h5, w5, c5, C.byref(st), C.c_void_p(ws.data_ptr()), C.c_void_p(p2.data_ptr()),
@@ -1078,14 +845,10 @@ def _fpn_backward_raw(taps, geom, params, ws, dp2, dscale, input_mask=0):
     """vtd_fpn_train_backward on dP2 as NHWC fp32 times dscale[0]: the ten gradients, in the order of `params`.  With `input_mask` (bit lv
     asks for C(2 + lv)) also vtd_fpn_train_backward_input: (the ten gradients, [dC2..dC5] with None for levels not asked for, their scales
     [4,2]); each dC(k) is NHWC fp32 [n,h,w,C] times its scales[lv, 0]."""
-    import ctypes as C
-    from . import _native
-    lib = _native.require()
     n, h5, w5, c5 = geom
     grads = [torch.empty_like(p) for p in params]
-    nbytes = int(lib.vtd_fpn_train_input_workspace_bytes(n, h5, w5, c5) if input_mask else lib.vtd_fpn_train_workspace_bytes(n, h5, w5, c5, 1))
-    _native.check(min(nbytes, 0), "vtd_fpn_train_workspace_bytes")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dp2.device)
+    query = ("vtd_fpn_train_input_workspace_bytes", (n, h5, w5, c5)) if input_mask else ("vtd_fpn_train_workspace_bytes", (n, h5, w5, c5, 1))
+    C, _native, lib, scratch = _native_workspace(*query, dp2.device)
     st, gst, tp = _fpn_struct(params), _fpn_struct(grads), _fpn_taps(taps)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -1154,318 +917,91 @@ class _FPNTrainFn(torch.autograd.Function):
         return (None, None, *dsrc, *grads)
 
 
-class _FPNHeadTrainFn(torch.autograd.Function):
-    """FPN -> DB head as one node: the backward hands the head's dP2 (NHWC fp32 with its power-of-two scale, as
-    vtd_dbhead_train_backward_input leaves it) straight to the FPN's backward, so the gradient never passes through an fp16 tensor or an
-    NCHW copy.  Inputs: padded taps, geom, BatchNorm mode / momentum / eps, the head's running-stat buffers, the FPN's ten tensors, the
-    head's twenty."""
+# What one run of the trunk node is, built by FeaturePyramidNetwork.forward_padded.  _TrunkPlan: `taps` the padded taps the node reads, `geom`
+# the FPN's geometry, `head` the head's (BatchNorm mode, momentum, eps, running-stat buffers), `stem` None or the stem's (geometry, eps,
+# running statistics), `blocks` a _BlockPlan for each BasicBlock from the lowest up (none: the FPN and the head alone) with `beps` their eps,
+# `bn` None or (training, momentum) for blocks on the batch-statistics entries.  _BlockPlan: the block's geometry, its running statistics,
+# its entry family and the count of its learnable tensors (9 with a downsample, 6 without)
+_TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn")
+_BlockPlan = namedtuple("_BlockPlan", "geom stats entry nlearn")
+
+
+class _TrunkFPNHeadTrainFn(torch.autograd.Function):
+    """[stem ->] [layer1 ->] [layer2 ->] [layer3 ->] [layer4 ->] FPN -> DB head as one node on padded taps, at whatever depth `plan` says.
+    Inputs: the plan, then the learnable tensors: the stem's 3 if it runs, those of the blocks from the lowest up, the FPN's 10, the head's 20.
+
+    Forward: the stem's launch on the image tap if there is one, then the blocks in order, each on the tap the one before wrote; the last
+    tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every second block.
+
+    Backward: head -> FPN -> the blocks from the top down, every gradient handed on as the kernels leave it (NHWC fp32 with its power-of-two
+    scale), never through fp16 or an NCHW copy.  The FPN's backward forms dC(k) for the levels the node computes itself (the top
+    len(blocks) / 2); dC5 goes into the last block.  Every block but the lowest forms its input gradient (a stage's first block: the strided
+    dgrad); where a stage's input is an FPN level too, the first block's dx and the FPN's dC(k) of that level are added at one power-of-two
+    scale (vtd_resblock_train_combine) before they go into the stage below.  The lowest block forms a dx only when the stem runs, and that dx
+    is the stem's dpool.  The parameter gradients of a block do not depend on whether its dx is formed, so a node gives the bits of the node
+    one stage shallower on the taps that stage produces."""
 
     @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, buffers, *params):
-        fpn_params, head_params = params[:10], params[10:]
-        n, h5, w5, _ = geom
+    def _split(plan, params):
+        """(the stem's tensors, the blocks', the FPN's, the head's) out of the node's flat parameter list."""
+        cuts = [3 if plan.stem is not None else 0]
+        for b in plan.blocks:
+            cuts.append(cuts[-1] + b.nlearn)
+        blocks = [params[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        return params[:cuts[0]], blocks, params[cuts[-1]:cuts[-1] + 10], params[cuts[-1] + 10:]
+
+    @staticmethod
+    def forward(ctx, plan, *params):
+        slearn, blearn, fpn_params, head_params = _TrunkFPNHeadTrainFn._split(plan, params)
+        n, h5, w5, _ = plan.geom
         hw = (8 * h5, 8 * w5)
-        p2p, fws = _fpn_forward_raw(taps, geom, fpn_params)
-        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, buffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.mark_non_differentiable(stats)
-        return prob, thresh, stats
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, *params = ctx.saved_tensors
-        fpn_params, head_params = params[:10], params[10:]
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        fgrads = _fpn_backward_raw(ctx.taps, ctx.geom, fpn_params, ctx.fws, dp2, dscale)
-        return (None, None, None, None, None, None, *fgrads, *hgrads)
-
-
-class _Layer4FPNHeadTrainFn(torch.autograd.Function):
-    """layer4 -> FPN -> DB head as one node on the padded taps C2..C4.  The backward hands the head's dP2 to the FPN's backward and the FPN's
-    dC5 (vtd_fpn_train_backward_input, level C5 alone) to the second block's backward, then that block's dx to the first block's, each as
-    the kernels leave it: NHWC fp32 with its power-of-two scale.  Inputs: taps, FPN geom, the head's BatchNorm mode / momentum / eps and
-    buffers, the blocks' geometries, eps and running statistics, then the learnable tensors: 9 + 6 of the blocks, the FPN's 10, the head's 20."""
-
-    @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
-        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
-        n, h5, w5, _ = geom
-        hw = (8 * h5, 8 * w5)
-        mid, bws0 = _block_forward_raw(taps[2], bgeoms[0], beps, b0, bstats[0])
-        c5, bws1 = _block_forward_raw(mid, bgeoms[1], beps, b1, bstats[1])
-        ftaps = (taps[0], taps[1], taps[2], c5)
-        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
-        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, mid, c5, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, (bws0, bws1)
-        ctx.mark_non_differentiable(stats)
-        return prob, thresh, stats
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, mid, c5, *params = ctx.saved_tensors
-        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        ftaps = (ctx.taps[0], ctx.taps[1], ctx.taps[2], c5)
-        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 8)
-        g1, dmid, dmid_scale = _block_backward_raw(mid, ctx.bgeoms[1], ctx.beps, b1, ctx.bstats[1], ctx.bws[1], c5, dtaps[3], scales[3], True)
-        g0, _, _ = _block_backward_raw(ctx.taps[2], ctx.bgeoms[0], ctx.beps, b0, ctx.bstats[0], ctx.bws[0], mid, dmid, dmid_scale, False)
-        return (None,) * 9 + (*g0, *g1, *fgrads, *hgrads)
-
-
-class _Layer4BNFPNHeadTrainFn(torch.autograd.Function):
-    """_Layer4FPNHeadTrainFn with layer4 on the vtd_resblock_bn_train_* entries: `btraining` selects batch statistics for layer4's five
-    BatchNorms (their running statistics in `bstats` are then updated in place, with `bmomentum`) or the frozen path.  The first block
-    forms no input gradient."""
-
-    @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, btraining, bmomentum, *params):
-        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
-        n, h5, w5, _ = geom
-        hw = (8 * h5, 8 * w5)
-        mid, bws0, _ = _block_bn_forward_raw(taps[2], bgeoms[0], btraining, bmomentum, beps, b0, bstats[0])
-        c5, bws1, _ = _block_bn_forward_raw(mid, bgeoms[1], btraining, bmomentum, beps, b1, bstats[1])
-        ftaps = (taps[0], taps[1], taps[2], c5)
-        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
-        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, mid, c5, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws, ctx.btraining = bgeoms, beps, bstats, (bws0, bws1), bool(btraining)
-        ctx.mark_non_differentiable(stats)
-        return prob, thresh, stats
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, mid, c5, *params = ctx.saved_tensors
-        b0, b1, fpn_params, head_params = params[:9], params[9:15], params[15:25], params[25:]
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        ftaps = (ctx.taps[0], ctx.taps[1], ctx.taps[2], c5)
-        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 8)
-        g1, dmid, dmid_scale = _block_bn_backward_raw(mid, ctx.bgeoms[1], ctx.btraining, ctx.beps, b1, ctx.bstats[1], ctx.bws[1], c5, dtaps[3],
-                                                      scales[3], True)
-        g0, _, _ = _block_bn_backward_raw(ctx.taps[2], ctx.bgeoms[0], ctx.btraining, ctx.beps, b0, ctx.bstats[0], ctx.bws[0], mid, dmid, dmid_scale,
-                                          False)
-        return (None,) * 11 + (*g0, *g1, *fgrads, *hgrads)
-
-
-class _Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
-    """layer3 -> layer4 -> FPN -> DB head as one node on the padded taps C2, C3.  The backward is _Layer4FPNHeadTrainFn's, continued: the FPN's
-    backward also forms dC4, layer4's first block forms its input gradient (the strided dgrad), the two are added at one power-of-two scale
-    (vtd_resblock_train_combine) and go into layer3's second block, whose dx goes into the first; layer3.0 forms no input gradient.
-    Inputs: taps, FPN geom, the head's BatchNorm mode / momentum / eps and buffers, the four blocks' geometries, eps and running statistics
-    (layer3.0, layer3.1, layer4.0, layer4.1), then the learnable tensors: 9 + 6 + 9 + 6 of the blocks, the FPN's 10, the head's 20."""
-
-    @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
-        blocks = (params[:9], params[9:15], params[15:24], params[24:30])
-        fpn_params, head_params = params[30:40], params[40:]
-        n, h5, w5, _ = geom
-        hw = (8 * h5, 8 * w5)
-        acts, bws, x = [], [], taps[1]
-        for i in range(4):                       # acts: layer3.0's output, C4, layer4.0's output, C5
-            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _RESBLOCK)
+        training, momentum, eps, hbuffers = plan.head
+        x, stem_saved = plan.taps[-1], ()
+        if plan.stem is not None:
+            sgeom, seps, sstats = plan.stem
+            x, idx, ctx.sws = _stem_forward_raw(plan.taps[0], sgeom, seps, slearn, sstats)
+            stem_saved = (x, idx)
+        acts, bws = [], []
+        for b, learn in zip(plan.blocks, blearn):      # acts: each block's output; every second one is a C(k)
+            x, ws = _block_forward_raw(x, b.geom, plan.beps, learn, b.stats, b.entry, plan.bn)[:2]
             acts.append(x)
             bws.append(ws)
-        ftaps = (taps[0], taps[1], acts[1], acts[3])
-        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
+        ftaps = (*plan.taps, *acts[1::2])[-4:]      # C2 .. C5: the last four (an image or pooled tap in front falls out)
+        p2p, fws = _fpn_forward_raw(ftaps, plan.geom, fpn_params)
         hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, *acts, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
+        ctx.save_for_backward(p2p, prob, thresh, *stem_saved, *acts, *params)
+        ctx.plan, ctx.hw, ctx.fws, ctx.hws, ctx.bws = plan, hw, fws, hws, tuple(bws)
         ctx.mark_non_differentiable(stats)
         return prob, thresh, stats
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, m3, c4, m4, c5, *params = ctx.saved_tensors
-        blocks = (params[:9], params[9:15], params[15:24], params[24:30])
-        fpn_params, head_params = params[30:40], params[40:]
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        ftaps = (ctx.taps[0], ctx.taps[1], c4, c5)
-        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 4 | 8)      # dC4 and dC5
-        ins = (ctx.taps[1], m3, c4, m4)
-        outs = (m3, c4, m4, c5)
-        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
-                                                         dx, _RESBLOCK)
-        g41, d, ds = bwd(3, dtaps[3], scales[3], True)
-        g40, d, ds = bwd(2, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
-        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
-        g31, d, ds = bwd(1, d, ds, True)
-        g30, _, _ = bwd(0, d, ds, False)
-        return (None,) * 9 + (*g30, *g31, *g40, *g41, *fgrads, *hgrads)
-
-
-class _Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
-    """layer2 -> layer3 -> layer4 -> FPN -> DB head as one node on the padded tap C2.  The backward is _Layer3Layer4FPNHeadTrainFn's, continued:
-    the FPN's backward also forms dC3, layer3's first block forms its input gradient (the strided dgrad), the two are added at one
-    power-of-two scale (vtd_resblock_train_combine) and go into layer2's second block, whose dx goes into the first; layer2.0 forms no
-    input gradient.  Inputs: (C2,), FPN geom, the head's BatchNorm mode / momentum / eps and buffers, the six blocks' geometries, eps and
-    running statistics (layer2.0 .. layer4.1), then the learnable tensors: 3 x (9 + 6) of the blocks, the FPN's 10, the head's 20."""
-
-    @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
-        blocks = (params[:9], params[9:15], params[15:24], params[24:30], params[30:39], params[39:45])
-        fpn_params, head_params = params[45:55], params[55:]
-        n, h5, w5, _ = geom
-        hw = (8 * h5, 8 * w5)
-        acts, bws, x = [], [], taps[0]
-        for i in range(6):                       # acts: layer2.0's output, C3, layer3.0's output, C4, layer4.0's output, C5
-            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _RESBLOCK)
-            acts.append(x)
-            bws.append(ws)
-        ftaps = (taps[0], acts[1], acts[3], acts[5])
-        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
-        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, *acts, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
-        ctx.mark_non_differentiable(stats)
-        return prob, thresh, stats
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, m2, c3, m3, c4, m4, c5, *params = ctx.saved_tensors
-        blocks = (params[:9], params[9:15], params[15:24], params[24:30], params[30:39], params[39:45])
-        fpn_params, head_params = params[45:55], params[55:]
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        ftaps = (ctx.taps[0], c3, c4, c5)
-        fgrads, dtaps, scales = _fpn_backward_raw(ftaps, ctx.geom, fpn_params, ctx.fws, dp2, dscale, 2 | 4 | 8)      # dC3, dC4 and dC5
-        ins = (ctx.taps[0], m2, c3, m3, c4, m4)
-        outs = (m2, c3, m3, c4, m4, c5)
-        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
-                                                         dx, _RESBLOCK)
-        g41, d, ds = bwd(5, dtaps[3], scales[3], True)
-        g40, d, ds = bwd(4, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
-        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
-        g31, d, ds = bwd(3, d, ds, True)
-        g30, d, ds = bwd(2, d, ds, True)                      # layer3.0's share of dC3
-        d, ds = _combine_scaled(d, ds, dtaps[1], scales[1])   # + the FPN's
-        g21, d, ds = bwd(1, d, ds, True)
-        g20, _, _ = bwd(0, d, ds, False)
-        return (None,) * 9 + (*g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
-
-
-class _Layer1Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
-    """layer1 -> layer2 -> layer3 -> layer4 -> FPN -> DB head as one node on the padded tap of the pooled stem output.  The backward is
-    _Layer2Layer3Layer4FPNHeadTrainFn's, continued: the FPN's backward also forms dC2, layer2's first block forms its input gradient (the
-    strided dgrad, 64 channels at C2's size), the two are added at one power-of-two scale (vtd_resblock_train_combine) and go into layer1's
-    second block, whose dx goes into the first; layer1.0 forms no input gradient (the stem is frozen).  Inputs: (pool,), FPN geom, the
-    head's BatchNorm mode / momentum / eps and buffers, the eight blocks' geometries, eps and running statistics (layer1.0 .. layer4.1),
-    then the learnable tensors: 6 + 6 of layer1's blocks, 3 x (9 + 6) of the others, the FPN's 10, the head's 20."""
-
-    CUTS = (0, 6, 12, 21, 27, 36, 42, 51, 57)
-
-    @classmethod
-    def _split(cls, params):
-        return tuple(params[a:b] for a, b in zip(cls.CUTS[:-1], cls.CUTS[1:])), params[57:67], params[67:]
-
-    @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, bgeoms, beps, bstats, *params):
-        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(params)
-        n, h5, w5, _ = geom
-        hw = (8 * h5, 8 * w5)
-        acts, bws, x = [], [], taps[0]
-        for i in range(8):                       # acts: layer1.0's output, C2, layer2.0's output, C3, layer3.0's, C4, layer4.0's, C5
-            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _block_entry(bgeoms[i]))
-            acts.append(x)
-            bws.append(ws)
-        ftaps = (acts[1], acts[3], acts[5], acts[7])
-        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
-        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, *acts, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
-        ctx.mark_non_differentiable(stats)
-        return prob, thresh, stats
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, m1, c2, m2, c3, m3, c4, m4, c5, *params = ctx.saved_tensors
-        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(params)
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        fgrads, dtaps, scales = _fpn_backward_raw((c2, c3, c4, c5), ctx.geom, fpn_params, ctx.fws, dp2, dscale, 1 | 2 | 4 | 8)      # dC2 .. dC5
-        ins = (ctx.taps[0], m1, c2, m2, c3, m3, c4, m4)
-        outs = (m1, c2, m2, c3, m3, c4, m4, c5)
-        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
-                                                         dx, _block_entry(ctx.bgeoms[i]))
-        g41, d, ds = bwd(7, dtaps[3], scales[3], True)
-        g40, d, ds = bwd(6, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
-        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
-        g31, d, ds = bwd(5, d, ds, True)
-        g30, d, ds = bwd(4, d, ds, True)                      # layer3.0's share of dC3
-        d, ds = _combine_scaled(d, ds, dtaps[1], scales[1])   # + the FPN's
-        g21, d, ds = bwd(3, d, ds, True)
-        g20, d, ds = bwd(2, d, ds, True)                      # layer2.0's share of dC2: 64 channels at C2's size
-        d, ds = _combine_scaled(d, ds, dtaps[0], scales[0])   # + the FPN's
-        g11, d, ds = bwd(1, d, ds, True)
-        g10, _, _ = bwd(0, d, ds, False)
-        return (None,) * 9 + (*g10, *g11, *g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
-
-
-class _StemLayer1Layer2Layer3Layer4FPNHeadTrainFn(torch.autograd.Function):
-    """stem -> layer1 -> layer2 -> layer3 -> layer4 -> FPN -> DB head as one node on the image tap.  The forward is the stem's launch
-    (csrc/stem_train.hip), then _Layer1Layer2Layer3Layer4FPNHeadTrainFn's on the pooled tap it wrote; the backward is that node's,
-    continued: layer1.0 forms its input gradient too, and that gradient (NHWC fp32 with its power-of-two scale) is the stem's dpool.  The
-    parameter gradients of a block do not depend on whether its dx is formed, so the eighty-seven gradients below the stem are the bits of
-    the node without it.  Inputs: (image tap,), FPN geom, the head's BatchNorm mode / momentum / eps and buffers, the stem's geometry, eps
-    and running statistics, the eight blocks' geometries, eps and running statistics, then the learnable tensors: the stem's 3, 6 + 6 of
-    layer1's blocks, 3 x (9 + 6) of the others, the FPN's 10, the head's 20."""
-
-    @staticmethod
-    def forward(ctx, taps, geom, training, momentum, eps, hbuffers, sgeom, seps, sstats, bgeoms, beps, bstats, *params):
-        slearn, rest = params[:3], params[3:]
-        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(rest)
-        n, h5, w5, _ = geom
-        hw = (8 * h5, 8 * w5)
-        pool, idx, sws = _stem_forward_raw(taps[0], sgeom, seps, slearn, sstats)
-        acts, bws, x = [], [], pool
-        for i in range(8):                       # acts: layer1.0's output, C2, layer2.0's output, C3, layer3.0's, C4, layer4.0's, C5
-            x, ws = _block_forward_raw(x, bgeoms[i], beps, blocks[i], bstats[i], _block_entry(bgeoms[i]))
-            acts.append(x)
-            bws.append(ws)
-        ftaps = (acts[1], acts[3], acts[5], acts[7])
-        p2p, fws = _fpn_forward_raw(ftaps, geom, fpn_params)
-        hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
-        ctx.save_for_backward(p2p, prob, thresh, pool, idx, *acts, *params)
-        ctx.taps, ctx.geom, ctx.hw, ctx.training, ctx.fws, ctx.hws = taps, geom, hw, bool(training), fws, hws
-        ctx.sgeom, ctx.seps, ctx.sstats, ctx.sws = sgeom, seps, sstats, sws
-        ctx.bgeoms, ctx.beps, ctx.bstats, ctx.bws = bgeoms, beps, bstats, tuple(bws)
-        ctx.mark_non_differentiable(stats)
-        return prob, thresh, stats
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_prob, grad_thresh, _grad_stats):
-        p2p, prob, thresh, pool, idx, m1, c2, m2, c3, m3, c4, m4, c5, *params = ctx.saved_tensors
-        slearn, rest = params[:3], params[3:]
-        blocks, fpn_params, head_params = _Layer1Layer2Layer3Layer4FPNHeadTrainFn._split(rest)
-        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, ctx.training, ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        fgrads, dtaps, scales = _fpn_backward_raw((c2, c3, c4, c5), ctx.geom, fpn_params, ctx.fws, dp2, dscale, 1 | 2 | 4 | 8)      # dC2 .. dC5
-        ins = (pool, m1, c2, m2, c3, m3, c4, m4)
-        outs = (m1, c2, m2, c3, m3, c4, m4, c5)
-        bwd = lambda i, dy, dys, dx: _block_backward_raw(ins[i], ctx.bgeoms[i], ctx.beps, blocks[i], ctx.bstats[i], ctx.bws[i], outs[i], dy, dys,  # noqa: E731
-                                                         dx, _block_entry(ctx.bgeoms[i]))
-        g41, d, ds = bwd(7, dtaps[3], scales[3], True)
-        g40, d, ds = bwd(6, d, ds, True)                      # the strided dgrad: layer4.0's share of dC4
-        d, ds = _combine_scaled(d, ds, dtaps[2], scales[2])   # + the FPN's
-        g31, d, ds = bwd(5, d, ds, True)
-        g30, d, ds = bwd(4, d, ds, True)                      # layer3.0's share of dC3
-        d, ds = _combine_scaled(d, ds, dtaps[1], scales[1])   # + the FPN's
-        g21, d, ds = bwd(3, d, ds, True)
-        g20, d, ds = bwd(2, d, ds, True)                      # layer2.0's share of dC2: 64 channels at C2's size
-        d, ds = _combine_scaled(d, ds, dtaps[0], scales[0])   # + the FPN's
-        g11, d, ds = bwd(1, d, ds, True)
-        g10, d, ds = bwd(0, d, ds, True)                      # layer1.0's input gradient: the stem's dpool
-        gs = _stem_backward_raw(ctx.taps[0], ctx.sgeom, ctx.seps, slearn, ctx.sstats, ctx.sws, pool, idx, d, ds)
-        return (None,) * 12 + (*gs, *g10, *g11, *g20, *g21, *g30, *g31, *g40, *g41, *fgrads, *hgrads)
+        plan, nb = ctx.plan, len(ctx.plan.blocks)
+        p2p, prob, thresh, *rest = ctx.saved_tensors
+        nstem = 2 if plan.stem is not None else 0
+        stem_saved, acts, params = rest[:nstem], rest[nstem:nstem + nb], rest[nstem + nb:]
+        slearn, blearn, fpn_params, head_params = _TrunkFPNHeadTrainFn._split(plan, params)
+        hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, bool(plan.head[0]), ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
+        ftaps = (*plan.taps, *acts[1::2])[-4:]
+        stages = nb // 2
+        fout = _fpn_backward_raw(ftaps, plan.geom, fpn_params, ctx.fws, dp2, dscale, sum(8 >> j for j in range(stages)))      # dC5 down
+        if not plan.blocks:
+            return (None, *fout, *hgrads)
+        fgrads, dtaps, scales = fout
+        ins = ((stem_saved[0] if plan.stem is not None else plan.taps[-1]), *acts[:-1])
+        bgrads, d, ds = [None] * nb, dtaps[3], scales[3]
+        for i in reversed(range(nb)):
+            b, want_dx = plan.blocks[i], i > 0 or plan.stem is not None
+            bgrads[i], d, ds = _block_backward_raw(ins[i], b.geom, plan.beps, blearn[i], b.stats, ctx.bws[i], acts[i], d, ds, want_dx, b.entry, plan.bn)
+            level = 3 - stages + i // 2      # the FPN level of this block's stage's input: C(2 + level), none below C2
+            if want_dx and i % 2 == 0 and level >= 0:
+                d, ds = _combine_scaled(d, ds, dtaps[level], scales[level])      # the stage's share of dC(k) + the FPN's
+        sgrads = ()
+        if plan.stem is not None:      # layer1.0's input gradient is the stem's dpool
+            sgeom, seps, sstats = plan.stem
+            sgrads = _stem_backward_raw(plan.taps[0], sgeom, seps, slearn, sstats, ctx.sws, *stem_saved, d, ds)
+        return (None, *sgrads, *(g for gs in bgrads for g in gs), *fgrads, *hgrads)
 
 
 def pack_tap(feature):
@@ -1564,11 +1100,16 @@ class DBHead(nn.Module):
                              f"{tuple(feats.shape) if torch.is_tensor(feats) else type(feats).__name__}")
         bns, params, buffers = self._train_operands(feats.device)
         prob, thresh, _ = _DBHeadTrainFn.apply(feats, src, (int(H), int(W)), self.training, bns[0].momentum, bns[0].eps, tuple(buffers), *params)
+        self._batches_seen(bns)
+        return {"probability": prob, "threshold": thresh}
+
+    def _batches_seen(self, bns):
+        """After a forward on the training kernels, which update the running statistics themselves: num_batches_tracked + 1 on the four
+        BatchNorms in training mode, as torch's modules count."""
         if self.training:
             with torch.no_grad():
                 for bn in bns:
                     bn.num_batches_tracked.add_(1)
-        return {"probability": prob, "threshold": thresh}
 
 
 class _EngineOwner:
@@ -1705,38 +1246,23 @@ class DBNet(_EngineOwner, nn.Module):
         elif trainable == "head+fpn":
             for p in self.backbone.parameters():
                 p.requires_grad_(False)
-        elif trainable == "head+fpn+layer4":
-            for i in range(7):
+        elif trainable in _STAGE_MODES:
+            first = self._first_trained()
+            for i in range(8):
                 for p in self.backbone[i].parameters():
-                    p.requires_grad_(False)
-            for p in list(self.backbone[7].parameters()) + list(self.fpn.parameters()) + list(self.head.parameters()):
+                    p.requires_grad_(i >= first)
+            for p in list(self.fpn.parameters()) + list(self.head.parameters()):
                 p.requires_grad_(True)
-        elif trainable == "head+fpn+layer4+layer3":
-            for i in range(6):
-                for p in self.backbone[i].parameters():
-                    p.requires_grad_(False)
-            for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
-                for p in m.parameters():
-                    p.requires_grad_(True)
-        elif trainable == "head+fpn+layer4+layer3+layer2":
-            for i in range(5):
-                for p in self.backbone[i].parameters():
-                    p.requires_grad_(False)
-            for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
-                for p in m.parameters():
-                    p.requires_grad_(True)
-        elif trainable == "head+fpn+layer4+layer3+layer2+layer1":
-            for i in range(4):
-                for p in self.backbone[i].parameters():
-                    p.requires_grad_(False)
-            for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
-                for p in m.parameters():
-                    p.requires_grad_(True)
         elif trainable == _BACKBONE_MODE:
             for p in self.parameters():
                 p.requires_grad_(True)
         self._head_versions = None
         return self
+
+    def _first_trained(self):
+        """The first backbone module a stage mode trains: the mode at position k - 1 of _STAGE_MODES trains the top k residual stages,
+        backbone.(8 - k) .. backbone.7, over the frozen backbone.0 .. backbone.(7 - k)."""
+        return 8 - (_STAGE_MODES.index(self.trainable) + 1)
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
@@ -1756,14 +1282,11 @@ class DBNet(_EngineOwner, nn.Module):
         with self._engine_lock:
             # keyed on the backbone tensors' versions only (load_state_dict bumps them): FPN and head updates never rebuild it
             frozen = self.backbone.state_dict()
-            if self.trainable == "head+fpn+layer4":      # the frozen tensors only: the engine's C5 (stale layer4 weights) is never read
-                frozen = {k: v for k, v in frozen.items() if not k.startswith("7.")}
-            elif self.trainable == "head+fpn+layer4+layer3":      # likewise: the engine's C4 and C5 are never read
-                frozen = {k: v for k, v in frozen.items() if not k.startswith(("6.", "7."))}
-            elif self.trainable == "head+fpn+layer4+layer3+layer2":      # likewise: only the engine's C2 is read
-                frozen = {k: v for k, v in frozen.items() if not k.startswith(("5.", "6.", "7."))}
-            elif self.trainable == "head+fpn+layer4+layer3+layer2+layer1":      # likewise: only the pooled stem output is read (forward_pool)
-                frozen = {k: v for k, v in frozen.items() if not k.startswith(("4.", "5.", "6.", "7."))}
+            if self.trainable in _STAGE_MODES:
+                # the frozen tensors only: what the engine computes from the trained stages (stale weights) is never read -- its C5 in the
+                # layer4 mode, C4 and C5 in the layer3 mode, all but C2 in the layer2 mode, all but the pooled stem output in the layer1 mode
+                trained = tuple(f"{i}." for i in range(self._first_trained(), 8))
+                frozen = {k: v for k, v in frozen.items() if not k.startswith(trained)}
             version = tuple(t._version for t in frozen.values())
             te = self.__dict__.get("_trunk_engine")
             if te is None or self.__dict__.get("_trunk_version") != version:
@@ -1810,14 +1333,8 @@ class DBNet(_EngineOwner, nn.Module):
             if self.training:
                 if self.trainable == _BACKBONE_MODE:
                     return self._forward_train_backbone(x)
-                if self.trainable == "head+fpn+layer4+layer3+layer2+layer1":
-                    return self._forward_train_head_fpn_layer4_layer3_layer2_layer1(x)
-                if self.trainable == "head+fpn+layer4+layer3+layer2":
-                    return self._forward_train_head_fpn_layer4_layer3_layer2(x)
-                if self.trainable == "head+fpn+layer4+layer3":
-                    return self._forward_train_head_fpn_layer4_layer3(x)
-                if self.trainable == "head+fpn+layer4":
-                    return self._forward_train_head_fpn_layer4(x)
+                if self.trainable in _STAGE_MODES:
+                    return self._forward_train_trunk(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
             # the inference engine packs the head on the host: rebuild it after an optimizer step (parameter versions) or a
             # train-mode forward (running statistics, mark_dirty)
@@ -1854,68 +1371,28 @@ class DBNet(_EngineOwner, nn.Module):
         return out
 
 
-    def _forward_train_head_fpn_layer4(self, x):
-        frozen = [n for i in range(7) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+    def _forward_train_trunk(self, x):
+        """The train-mode forward of the stage modes: the frozen trunk engine up to the lowest trained stage, then the trained stages, the FPN and
+        the head as one autograd node."""
+        first = self._first_trained()
+        k = 8 - first      # the stages that train: layer(5 - k) .. layer4
+        frozen = [n for i in range(first) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
         if frozen:
-            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4'): {frozen[0]} requires grad, but backward below layer4 is not "
-                               "implemented; only layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. backbone.6)")
-        for m in (self.backbone[7], self.fpn, self.head):
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below layer{5 - k} is not "
+                               f"implemented; only {', '.join(f'layer{j}' for j in range(5 - k, 5))}, the FPN and the DB head train (set "
+                               f"requires_grad_(False) on backbone.0 .. backbone.{first - 1})")
+        for m in (*(self.backbone[i] for i in range(first, 8)), self.fpn, self.head):
             if not next(m.parameters()).is_cuda:
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = self.trunk_engine().forward_trunk(x)   # C5 of the engine is computed from the weights it was built with: ignored
-        if getattr(self, "trunk_bn", "frozen") == "batch":   # layer4's running statistics move too; mark_dirty below covers them
-            out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7], trunk_batch_stats=True)
-        else:
-            out = self.fpn.forward_padded(taps[:3], head=self.head, layer4=self.backbone[7])
+        # the engine's taps above the lowest trained stage's input come from the weights it was built with and are ignored; with every stage
+        # trained the stem alone runs (forward_pool).  New tensors per call: autograd may keep them
+        engine = self.trunk_engine()
+        taps = [engine.forward_pool(x)] if k == 4 else engine.forward_trunk(x)[:4 - k]
+        stages = {f"layer{j}": self.backbone[3 + j] for j in range(5 - k, 5)}
+        # trunk_bn="batch" is the layer4 mode's alone (set_trainable): layer4's running statistics move too; mark_dirty below covers them
+        out = self.fpn.forward_padded(taps, head=self.head, trunk_batch_stats=getattr(self, "trunk_bn", "frozen") == "batch", **stages)
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
-
-
-    def _forward_train_head_fpn_layer4_layer3(self, x):
-        frozen = [n for i in range(6) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
-        if frozen:
-            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4+layer3'): {frozen[0]} requires grad, but backward below layer3 is not "
-                               "implemented; only layer3, layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. "
-                               "backbone.5)")
-        for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
-            if not next(m.parameters()).is_cuda:
-                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = self.trunk_engine().forward_trunk(x)   # C4 and C5 of the engine come from the weights it was built with: ignored
-        out = self.fpn.forward_padded(taps[:2], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6])
-        self.mark_dirty()   # the kernels updated the head's running statistics in place
-        return out
-
-
-    def _forward_train_head_fpn_layer4_layer3_layer2(self, x):
-        frozen = [n for i in range(5) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
-        if frozen:
-            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4+layer3+layer2'): {frozen[0]} requires grad, but backward below layer2 is not "
-                               "implemented; only layer2, layer3, layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. "
-                               "backbone.4)")
-        for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
-            if not next(m.parameters()).is_cuda:
-                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = self.trunk_engine().forward_trunk(x)   # C3, C4 and C5 of the engine come from the weights it was built with: ignored
-        out = self.fpn.forward_padded(taps[:1], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5])
-        self.mark_dirty()   # the kernels updated the head's running statistics in place
-        return out
-
-
-    def _forward_train_head_fpn_layer4_layer3_layer2_layer1(self, x):
-        frozen = [n for i in range(4) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
-        if frozen:
-            raise RuntimeError(f"DBNet(trainable='head+fpn+layer4+layer3+layer2+layer1'): {frozen[0]} requires grad, but backward below layer1 is not "
-                               "implemented; only layer1 .. layer4, the FPN and the DB head train (set requires_grad_(False) on backbone.0 and "
-                               "backbone.1)")
-        for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
-            if not next(m.parameters()).is_cuda:
-                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        pool = self.trunk_engine().forward_pool(x)   # the stem alone runs: the engine's stages come from the weights it was built with
-        out = self.fpn.forward_padded([pool], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5],
-                                      layer1=self.backbone[4])
-        self.mark_dirty()   # the kernels updated the head's running statistics in place
-        return out
-
 
     def _forward_train_backbone(self, x):
         if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
