@@ -366,6 +366,30 @@ int vtd_resblock_bn_train_backward(const void* x_dev, int n, int h_in, int w_in,
                                    int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                    const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- The same with layer3's width too (csrc/resblock_bn_train.hip, the same launch functions): vtd_block_bn_train_* take the arguments of
+ * vtd_resblock_bn_train_*, one for one, and build four geometries: (cin 128, width 256, stride 2, even h_in and w_in, with downsample),
+ * (cin 256, width 256, stride 1), (cin 256, width 512, stride 2, even extents, with downsample) and (cin 512, width 512, stride 1); every
+ * other geometry is refused with -3501.  training = 0 hands the call to vtd_resblock_train_forward / _backward (the frozen path with the
+ * strided dx): their bits.  For the two width-512 geometries y, the statistics, the running update, every parameter gradient and the
+ * stride-1 dx are the bits of vtd_resblock_bn_train_*.
+ * The per-channel reductions of a 256-wide z (the statistics' partials and the backward's s1, s2): 64 threads x 4 channels cover the width,
+ * so the 256 threads of a workgroup are four quarters of its r rows.  Quarter k sums rows ceil(k r / 4) .. ceil((k + 1) r / 4) - 1 in row
+ * order in fp64; the workgroup's partial is (q0 + q1) + (q2 + q3); the workgroups -- min(256, ceil(n h w / 256)) of ceil(n h w / workgroups)
+ * consecutive rows, as at width 512 -- are combined in workgroup order (Chan's combination for the statistics).  Shape-only.
+ * dx_dev on a stride-2 block is accepted: dz1 goes to the even positions of a zeroed ring-padded plane of the input's extent, the stride-1
+ * 3x3 dgrad runs over it on the raw conv1 weights (rotated, transposed), and ds^T(dz_d) -- a 1x1 GEMM of the downsample BatchNorm's own dz on
+ * the transposed raw downsample weights -- is added at the even (row, column) positions after the power-of-two factor sc2 sc1 / scd that
+ * brings dz_d's scale to dz1's (exact).  The parameter gradients do not depend on whether dx is asked for.  The statistics are still not
+ * fused into the convolution's epilogue.  No atomics, shape-only grids: bitwise repeatable.
+ * Errors, before any launch: -3501 (argument / unsupported geometry / training outside {0, 1} / training = 1 with n h w < 2 / momentum
+ * outside [0, 1] / dx_dev without dxscale_dev), -3502 (alignment). */
+int64_t vtd_block_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_block_bn_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               int training, float momentum, float eps, void* workspace_dev, void* y_dev, float* stats_dev, vtd_stream stream);
+int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
 /* ---- ResNet stem training with frozen-statistics BatchNorm (csrc/stem_train.hip): pool = maxpool3x3/s2/p1(relu(bn(conv7x7/s2/p3(x)))) on an
  * image x [n,3,height,width]; height and width are the image's, even and at least 2 (the product's 640 is not built in).  hc x wc = height / 2
  * x width / 2 is the conv map, hp x wp = ceil(hc / 2) x ceil(wc / 2) the pooled map.  The running statistics normalise and are never written;

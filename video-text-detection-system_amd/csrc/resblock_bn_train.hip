@@ -1,15 +1,20 @@
 // ResNet BasicBlock training with batch-statistics BatchNorm (torch's train() mode: the statistics of the batch normalise, the running
-// statistics are updated in place), forward and backward, for the two blocks of ResNet-18's layer4: (256 -> 512, stride 2, downsample) and
-// (512 -> 512, stride 1).  W = 512 throughout.  With training = 0 the entries hand the call to the frozen-statistics path
-// (resblock_train.hip, vtd_basicblock_train_*) unchanged.
+// statistics are updated in place), forward and backward, for the blocks of ResNet-18's layer3 and layer4: (128 -> 256, stride 2,
+// downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W below is the block's width (256 or
+// 512), a template argument of every kernel.  Two entry families share the launch functions, told apart by their error base as in
+// resblock_train.hip: vtd_resblock_bn_train_* (-3400: layer4's two geometries, no input gradient of the stride-2 block, -3403) and
+// vtd_block_bn_train_* (-3500: the four geometries, the input gradient of either stride).  With training = 0 the entries hand the call to
+// the frozen-statistics path (resblock_train.hip) unchanged: the first family to vtd_basicblock_train_*, the second to vtd_resblock_train_*.
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
 //
 // Forward, per convolution + BatchNorm pair (conv1 / bn1, the downsample, conv2 / bn2):
 //   pack             the raw weights -> fp16 GEMM panel [W][ksz^2 cin] (k = tap * cin + ci); no fold: gamma rstd is not known yet
 //   conv             conv_igemm.hip with EPI_OUT_F32 and a zero bias: z [M][W] fp32, kept in the workspace for the backward
-//   stats partial    workgroup g owns rows g per .. g per + per - 1 (per = ceil(M / G), G = min(256, ceil(M / 256))).  Thread t owns channels
-//                    4 (t % 128) .. + 3 with 16-byte loads; t < 128 sums the first ceil(r / 2) of the workgroup's r rows in row order, t >= 128
-//                    the rest; sums of z and z^2 in fp64, lower + upper, then (count, mean, M2) per channel
+//   stats partial    workgroup g owns rows g per .. g per + per - 1 (per = ceil(M / G), G = min(256, ceil(M / 256))).  W / 4 threads cover the
+//                    width, 4 channels each with 16-byte loads, so the 256 threads are P = 1024 / W parts of the workgroup's r rows: part k
+//                    sums rows ceil(k r / P) .. ceil((k + 1) r / P) - 1 in row order, sums of z and z^2 in fp64.
+//                    W = 512: two halves, lower + upper.  W = 256: four quarters, (q0 + q1) + (q2 + q3) -- the rule of rb_reduce64_kernel.
+//                    Then (count, mean, M2) per channel
 //   stats finish     one thread per channel: Chan's combination of the partials in workgroup order (fp64) -> mu, biased sigma^2; the running
 //                    values mean <- (1 - m) mean + m mu, var <- (1 - m) var + m sigma^2 M / (M - 1); table {mu, rstd, gamma, beta} [4][W]
 //   apply            relu(((z - mu) rstd) gamma + beta [+ id]) -> ring-padded fp16 tap; the downsample's has no ReLU.  One thread = 8 channels
@@ -23,7 +28,14 @@
 //   wgrad<3>         G[c][k] = sum_m dz[m][c] x[m][k] on wgrad_mfma.h, min(8, ceil(M / 4096)) slabs; dW = the slabs summed in order in fp64
 //                    with the scale undone: dz carries gamma rstd, no factor follows
 //   dgrad            da1 = conv2^T(dz2): conv_igemm.hip on the raw weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
-//   dx (stride 1)    conv1^T(dz1) the same way, plus g2 brought to the same scale.  The stride-2 block forms no input gradient here
+//   dx (stride 1)    conv1^T(dz1) the same way, plus g2 brought to the same scale
+//   dx (stride 2)    (vtd_block_bn_train_* only) the construction of resblock_train.hip on the batch-statistics quantities: dz1 goes to the even
+//                    positions of a zeroed ring-padded plane of the input's 2h x 2w pixels (`form` with dil = 2), the stride-1 3x3 dgrad runs
+//                    over that plane on the raw conv1 weights, rotated and transposed.  The downsample's transpose is a 1x1 GEMM of dz_d, the
+//                    downsample BatchNorm's own dz (not g2, not dz2: each pair has its own statistics), on the transposed raw downsample
+//                    weights; it runs right after the downsample pair's `form`, into a buffer of its own, because the dz planes are reused
+//                    by bn1.  dz_d carries its own power-of-two multiplier scd[2]; the product is added at the even (row, column) positions
+//                    times sc2[2] sc1[2] / scd[2], which brings it to dz1's scale exactly
 // Nothing divides by gamma or sigma.  No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
 #include "resblock_common.h"
 
@@ -35,27 +47,36 @@ int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int c
                                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
                                    float* dx, float* dxscale, hipStream_t s);
 
+int64_t vtd_resblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
+                                void* y, hipStream_t s);
+int vtd_launch_resblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                 const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                 float* dx, float* dxscale, hipStream_t s);
+
 namespace {
 
 constexpr int BT_THREADS = RB_THREADS;
-constexpr int BT_W = 512;          // the block's width: layer4's
 constexpr int BT_MAX_RED = 256;
-constexpr int BT_ERR = -3400;
+// error bases: the vtd_resblock_bn_train_* entries (layer4's two geometries, no strided dx) answer -3401 / -3402 / -3403, the
+// vtd_block_bn_train_* entries (four geometries) -3501 / -3502
+constexpr int BT_LEGACY = -3400, BT_GENERAL = -3500;
 
 typedef double doublex4 __attribute__((ext_vector_type(4)));
 
 struct Geo {
-    int n, hin, win, cin, stride, h, w;
+    int n, hin, win, cin, width, stride, h, w;
     int64_t m;
     bool ds;
     int red;       // reduce workgroups
     int64_t per;   // rows of each
 };
 
-bool make_geo(int n, int hin, int win, int cin, int width, int stride, Geo& g) {
-    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096 || width != BT_W) return false;
-    if (!((cin == 256 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == 512 && stride == 1))) return false;
-    g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.stride = stride; g.h = hin / stride; g.w = win / stride;
+bool make_geo(int n, int hin, int win, int cin, int width, int stride, int base, Geo& g) {
+    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096) return false;
+    if (width != 512 && (base == BT_LEGACY || width != 256)) return false;
+    if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
+    g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.width = width; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w;
     g.ds = stride == 2;
     int64_t r = (g.m + 255) / 256;
@@ -66,13 +87,13 @@ bool make_geo(int n, int hin, int win, int cin, int width, int stride, Geo& g) {
 
 // the workspace of a training = 1 forward.  tab: {mu, rstd, gamma, beta} [4][W] per pair (bn1, bn2, the downsample's)
 struct FwdLayout { int64_t a1, id, z1, z2, zd, w1, w2, wd, zero, part, tab, total; };
-struct BwdLayout { int64_t g2, g1, dzh, dzp, wt, zero, part, pmax, coef, sc, slab, total; };
+struct BwdLayout { int64_t g2, g1, dzh, dzp, wt, zero, part, pmax, coef, sc, slab, zp, wdt, dst, total; };
 
 FwdLayout fwd_layout(const Geo& g) {
     FwdLayout L;
     int64_t o = 0;
     auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
-    const int64_t W = BT_W, pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * W * 2, zb = g.m * W * 4;
+    const int64_t W = g.width, pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * W * 2, zb = g.m * W * 4;
     L.a1 = take(pad); L.id = take(g.ds ? pad : 0);
     L.z1 = take(zb); L.z2 = take(zb); L.zd = take(g.ds ? zb : 0);
     L.w1 = take(W * 9 * g.cin * 2); L.w2 = take(W * 9 * W * 2); L.wd = take(g.ds ? W * g.cin * 2 : 0);
@@ -83,11 +104,13 @@ FwdLayout fwd_layout(const Geo& g) {
     return L;
 }
 
-BwdLayout bwd_layout(const Geo& g) {
+// `strided`: room for the stride-2 block's input gradient (the zero-inserted plane, the downsample's transposed panel and ds^T(dz_d)), at
+// the end
+BwdLayout bwd_layout(const Geo& g, bool strided) {
     BwdLayout L;
     int64_t o = 0;
     auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
-    const int64_t W = BT_W, pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * W * 2;
+    const int64_t W = g.width, pad = (int64_t)g.n * (g.h + 2) * (g.w + 2) * W * 2;
     L.g2 = take(g.m * W * 4); L.g1 = take(g.m * W * 4);
     L.dzh = take(g.m * W * 2); L.dzp = take(pad);
     L.wt = take(W * 9 * W * 2);
@@ -96,6 +119,9 @@ BwdLayout bwd_layout(const Geo& g) {
     L.coef = take(3 * W * 4);
     L.sc = take(3 * 4 * 4);
     L.slab = take((int64_t)wg_slabs(g.m) * W * 9 * W * 4);
+    L.zp = take(strided ? (int64_t)g.n * (g.hin + 2) * (g.win + 2) * W * 2 : 0);
+    L.wdt = take(strided ? (int64_t)g.cin * W * 2 : 0);
+    L.dst = take(strided ? g.m * g.cin * 4 : 0);
     L.total = o;
     return L;
 }
@@ -105,51 +131,65 @@ __device__ __forceinline__ float nmax(float m, float a) { return a > m || a != a
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------
 // wp [W][taps cin], k = tap * cin + ci: half(w[co][ci][tap]); zero[W] = 0 (the convolutions' bias row)
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_pack_kernel(const float* w, int cin, int taps, half_t* wp, float* zero) {
     const int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x;
     const int K = taps * cin;
-    if (i < (int64_t)BT_W * K) {
+    if (i < (int64_t)W * K) {
         const int co = (int)(i / K), k = (int)(i - (int64_t)co * K), tap = k / cin, ci = k - tap * cin;
         wp[i] = (half_t)w[((int64_t)co * cin + ci) * taps + tap];
-    } else if (zero && i < (int64_t)BT_W * K + BT_W) {
-        zero[i - (int64_t)BT_W * K] = 0.f;
+    } else if (zero && i < (int64_t)W * K + W) {
+        zero[i - (int64_t)W * K] = 0.f;
     }
 }
 
-// the rows [lo, hi) of thread t in workgroup `blk`: the lower half of the workgroup's rows for t < 128, the upper half for t >= 128
-__device__ __forceinline__ void bt_rows(int64_t rows, int64_t per, int hf, int64_t& m0, int64_t& m1, int64_t& lo, int64_t& hi) {
+// the rows [lo, hi) of part `grp` of the P = 1024 / W parts of workgroup `blk`'s r rows: ceil(grp r / P) .. ceil((grp + 1) r / P) - 1.  W = 512:
+// the lower half (the first ceil(r / 2) rows) and the upper; W = 256: four quarters
+template <int W>
+__device__ __forceinline__ void bt_rows(int64_t rows, int64_t per, int grp, int64_t& m0, int64_t& m1, int64_t& lo, int64_t& hi) {
+    constexpr int P = 4 * BT_THREADS / W;
     m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows;
     m1 = m0 + per < rows ? m0 + per : rows;
-    const int64_t mid = m0 + (m1 - m0 + 1) / 2;
-    lo = hf ? mid : m0;
-    hi = hf ? m1 : mid;
+    const int64_t r = m1 - m0;
+    lo = m0 + (grp * r + P - 1) / P;
+    hi = m0 + ((grp + 1) * r + P - 1) / P;
 }
 
-// z [rows][W] fp32 -> part[g][c] = {count, mean, M2} (fp64).  LDS [value][thread]: consecutive lanes, consecutive doubles
+// the parts of one workgroup, part 0 in registers and the others in LDS [part - 1][value][lane]: lower + upper for two parts,
+// (q0 + q1) + (q2 + q3) for four
+template <int P, int L>
+__device__ __forceinline__ double bt_join(double own, double (*sh)[8][L], int v, int j) {
+    if (P == 2) return own + sh[0][v][j];
+    return (own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j]);
+}
+
+// z [rows][W] fp32 -> part[g][c] = {count, mean, M2} (fp64).  LDS [part][value][lane]: consecutive lanes, consecutive doubles
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_stats_partial_kernel(const float* z, int64_t rows, int64_t per, double* part) {
-    const int t = threadIdx.x, j = t & 127, hf = t >> 7;
+    constexpr int L = W / 4, P = BT_THREADS / L;
+    const int t = threadIdx.x, j = t % L, grp = t / L;
     int64_t m0, m1, lo, hi;
-    bt_rows(rows, per, hf, m0, m1, lo, hi);
+    bt_rows<W>(rows, per, grp, m0, m1, lo, hi);
     double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
     for (int64_t m = lo; m < hi; ++m) {
-        const floatx4 v = *(const floatx4*)(z + m * BT_W + 4 * j);
+        const floatx4 v = *(const floatx4*)(z + m * W + 4 * j);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const double a = (double)v[e]; s[e] += a; q[e] += a * a; }
     }
-    __shared__ double sh[8][128];
-    if (hf) {
+    __shared__ double sh[P - 1][8][L];
+    if (grp) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { sh[e][j] = s[e]; sh[4 + e][j] = q[e]; }
+        for (int e = 0; e < 4; ++e) { sh[grp - 1][e][j] = s[e]; sh[grp - 1][4 + e][j] = q[e]; }
     }
     __syncthreads();
-    if (!hf) {
+    if (!grp) {
         const double cnt = (double)(m1 - m0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const double S = s[e] + sh[e][j], Q = q[e] + sh[4 + e][j];
+            const double S = bt_join<P, L>(s[e], sh, e, j), Q = bt_join<P, L>(q[e], sh, 4 + e, j);
             const double mean = cnt > 0 ? S / cnt : 0.0;
-            double* o = part + ((int64_t)blockIdx.x * BT_W + 4 * j + e) * 3;
+            double* o = part + ((int64_t)blockIdx.x * W + 4 * j + e) * 3;
             o[0] = cnt; o[1] = mean; o[2] = cnt > 0 ? fmax(Q - S * mean, 0.0) : 0.0;
         }
     }
@@ -157,12 +197,13 @@ __global__ __launch_bounds__(BT_THREADS) void bt_stats_partial_kernel(const floa
 
 // One thread per channel: Chan's combination of the partials in workgroup order (fp64), torch's running-statistics update, the table
 // {mu, rstd, gamma, beta} and (optionally) stats_out = {mu, sigma^2} [2][W]
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_stats_finish_kernel(const double* part, int G, const float* gam, const float* bet, float* rmean, float* rvar,
                                                                      float momentum, float eps, float* tab, float* stats_out) {
     const int c = blockIdx.x * BT_THREADS + threadIdx.x;
     double n = 0.0, mu = 0.0, m2 = 0.0;
     for (int g = 0; g < G; ++g) {
-        const double* q = part + ((int64_t)g * BT_W + c) * 3;
+        const double* q = part + ((int64_t)g * W + c) * 3;
         const double nb = q[0];
         if (nb <= 0.0) continue;
         const double tot = n + nb, d = q[1] - mu;
@@ -174,32 +215,33 @@ __global__ __launch_bounds__(BT_THREADS) void bt_stats_finish_kernel(const doubl
     rmean[c] = (float)((1.0 - (double)momentum) * (double)rmean[c] + (double)momentum * mu);
     rvar[c] = (float)((1.0 - (double)momentum) * (double)rvar[c] + (double)momentum * unbiased);
     tab[c] = (float)mu;
-    tab[BT_W + c] = (float)(1.0 / sqrt(var + (double)eps));
-    tab[2 * BT_W + c] = gam[c];
-    tab[3 * BT_W + c] = bet[c];
+    tab[W + c] = (float)(1.0 / sqrt(var + (double)eps));
+    tab[2 * W + c] = gam[c];
+    tab[3 * W + c] = bet[c];
     if (stats_out) {
         stats_out[c] = (float)mu;
-        stats_out[BT_W + c] = (float)var;
+        stats_out[W + c] = (float)var;
     }
 }
 
 // out (padded tap) = [relu](((z - mu) rstd) gamma + beta [+ res]); res is a padded tap of the output's extents.  One thread = 8 channels
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_apply_kernel(const float* z, int64_t rows, const float* tab, const half_t* res, int relu, int H, int Wd,
                                                               half_t* out) {
     const int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x;
-    if (i >= rows * (BT_W / 8)) return;
-    const int c0 = (int)(i & 63) * 8;
-    const int64_t m = i >> 6;
+    if (i >= rows * (W / 8)) return;
+    const int c0 = (int)(i % (W / 8)) * 8;
+    const int64_t m = i / (W / 8);
     const int HW = H * Wd, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
-    const int64_t off = (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * BT_W + c0;
+    const int64_t off = (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * W + c0;
     half8 rv = {0, 0, 0, 0, 0, 0, 0, 0};
     if (res) rv = *(const half8*)(res + off);
     half8 h;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const floatx4 v = *(const floatx4*)(z + i * 8 + 4 * k);
-        const floatx4 mu = *(const floatx4*)(tab + c0 + 4 * k), rs = *(const floatx4*)(tab + BT_W + c0 + 4 * k);
-        const floatx4 gm = *(const floatx4*)(tab + 2 * BT_W + c0 + 4 * k), bt = *(const floatx4*)(tab + 3 * BT_W + c0 + 4 * k);
+        const floatx4 mu = *(const floatx4*)(tab + c0 + 4 * k), rs = *(const floatx4*)(tab + W + c0 + 4 * k);
+        const floatx4 gm = *(const floatx4*)(tab + 2 * W + c0 + 4 * k), bt = *(const floatx4*)(tab + 3 * W + c0 + 4 * k);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float a = ((v[e] - mu[e]) * rs[e]) * gm[e] + bt[e];
@@ -213,18 +255,20 @@ __global__ __launch_bounds__(BT_THREADS) void bt_apply_kernel(const float* z, in
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------------
 // g, z [rows][W] fp32 -> part[blk][0][c] = sum g, part[blk][1][c] = sum g xh (fp64), pmax[blk][0][c] = max |g|, pmax[blk][1][c] = max |xh|,
-// xh = (z - mu) rstd as the forward formed it.  Rows and threads as bt_stats_partial_kernel
+// xh = (z - mu) rstd as the forward formed it.  Rows, threads and the order of the parts as bt_stats_partial_kernel
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_bwd_reduce_kernel(const float* g, const float* z, const float* tab, int64_t rows, int64_t per, double* part,
                                                                    float* pmax) {
-    const int t = threadIdx.x, j = t & 127, hf = t >> 7;
+    constexpr int L = W / 4, P = BT_THREADS / L;
+    const int t = threadIdx.x, j = t % L, grp = t / L;
     int64_t m0, m1, lo, hi;
-    bt_rows(rows, per, hf, m0, m1, lo, hi);
-    const floatx4 mu = *(const floatx4*)(tab + 4 * j), rs = *(const floatx4*)(tab + BT_W + 4 * j);
+    bt_rows<W>(rows, per, grp, m0, m1, lo, hi);
+    const floatx4 mu = *(const floatx4*)(tab + 4 * j), rs = *(const floatx4*)(tab + W + 4 * j);
     double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
     floatx4 mg = {0.f, 0.f, 0.f, 0.f}, mx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int64_t m = lo; m < hi; ++m) {
-        const floatx4 gv = *(const floatx4*)(g + m * BT_W + 4 * j), zv = *(const floatx4*)(z + m * BT_W + 4 * j);
+        const floatx4 gv = *(const floatx4*)(g + m * W + 4 * j), zv = *(const floatx4*)(z + m * W + 4 * j);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float xh = (zv[e] - mu[e]) * rs[e];
@@ -234,24 +278,29 @@ __global__ __launch_bounds__(BT_THREADS) void bt_bwd_reduce_kernel(const float* 
             mx[e] = nmax(mx[e], fabsf(xh));
         }
     }
-    __shared__ double sh[8][128];
-    __shared__ float shm[8][128];
-    if (hf) {
+    __shared__ double sh[P - 1][8][L];
+    __shared__ float shm[P - 1][8][L];
+    if (grp) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { sh[e][j] = s1[e]; sh[4 + e][j] = s2[e]; shm[e][j] = mg[e]; shm[4 + e][j] = mx[e]; }
+        for (int e = 0; e < 4; ++e) {
+            sh[grp - 1][e][j] = s1[e]; sh[grp - 1][4 + e][j] = s2[e];
+            shm[grp - 1][e][j] = mg[e]; shm[grp - 1][4 + e][j] = mx[e];
+        }
     }
     __syncthreads();
-    if (!hf) {
+    if (!grp) {
         doublex4 o1, o2;
         floatx4 p1, p2;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            o1[e] = s1[e] + sh[e][j]; o2[e] = s2[e] + sh[4 + e][j];
-            p1[e] = nmax(mg[e], shm[e][j]); p2[e] = nmax(mx[e], shm[4 + e][j]);
+            o1[e] = bt_join<P, L>(s1[e], sh, e, j); o2[e] = bt_join<P, L>(s2[e], sh, 4 + e, j);
+            p1[e] = mg[e]; p2[e] = mx[e];
+#pragma unroll
+            for (int k = 0; k < P - 1; ++k) { p1[e] = nmax(p1[e], shm[k][e][j]); p2[e] = nmax(p2[e], shm[k][4 + e][j]); }
         }
-        const int64_t b = (int64_t)blockIdx.x * 2 * BT_W + 4 * j;
-        *(doublex4*)(part + b) = o1; *(doublex4*)(part + b + BT_W) = o2;
-        *(floatx4*)(pmax + b) = p1; *(floatx4*)(pmax + b + BT_W) = p2;
+        const int64_t b = (int64_t)blockIdx.x * 2 * W + 4 * j;
+        *(doublex4*)(part + b) = o1; *(doublex4*)(part + b + W) = o2;
+        *(floatx4*)(pmax + b) = p1; *(floatx4*)(pmax + b + W) = p2;
     }
 }
 
@@ -259,24 +308,25 @@ __global__ __launch_bounds__(BT_THREADS) void bt_bwd_reduce_kernel(const float* 
 // undone; coef = {gamma rstd, s1 / M, s2 / M} [3][W] at the incoming scale; out_sc = {total scale, 1 / total, this stage's multiplier, 0}:
 // the multiplier is a power of two from the bound max_c |gamma rstd| (max |g| + |s1| / M + max |xh| |s2| / M) >= max |dz| (1 when that is
 // zero or not finite)
-__global__ __launch_bounds__(BT_W) void bt_bwd_finish_kernel(const double* part, const float* pmax, int G, double inv_m, const float* tab, const float* in_sc,
-                                                             float* coef, float* dgam, float* dbet, float* out_sc) {
+template <int W>
+__global__ __launch_bounds__(W) void bt_bwd_finish_kernel(const double* part, const float* pmax, int G, double inv_m, const float* tab, const float* in_sc,
+                                                          float* coef, float* dgam, float* dbet, float* out_sc) {
     const int c = threadIdx.x;
     double s1 = 0.0, s2 = 0.0;
     float mg = 0.f, mx = 0.f;
     for (int g = 0; g < G; ++g) {
-        const int64_t b = (int64_t)g * 2 * BT_W + c;
-        s1 += part[b]; s2 += part[b + BT_W];
-        mg = nmax(mg, pmax[b]); mx = nmax(mx, pmax[b + BT_W]);
+        const int64_t b = (int64_t)g * 2 * W + c;
+        s1 += part[b]; s2 += part[b + W];
+        mg = nmax(mg, pmax[b]); mx = nmax(mx, pmax[b + W]);
     }
-    const float A = tab[2 * BT_W + c] * tab[BT_W + c], B = (float)(s1 * inv_m), C = (float)(s2 * inv_m);
-    coef[c] = A; coef[BT_W + c] = B; coef[2 * BT_W + c] = C;
+    const float A = tab[2 * W + c] * tab[W + c], B = (float)(s1 * inv_m), C = (float)(s2 * inv_m);
+    coef[c] = A; coef[W + c] = B; coef[2 * W + c] = C;
     dbet[c] = (float)(s1 * (double)in_sc[1]);
     dgam[c] = (float)(s2 * (double)in_sc[1]);
-    __shared__ float sh[BT_W];
+    __shared__ float sh[W];
     sh[c] = (float)(fabs((double)A) * ((double)mg + fabs((double)B) + (double)mx * fabs((double)C)));
     __syncthreads();
-    for (int o = BT_W / 2; o > 0; o >>= 1) {
+    for (int o = W / 2; o > 0; o >>= 1) {
         if (c < o) sh[c] = nmax(sh[c], sh[c + o]);
         __syncthreads();
     }
@@ -294,21 +344,23 @@ __global__ __launch_bounds__(BT_W) void bt_bwd_finish_kernel(const double* part,
     }
 }
 
-// dz = gamma rstd (g - s1 / M - xh s2 / M) in fp32, times the multiplier, as fp16: flat [rows][W] and (when given) the interior of a
-// ring-padded plane.  One thread = 8 channels.
+// dz = gamma rstd (g - s1 / M - xh s2 / M) in fp32, times the multiplier, as fp16: flat [rows][W] and (when given) a ring-padded plane
+// [n][dil H + 2][dil Wd + 2][W] at pixel (dil y, dil x): dil = 1 fills the interior, dil = 2 the even positions of the stride-2 dgrad's
+// zero-inserted plane.  One thread = 8 channels.
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_form_kernel(const float* g, const float* z, const float* tab, const float* coef, const float* sc,
-                                                             int64_t rows, int H, int Wd, half_t* flat, half_t* padded) {
+                                                             int64_t rows, int H, int Wd, int dil, half_t* flat, half_t* padded) {
     const int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x;
-    if (i >= rows * (BT_W / 8)) return;
-    const int c0 = (int)(i & 63) * 8;
+    if (i >= rows * (W / 8)) return;
+    const int c0 = (int)(i % (W / 8)) * 8;
     const float mul = sc[2];
     half8 h;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const floatx4 gv = *(const floatx4*)(g + i * 8 + 4 * k), zv = *(const floatx4*)(z + i * 8 + 4 * k);
-        const floatx4 mu = *(const floatx4*)(tab + c0 + 4 * k), rs = *(const floatx4*)(tab + BT_W + c0 + 4 * k);
-        const floatx4 A = *(const floatx4*)(coef + c0 + 4 * k), B = *(const floatx4*)(coef + BT_W + c0 + 4 * k),
-                      C = *(const floatx4*)(coef + 2 * BT_W + c0 + 4 * k);
+        const floatx4 mu = *(const floatx4*)(tab + c0 + 4 * k), rs = *(const floatx4*)(tab + W + c0 + 4 * k);
+        const floatx4 A = *(const floatx4*)(coef + c0 + 4 * k), B = *(const floatx4*)(coef + W + c0 + 4 * k),
+                      C = *(const floatx4*)(coef + 2 * W + c0 + 4 * k);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float xh = (zv[e] - mu[e]) * rs[e];
@@ -317,21 +369,22 @@ __global__ __launch_bounds__(BT_THREADS) void bt_form_kernel(const float* g, con
     }
     *(half8*)(flat + i * 8) = h;
     if (padded) {
-        const int64_t m = i >> 6;
+        const int64_t m = i / (W / 8);
         const int HW = H * Wd, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
-        *(half8*)(padded + (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * BT_W + c0) = h;
+        *(half8*)(padded + (((int64_t)img * (dil * H + 2) + dil * y + 1) * (dil * Wd + 2) + dil * x + 1) * W + c0) = h;
     }
 }
 
 // wt [cin][taps * W]: row ci, k = tap' * W + co holds half(w[co][ci][taps - 1 - tap']) (the window rotated by 180 degrees, the raw weights
 // transposed, rounded as the forward packs them); a zero bias row of W entries
+template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_pack_dgrad_kernel(const float* w, int cin, int taps, half_t* wt, float* zero) {
     const int i = blockIdx.x * BT_THREADS + threadIdx.x;
-    const int K = taps * BT_W;
+    const int K = taps * W;
     if (i < cin * K) {
-        const int ci = i / K, k = i - ci * K, tap = k / BT_W, co = k - tap * BT_W;
+        const int ci = i / K, k = i - ci * K, tap = k / W, co = k - tap * W;
         wt[i] = (half_t)w[((int64_t)co * cin + ci) * taps + (taps - 1 - tap)];
-    } else if (i < cin * K + BT_W) {
+    } else if (i < cin * K + W) {
         zero[i - cin * K] = 0.f;
     }
 }
@@ -349,35 +402,51 @@ __global__ __launch_bounds__(BT_THREADS) void bt_dw_kernel(const float* slab, in
     }
 }
 
-}  // namespace
+// the stride-2 block: dx [n][2H][2Wd][cin] (at dz1's total scale, dscale sc2[2] sc1[2]) += t = ds^T(dz_d) [n][H][Wd][cin] (at dz_d's total
+// scale, dscale scd[2]) times sc2[2] sc1[2] / scd[2], powers of two all three, at the even (row, column) positions: the 1x1 stride-2
+// convolution reads no other.  One thread = 4 channels.
+__global__ __launch_bounds__(BT_THREADS) void bt_add_downsample_kernel(float* dx, const float* t, int64_t rows, int H, int Wd, int cin, const float* sc2,
+                                                                       const float* sc1, const float* scd) {
+    const int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x;
+    const int C4 = cin >> 2;
+    if (i >= rows * C4) return;
+    const int cq = (int)(i % C4);
+    const int64_t m = i / C4;
+    const int HW = H * Wd, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    float* d = dx + (((int64_t)img * 2 * H + 2 * y) * 2 * Wd + 2 * x) * cin + 4 * cq;
+    const float mul = sc2[2] * sc1[2] / scd[2];
+    floatx4 a = *(floatx4*)d;
+    const floatx4 b = *(const floatx4*)(t + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] += b[e] * mul;
+    *(floatx4*)d = a;
+}
 
-int64_t vtd_resblock_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+int64_t ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode, int base) {
     Geo g;
-    if (!make_geo(n, hin, win, cin, width, stride, g) || mode < 0 || mode > 1) return BT_ERR - 1;
+    if (!make_geo(n, hin, win, cin, width, stride, base, g) || mode < 0 || mode > 1) return base - 1;
+    const bool general = base != BT_LEGACY;
     // either mode of `training` runs in one allocation: the frozen path's layout starts at offset 0 too
-    const int64_t frozen = vtd_basicblock_ws_bytes(n, hin, win, cin, width, stride, mode), own = mode ? bwd_layout(g).total : fwd_layout(g).total;
-    if (frozen < 0) return BT_ERR - 1;
+    const int64_t frozen = general ? vtd_resblock_ws_bytes(n, hin, win, cin, width, stride, mode)
+                                   : vtd_basicblock_ws_bytes(n, hin, win, cin, width, stride, mode);
+    const int64_t own = mode ? bwd_layout(g, general && g.ds).total : fwd_layout(g).total;
+    if (frozen < 0) return base - 1;
     return frozen > own ? frozen : own;
 }
 
-int vtd_launch_resblock_bn_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
-                                   float momentum, float eps, void* ws, void* y, float* stats, hipStream_t s) {
-    Geo g;
-    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, g) || !params_ok(P, g.ds) || !(eps > 0.f) || (training != 0 && training != 1))
-        return BT_ERR - 1;
-    if (training && (g.m < 2 || !(momentum >= 0.f && momentum <= 1.f))) return BT_ERR - 1;
-    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)stats & 3)) return BT_ERR - 2;
-    if (!training) return vtd_launch_basicblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+template <int W>
+int forward_launches(const void* x, const Geo& g, const vtd_basicblock_params* P, float momentum, float eps, void* ws, void* y, float* stats,
+                     hipStream_t s) {
     const FwdLayout L = fwd_layout(g);
-    const int W = BT_W;
+    const int n = g.n, hin = g.hin, win = g.win, cin = g.cin, stride = g.stride;
     const int64_t M = g.m;
     char* w = (char*)ws;
     half_t *a1 = (half_t*)(w + L.a1), *id = (half_t*)(w + L.id), *w1 = (half_t*)(w + L.w1), *w2 = (half_t*)(w + L.w2), *wd = (half_t*)(w + L.wd);
     float *z1 = (float*)(w + L.z1), *z2 = (float*)(w + L.z2), *zd = (float*)(w + L.zd), *zero = (float*)(w + L.zero), *tab = (float*)(w + L.tab);
     double* part = (double*)(w + L.part);
-    hipLaunchKernelGGL(bt_pack_kernel, dim3(nblk((int64_t)W * 9 * cin + W)), dim3(BT_THREADS), 0, s, (const float*)P->conv1_w, cin, 9, w1, zero);
-    hipLaunchKernelGGL(bt_pack_kernel, dim3(nblk((int64_t)W * 9 * W)), dim3(BT_THREADS), 0, s, (const float*)P->conv2_w, W, 9, w2, (float*)nullptr);
-    if (g.ds) hipLaunchKernelGGL(bt_pack_kernel, dim3(nblk((int64_t)W * cin)), dim3(BT_THREADS), 0, s, (const float*)P->ds_w, cin, 1, wd, (float*)nullptr);
+    hipLaunchKernelGGL(bt_pack_kernel<W>, dim3(nblk((int64_t)W * 9 * cin + W)), dim3(BT_THREADS), 0, s, (const float*)P->conv1_w, cin, 9, w1, zero);
+    hipLaunchKernelGGL(bt_pack_kernel<W>, dim3(nblk((int64_t)W * 9 * W)), dim3(BT_THREADS), 0, s, (const float*)P->conv2_w, W, 9, w2, (float*)nullptr);
+    if (g.ds) hipLaunchKernelGGL(bt_pack_kernel<W>, dim3(nblk((int64_t)W * cin)), dim3(BT_THREADS), 0, s, (const float*)P->ds_w, cin, 1, wd, (float*)nullptr);
     const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * (W / 8));
     hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, a1, n, g.h, g.w, W);
     hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, (half_t*)y, n, g.h, g.w, W);
@@ -395,11 +464,11 @@ int vtd_launch_resblock_bn_forward(const void* x, int n, int hin, int win, int c
                     float* rmean, float* rvar, const half_t* res, int relu, half_t* out) {
         const int rc = conv_f32(in, ic, hi, wi, ksz, st, wp, z);
         if (rc) return rc;
-        hipLaunchKernelGGL(bt_stats_partial_kernel, dim3(g.red), dim3(BT_THREADS), 0, s, (const float*)z, M, g.per, part);
-        hipLaunchKernelGGL(bt_stats_finish_kernel, dim3(W / BT_THREADS), dim3(BT_THREADS), 0, s, (const double*)part, g.red, gam, bet, rmean, rvar, momentum,
+        hipLaunchKernelGGL(bt_stats_partial_kernel<W>, dim3(g.red), dim3(BT_THREADS), 0, s, (const float*)z, M, g.per, part);
+        hipLaunchKernelGGL(bt_stats_finish_kernel<W>, dim3(W / BT_THREADS), dim3(BT_THREADS), 0, s, (const double*)part, g.red, gam, bet, rmean, rvar, momentum,
                            eps, tab + row * 4 * W, stats ? stats + row * 2 * W : (float*)nullptr);
-        hipLaunchKernelGGL(bt_apply_kernel, dim3(nblk(M * (W / 8))), dim3(BT_THREADS), 0, s, (const float*)z, M, (const float*)(tab + row * 4 * W), res, relu,
-                           g.h, g.w, out);
+        hipLaunchKernelGGL(bt_apply_kernel<W>, dim3(nblk(M * (W / 8))), dim3(BT_THREADS), 0, s, (const float*)z, M, (const float*)(tab + row * 4 * W), res,
+                           relu, g.h, g.w, out);
         return -(int)hipGetLastError();
     };
     int rc;
@@ -408,21 +477,25 @@ int vtd_launch_resblock_bn_forward(const void* x, int n, int hin, int win, int c
     return pair(a1, W, g.h, g.w, 3, 1, w2, z2, 1, P->bn2_w, P->bn2_b, P->bn2_mean, P->bn2_var, g.ds ? id : (const half_t*)x, 1, (half_t*)y);
 }
 
-int vtd_launch_resblock_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
-                                    float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
-                                    void* scratch, float* dx, float* dxscale, hipStream_t s) {
+int launch_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training, float momentum,
+                   float eps, void* ws, void* y, float* stats, hipStream_t s, int base) {
     Geo g;
-    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
-        !(eps > 0.f) || (dx && !dxscale) || (training != 0 && training != 1) || (training && g.m < 2))
-        return BT_ERR - 1;
-    if (dx && g.stride != 1) return BT_ERR - 3;
-    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dy & 15) || ((uintptr_t)dscale & 7) ||
-        ((uintptr_t)dx & 15) || ((uintptr_t)dxscale & 7))
-        return BT_ERR - 2;
-    if (!training) return vtd_launch_basicblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, base, g) || !params_ok(P, g.ds) || !(eps > 0.f) || (training != 0 && training != 1))
+        return base - 1;
+    if (training && (g.m < 2 || !(momentum >= 0.f && momentum <= 1.f))) return base - 1;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)stats & 3)) return base - 2;
+    if (!training)
+        return base == BT_LEGACY ? vtd_launch_basicblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s)
+                                 : vtd_launch_resblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+    return width == 256 ? forward_launches<256>(x, g, P, momentum, eps, ws, y, stats, s) : forward_launches<512>(x, g, P, momentum, eps, ws, y, stats, s);
+}
+
+template <int W>
+int backward_launches(const void* x, const Geo& g, const vtd_basicblock_params* P, const void* ws, const void* y, const float* dy, const float* dscale,
+                      const vtd_basicblock_params* Gp, void* scratch, float* dx, float* dxscale, hipStream_t s, bool general) {
     const FwdLayout L = fwd_layout(g);
-    const BwdLayout B = bwd_layout(g);
-    const int W = BT_W;
+    const BwdLayout B = bwd_layout(g, general && g.ds);
+    const int n = g.n, hin = g.hin, win = g.win, cin = g.cin, stride = g.stride;
     const int64_t M = g.m;
     const char* w = (const char*)ws;
     char* q = (char*)scratch;
@@ -436,16 +509,18 @@ int vtd_launch_resblock_bn_backward(const void* x, int n, int hin, int win, int 
     const unsigned ring = nblk((int64_t)n * (2 * (g.w + 2) + 2 * g.h) * (W / 8));
     const int S = wg_slabs(M);
     const double inv_m = 1.0 / (double)M;
+    const bool strided_dx = dx && g.ds;      // the general entries only: the others refused it
 
-    // one pair's BatchNorm backward: the two channel sums, dgamma / dbeta, the scale, dz as the fp16 operands
-    auto bn_back = [&](const float* gr, const float* z, int row, const float* in_sc, float* out_sc, float* dgam, float* dbet, bool want_padded) {
+    // one pair's BatchNorm backward: the two channel sums, dgamma / dbeta, the scale, dz as the fp16 operands: flat, and (when `plane` is given)
+    // the interior of the ring-padded dzp (dil = 1) or the even positions of the zeroed plane of the input's extent (dil = 2)
+    auto bn_back = [&](const float* gr, const float* z, int row, const float* in_sc, float* out_sc, float* dgam, float* dbet, half_t* plane, int dil) {
         const float* t = tab + row * 4 * W;
-        hipLaunchKernelGGL(bt_bwd_reduce_kernel, dim3(g.red), dim3(BT_THREADS), 0, s, gr, z, t, M, g.per, part, pmax);
-        hipLaunchKernelGGL(bt_bwd_finish_kernel, dim3(1), dim3(BT_W), 0, s, (const double*)part, (const float*)pmax, g.red, inv_m, t, in_sc, coef, dgam, dbet,
+        hipLaunchKernelGGL(bt_bwd_reduce_kernel<W>, dim3(g.red), dim3(BT_THREADS), 0, s, gr, z, t, M, g.per, part, pmax);
+        hipLaunchKernelGGL(bt_bwd_finish_kernel<W>, dim3(1), dim3(W), 0, s, (const double*)part, (const float*)pmax, g.red, inv_m, t, in_sc, coef, dgam, dbet,
                            out_sc);
-        if (want_padded) hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, dzp, n, g.h, g.w, W);
-        hipLaunchKernelGGL(bt_form_kernel, dim3(nblk(M * (W / 8))), dim3(BT_THREADS), 0, s, gr, z, t, (const float*)coef, (const float*)out_sc, M, g.h, g.w,
-                           dzh, want_padded ? dzp : (half_t*)nullptr);
+        if (plane && dil == 1) hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring), dim3(RB_THREADS), 0, s, plane, n, g.h, g.w, W);
+        hipLaunchKernelGGL(bt_form_kernel<W>, dim3(nblk(M * (W / 8))), dim3(BT_THREADS), 0, s, gr, z, t, (const float*)coef, (const float*)out_sc, M, g.h, g.w,
+                           dil, dzh, plane);
     };
     auto wgrad = [&](const half_t* xin, int xc, int hi, int wi, int ksz, int st, const float* scl, float* dw) {
         WgArgs wa;
@@ -454,34 +529,96 @@ int vtd_launch_resblock_bn_backward(const void* x, int n, int hin, int win, int 
         hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(ksz * ksz * xc / 128 * S, W / 128), dim3(WG_THREADS), 0, s, wa);
         hipLaunchKernelGGL(bt_dw_kernel, dim3(W), dim3(BT_THREADS), 0, s, (const float*)slab, S, xc, ksz * ksz, scl, dw);
     };
-    // conv^T of the padded dz plane into [M][W] fp32: the raw weights of a 3x3 conv with W input channels, rotated and transposed
-    auto dgrad = [&](const float* wsrc, float* out) {
-        hipLaunchKernelGGL(bt_pack_dgrad_kernel, dim3(nblk((int64_t)W * 9 * W + W)), dim3(BT_THREADS), 0, s, wsrc, W, 9, wt, zero);
-        ConvParams c = conv_of(n, g.h, g.w, W, dzp, W, g.h, g.w, 3, 1, wt, zero);
-        c.out = out; c.ldc = W; c.flags = EPI_OUT_F32;
+    // conv^T of a padded dz plane of hp x wp pixels (W channels) into [n hp wp][rows] fp32: the raw weights of a conv with `rows` input
+    // channels, rotated and transposed into `panel`
+    auto dgrad = [&](const half_t* gp, int hp, int wp, const float* wsrc, int rows, int ksz, half_t* panel, float* out) {
+        hipLaunchKernelGGL(bt_pack_dgrad_kernel<W>, dim3(nblk((int64_t)rows * ksz * ksz * W + W)), dim3(BT_THREADS), 0, s, wsrc, rows, ksz * ksz, panel, zero);
+        ConvParams c = conv_of(n, hp, wp, rows, gp, W, hp, wp, ksz, 1, panel, zero);
+        c.out = out; c.ldc = rows; c.flags = EPI_OUT_F32;
         return vtd_launch_conv(c, -1, s);
     };
 
     int rc;
     hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, g.h, g.w, W, g2);
-    bn_back(g2, z2, 1, dscale, sc2, Gp->bn2_w, Gp->bn2_b, true);
+    bn_back(g2, z2, 1, dscale, sc2, Gp->bn2_w, Gp->bn2_b, dzp, 1);
     wgrad(a1, W, g.h, g.w, 3, 1, sc2, Gp->conv2_w);
     VTD_HIP_CHECK(hipGetLastError());
     // da1 = conv2^T(dz2) into the g1 buffer, masked in place by a1 > 0
-    if ((rc = dgrad((const float*)P->conv2_w, g1))) return rc;
+    if ((rc = dgrad(dzp, g.h, g.w, (const float*)P->conv2_w, W, 3, wt, g1))) return rc;
     if (g.ds) {   // the downsample pair: its upstream gradient is g2
-        bn_back(g2, zd, 2, dscale, scd, Gp->ds_bn_w, Gp->ds_bn_b, false);
+        bn_back(g2, zd, 2, dscale, scd, Gp->ds_bn_w, Gp->ds_bn_b, strided_dx ? dzp : (half_t*)nullptr, 1);
         wgrad((const half_t*)x, cin, hin, win, 1, 2, scd, Gp->ds_w);
+        // ds^T(dz_d) at dz_d's scale into a buffer of its own, now: bn1's pair takes the dz operands next
+        if (strided_dx && (rc = dgrad(dzp, g.h, g.w, (const float*)P->ds_w, cin, 1, (half_t*)(q + B.wdt), (float*)(q + B.dst)))) return rc;
     }
     hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, (const float*)g1, a1, M, g.h, g.w, W, g1);
-    bn_back(g1, z1, 0, sc2, sc1, Gp->bn1_w, Gp->bn1_b, dx != nullptr);
+    if (strided_dx) VTD_HIP_CHECK(hipMemsetAsync(q + B.zp, 0, (size_t)n * (hin + 2) * (win + 2) * W * 2, s));
+    bn_back(g1, z1, 0, sc2, sc1, Gp->bn1_w, Gp->bn1_b, strided_dx ? (half_t*)(q + B.zp) : dx ? dzp : (half_t*)nullptr, strided_dx ? 2 : 1);
     wgrad((const half_t*)x, cin, hin, win, 3, stride, sc1, Gp->conv1_w);
     VTD_HIP_CHECK(hipGetLastError());
-    if (dx) {
-        if ((rc = dgrad((const float*)P->conv1_w, dx))) return rc;
+    if (dx && !g.ds) {
+        if ((rc = dgrad(dzp, g.h, g.w, (const float*)P->conv1_w, W, 3, wt, dx))) return rc;
         hipLaunchKernelGGL(rb_add_identity_kernel, dim3(nblk(M * (W / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g2, M * (W / 4), (const float*)sc2,
                            (const float*)sc1);
         hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
+    } else if (dx) {
+        // dz1 sits at the even positions of the zeroed plane of the input's size: the stride-1 path over it, see the head of this file
+        if ((rc = dgrad((const half_t*)(q + B.zp), hin, win, (const float*)P->conv1_w, cin, 3, wt, dx))) return rc;
+        hipLaunchKernelGGL(bt_add_downsample_kernel, dim3(nblk(M * (cin / 4))), dim3(BT_THREADS), 0, s, dx, (const float*)(q + B.dst), M, g.h, g.w, cin,
+                           (const float*)sc2, (const float*)sc1, (const float*)scd);
+        hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
     }
     return -(int)hipGetLastError();
+}
+
+int launch_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training, float eps,
+                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch, float* dx,
+                    float* dxscale, hipStream_t s, int base) {
+    Geo g;
+    const bool legacy = base == BT_LEGACY;
+    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, base, g) || !params_ok(P, g.ds) || !grads_ok(Gp, g.ds) ||
+        !(eps > 0.f) || (dx && !dxscale) || (training != 0 && training != 1) || (training && g.m < 2))
+        return base - 1;
+    if (legacy && dx && g.stride != 1) return base - 3;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dy & 15) || ((uintptr_t)dscale & 7) ||
+        ((uintptr_t)dx & 15) || ((uintptr_t)dxscale & 7))
+        return base - 2;
+    if (!training)
+        return legacy ? vtd_launch_basicblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s)
+                      : vtd_launch_resblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+    return width == 256 ? backward_launches<256>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy)
+                        : backward_launches<512>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy);
+}
+
+}  // namespace
+
+int64_t vtd_resblock_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(n, hin, win, cin, width, stride, mode, BT_LEGACY);
+}
+
+int vtd_launch_resblock_bn_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                   float momentum, float eps, void* ws, void* y, float* stats, hipStream_t s) {
+    return launch_forward(x, n, hin, win, cin, width, stride, P, training, momentum, eps, ws, y, stats, s, BT_LEGACY);
+}
+
+int vtd_launch_resblock_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                    float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
+                                    void* scratch, float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(x, n, hin, win, cin, width, stride, P, training, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, BT_LEGACY);
+}
+
+// the four geometries of layer3 and layer4, with the input gradient of the stride-2 blocks
+int64_t vtd_block_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(n, hin, win, cin, width, stride, mode, BT_GENERAL);
+}
+
+int vtd_launch_block_bn_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                float momentum, float eps, void* ws, void* y, float* stats, hipStream_t s) {
+    return launch_forward(x, n, hin, win, cin, width, stride, P, training, momentum, eps, ws, y, stats, s, BT_GENERAL);
+}
+
+int vtd_launch_block_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                 float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
+                                 void* scratch, float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(x, n, hin, win, cin, width, stride, P, training, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, BT_GENERAL);
 }

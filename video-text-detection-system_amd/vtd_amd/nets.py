@@ -114,11 +114,25 @@ _BN_TRAIN_BUILT = ("train-mode (batch-statistics) BatchNorm is built for the Bas
                    "downsample, 512 -> 512 stride 1); layer3, layer2, layer1, the stem and Bottleneck blocks keep frozen statistics")
 
 
-def _block_bn_check(block):
-    """The BatchNorms of a BasicBlock that vtd_resblock_bn_train_* can run in train mode (bn1, bn2, the downsample's), validated."""
+# the same on the vtd_block_bn_train_* entries: layer3's two geometries too, and the input gradient of either stride
+_BLOCK_BN_GEOMETRIES = ((128, 256, 2, True), (256, 256, 1, False)) + _BN_TRAIN_GEOMETRIES
+_BLOCK_BN_BUILT = ("basic_block_bn_train (train-mode, batch-statistics BatchNorm) is built for the BasicBlocks of ResNet-18's layer3 and layer4 "
+                   "(128 -> 256 and 256 -> 512 stride 2 with downsample, 256 -> 256 and 512 -> 512 stride 1); layer2, layer1, the stem and "
+                   "Bottleneck blocks keep frozen statistics")
+# the stages whose BatchNorms the trunk node can run with batch statistics (forward_padded's trunk_batch_stats, DBNet's trunk_bn), with the
+# training mode each goes with
+_TRUNK_BN_STAGES = {("layer4",): "head+fpn+layer4", ("layer3", "layer4"): "head+fpn+layer4+layer3"}
+_TRUNK_BN_BUILT = ("train-mode (batch-statistics) trunk BatchNorm is built for ('layer4',) with trainable='head+fpn+layer4' and for "
+                   "('layer3', 'layer4') with trainable='head+fpn+layer4+layer3', on resnet18; the tuple names exactly the residual stages that "
+                   "train; layer2, layer1 and the stem keep frozen statistics")
+
+
+def _block_bn_check(block, geometries=_BN_TRAIN_GEOMETRIES, built=_BN_TRAIN_BUILT):
+    """The BatchNorms of a BasicBlock that vtd_resblock_bn_train_* (or, with the four `geometries`, vtd_block_bn_train_*) can run in train
+    mode (bn1, bn2, the downsample's), validated."""
     cin, width, ds = block.conv1.in_channels, block.conv1.out_channels, hasattr(block, "downsample")
-    if (cin, width, block.stride, ds) not in _BN_TRAIN_GEOMETRIES:
-        raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {block.stride}): " + _BN_TRAIN_BUILT)
+    if (cin, width, block.stride, ds) not in geometries:
+        raise RuntimeError(f"BasicBlock({cin} -> {width}, stride {block.stride}): " + built)
     bns = [block.bn1, block.bn2] + ([block.downsample[1]] if ds else [])
     if any(bn.momentum is None or bn.momentum != bns[0].momentum for bn in bns):
         raise ValueError("the HIP batch-statistics BasicBlock kernels need one fixed momentum on all of the block's BatchNorms "
@@ -156,19 +170,37 @@ def basic_block_train(block, x, batch_stats=False):
     return _BlockTrainFn.apply(pack_tap(x), src, geom, eps, tuple(stats), _block_entry(geom), None, *learn)
 
 
-def _basic_block_bn_train(block, x, bns):
-    (cin, width, stride), eps, learn, stats = block._train_operands(x.device)
+def basic_block_bn_train(block, x):
+    """One BasicBlock of ResNet-18's layer3 or layer4 (128 -> 256 and 256 -> 512 at stride 2 with downsample and even extents, 256 -> 256 and
+    512 -> 512 at stride 1) on the vtd_block_bn_train_* entries (csrc/resblock_bn_train.hip) with torch's module semantics: in
+    ``block.training`` mode the statistics of the batch normalise, the running statistics are updated in place and ``num_batches_tracked``
+    advances on each of the block's BatchNorms; in ``eval()`` mode it gives the bits of ``basic_block_train(block, x)``.  Returns
+    ``[n,width,h,w]`` fp32, differentiable w.r.t. the block's learnable tensors and w.r.t. ``x`` for either stride (the stride-2 blocks
+    through the strided dgrad of dz1 plus the downsample's transpose of its own dz).  For layer4's blocks the output, the parameter
+    gradients, the running update and the stride-1 input gradient are the bits of ``basic_block_train(block, x, batch_stats=True)``."""
+    if not isinstance(block, BasicBlock):
+        raise RuntimeError("basic_block_bn_train: Bottleneck training is not built; " + _BLOCK_BN_BUILT)
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != block.conv1.in_channels:
+        raise ValueError(f"BasicBlock input must be a [n,{block.conv1.in_channels},H,W] tensor")
+    bns = _block_bn_check(block, _BLOCK_BN_GEOMETRIES, _BLOCK_BN_BUILT)   # what is built, before anything about the device
+    if not x.is_cuda:
+        raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    return _basic_block_bn_train(block, x, bns, general=True)
+
+
+def _basic_block_bn_train(block, x, bns, general=False):
+    (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=general)
     n, _, hin, win = x.shape
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
         raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
     if block.training and n * (hin // stride) * (win // stride) < 2:
         raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got an output of {n} x {hin // stride} x {win // stride}")
-    if stride != 1 and x.requires_grad and torch.is_grad_enabled():
+    if not general and stride != 1 and x.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("BasicBlock(stride 2, batch_stats=True): the input requires grad, but the input gradient of the stride-2 block is not "
                            "built with batch-statistics BatchNorm; pass x.detach()")
     src = x if x.requires_grad and torch.is_grad_enabled() else None
-    out = _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _RESBLOCK_BN,
-                              (bool(block.training), float(bns[0].momentum)), *learn)
+    out = _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats),
+                              _BLOCK_BN if general else _RESBLOCK_BN, (bool(block.training), float(bns[0].momentum)), *learn)
     if block.training:
         with torch.no_grad():
             for bn in bns:
@@ -283,7 +315,13 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False):
-        """With `trunk_batch_stats=True` (the layer4 -> FPN -> head node only: passing it with `layer3` or a lower stage raises ValueError)
+        """`trunk_batch_stats` may also be a tuple or list of stage names.  ("layer4",) means what True means.  ("layer3", "layer4") goes with
+        taps [C2, C3], `layer3`, `layer4` and `head` and nothing lower: the four blocks run on the vtd_block_bn_train_* entries, in one mode
+        (train() or eval()) with one momentum and one eps, else ValueError; layer4.0 forms its input gradient (dz1 through the strided dgrad
+        plus the downsample's transpose of its own dz), which is combined with the FPN's dC4; layer3.0 forms none.  Any other tuple raises
+        ValueError.
+
+        With `trunk_batch_stats=True` (the layer4 -> FPN -> head node only: passing it with `layer3` or a lower stage raises ValueError)
         layer4 runs on the vtd_resblock_bn_train_* entries: while layer4 is in training mode its five BatchNorms normalise with the statistics
         of the batch, their running statistics are updated in place and their num_batches_tracked advance; in eval() mode the frozen path
         runs, the same bits as without the flag.
@@ -317,10 +355,20 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
-        if trunk_batch_stats and (layer4 is None or any(m is not None for m in (layer3, layer2, layer1, stem))):
+        bn_stages = ()
+        if isinstance(trunk_batch_stats, (tuple, list)):
+            bn_stages = tuple(trunk_batch_stats)
+            if not any(bn_stages == stages for stages in _TRUNK_BN_STAGES):      # no hashing: any tuple may come
+                raise ValueError(f"forward_padded(..., trunk_batch_stats={trunk_batch_stats!r}): " + _TRUNK_BN_BUILT)
+        elif trunk_batch_stats:
+            bn_stages = ("layer4",)
+        if bn_stages == ("layer4",) and (layer4 is None or any(m is not None for m in (layer3, layer2, layer1, stem))):
             raise ValueError("forward_padded(..., trunk_batch_stats=True) is the layer4 -> FPN -> head node: " + _BN_TRAIN_BUILT)
+        if len(bn_stages) == 2 and (layer4 is None or layer3 is None or any(m is not None for m in (layer2, layer1, stem))):
+            raise ValueError("forward_padded(..., trunk_batch_stats=('layer3', 'layer4')) is the layer3 -> layer4 -> FPN -> head node on the taps "
+                             "[C2, C3]: it needs layer3, layer4 and the head and takes no lower stage; " + _TRUNK_BN_BUILT)
         if stem is not None or any(m is not None for m in layers):
-            return self._forward_padded_trunk(taps, head, layers, stem, trunk_batch_stats)
+            return self._forward_padded_trunk(taps, head, layers, stem, bn_stages)
         if not isinstance(taps, (list, tuple)) or len(taps) != 4:
             raise ValueError("padded taps must be the four tensors [C2, C3, C4, C5]")
         _check_padded_taps(taps)
@@ -339,9 +387,10 @@ class FeaturePyramidNetwork(nn.Module):
         head._batches_seen(bns)
         return {"probability": prob, "threshold": thresh}
 
-    def _forward_padded_trunk(self, taps, head, layers, stem, trunk_batch_stats):
+    def _forward_padded_trunk(self, taps, head, layers, stem, bn_stages):
         """forward_padded with trunk stages: `layers` is (layer1, layer2, layer3, layer4), the node starts at the lowest one given (with `stem`:
-        at the stem) and needs every stage above it and the head."""
+        at the stem) and needs every stage above it and the head.  `bn_stages`: () or the stages (all of the node's) that run with batch
+        statistics, ("layer4",) on the vtd_resblock_bn_train_* entries or ("layer3", "layer4") on vtd_block_bn_train_*."""
         low = 0 if stem is not None else next(i for i, m in enumerate(layers) if m is not None)
         above = _STAGES[0 if stem is not None else low + 1:]
         if head is None or any(m is None for m in layers[4 - len(above):]):
@@ -349,6 +398,11 @@ class FeaturePyramidNetwork(nn.Module):
                              + ", ".join(st.name for st in above) + (" and " if above else "") + "the DBHead too")
         if stem is not None and (not isinstance(stem, (list, tuple)) or len(stem) != 2):
             raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
+        deep_bn = len(bn_stages) == 2
+        if deep_bn:      # the plan is node-wide: one eps over the four blocks (one mode and one momentum are checked below)
+            eps_all = {m.eps for layer in layers[2:] for m in layer.modules() if isinstance(m, nn.BatchNorm2d)}
+            if len(eps_all) > 1:
+                raise ValueError("layer3's and layer4's four blocks must have one BatchNorm eps")
         # the taps the node reads: the FPN levels below the lowest stage's output, the last of them that stage's input; layer1 reads the pooled
         # stem output and the stem the image, neither an FPN level
         names = ["image"] if stem is not None else [st.tap for st in _STAGES[1:low + 1]] or [_STAGES[0].tap]
@@ -377,11 +431,13 @@ class FeaturePyramidNetwork(nn.Module):
         params = self._live_checked(dev)
         bns, hparams, hbuffers = head._train_operands(dev)
         bn, bbns = None, []
-        if trunk_batch_stats:
-            blocks = ops[-1][0]
-            bbns = [b for blk in blocks for b in _block_bn_check(blk)]
-            if blocks[0].training != blocks[1].training or any(b.momentum != bbns[0].momentum for b in bbns):
-                raise ValueError("layer4's two blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
+        if bn_stages:
+            blocks = [blk for o in ops for blk in o[0]]      # the node's stages are exactly bn_stages (forward_padded)
+            check = (_BLOCK_BN_GEOMETRIES, _BLOCK_BN_BUILT) if deep_bn else ()
+            bbns = [b for blk in blocks for b in _block_bn_check(blk, *check)]
+            if any(blk.training != blocks[0].training for blk in blocks) or any(b.momentum != bbns[0].momentum for b in bbns):
+                raise ValueError(("layer3's and layer4's four" if deep_bn else "layer4's two") +
+                                 " blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
             n, _, h5, w5 = outs[-1]
             if blocks[0].training and n * h5 * w5 < 2:
                 raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a C5 of {n} x {h5} x {w5}")
@@ -390,7 +446,7 @@ class FeaturePyramidNetwork(nn.Module):
         for _, geoms, _, learn, stats in ops:
             for g, lr, s in zip(geoms, learn, stats):
                 # a node of one stage runs on that stage's own entry family, as forward_<stage>_padded does; a deeper one on the block's by width
-                entry = _RESBLOCK_BN if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
+                entry = (_BLOCK_BN if deep_bn else _RESBLOCK_BN) if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
                 blocks.append((_BlockPlan(g, s, entry, len(lr)), lr))
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, tuple(b for b, _ in blocks), beps, bn)
         out = self._run_node(head, bns, plan, *slearn, *(t for _, lr in blocks for t in lr), *params, *hparams)
@@ -725,6 +781,7 @@ _BASICBLOCK = "vtd_basicblock_train"   # the entry family of layer4's two geomet
 _RESBLOCK = "vtd_resblock_train"       # the entry family of the six geometries of layer2, layer3 and layer4
 _BLOCK64 = "vtd_block64_train"         # the entry family of layer1's 64 -> 64 block
 _RESBLOCK_BN = "vtd_resblock_bn_train"   # layer4's two geometries with batch-statistics BatchNorm (csrc/resblock_bn_train.hip)
+_BLOCK_BN = "vtd_block_bn_train"         # layer3's and layer4's four with batch-statistics BatchNorm, and the strided dx (the same file)
 
 
 def _block_entry(geom):
@@ -734,10 +791,11 @@ def _block_entry(geom):
 
 def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None):
     """vtd_basicblock_train_forward (or `entry`'s) on a padded tap: (padded y [n,h+2,w+2,width] fp16, workspace).  With `bn` = (training,
-    momentum) it is vtd_resblock_bn_train_forward, which takes the two after the parameters, and the result has a third member: the batch
+    momentum) it is vtd_resblock_bn_train_forward (vtd_block_bn_train_forward when `entry` names that family), which takes the two after the
+    parameters, and the result has a third member: the batch
     statistics [3,2,width] fp32 -- mu and the biased variance of bn1, bn2 and the downsample's BatchNorm; rows the call does not write are
     NaN.  In training mode the running statistics in `stats` are then updated in place."""
-    entry = _RESBLOCK_BN if bn is not None else entry
+    entry = entry if bn is None or entry == _BLOCK_BN else _RESBLOCK_BN
     C, _native, lib, ws = _native_workspace(entry + "_workspace_bytes", (*geom, 0), tap.device)
     n, hin, win, cin, width, stride = geom
     y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
@@ -753,8 +811,9 @@ def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None)
 def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx, entry=_BASICBLOCK, bn=None):
     """vtd_basicblock_train_backward (or `entry`'s) on dy as NHWC fp32 times dscale[0]: (the gradients in the order of `learn`, dx, dxscale);
     dx is NHWC fp32 [n,h_in,w_in,cin] times dxscale[0], or None.  With `bn` = (training, momentum) it is vtd_resblock_bn_train_backward,
-    which takes the mode after the parameters and forms dx for the stride-1 block only."""
-    entry = _RESBLOCK_BN if bn is not None else entry
+    which takes the mode after the parameters and forms dx for the stride-1 block only, or when `entry` names that family
+    vtd_block_bn_train_backward, which forms dx for either stride."""
+    entry = entry if bn is None or entry == _BLOCK_BN else _RESBLOCK_BN
     grads = [torch.empty_like(p) for p in learn]
     C, _native, lib, scratch = _native_workspace(entry + "_workspace_bytes", (*geom, 1), tap.device)
     n, hin, win, cin, width, stride = geom
@@ -1188,7 +1247,11 @@ class DBNet(_EngineOwner, nn.Module):
         self.set_trainable(trainable, trunk_bn)
 
     def set_trainable(self, trainable, trunk_bn=None):
-        """`trunk_bn` ("frozen", the default, or "batch"; None keeps the current value) is the mode of the trained trunk stages' BatchNorms.
+        """`trunk_bn` ("frozen", the default, "batch", or a tuple of stage names; None keeps the current value) is the mode of the trained trunk
+        stages' BatchNorms.  A tuple names exactly the residual stages the mode trains, else ValueError: ("layer4",) goes with
+        trainable="head+fpn+layer4" and is equivalent to "batch"; ("layer3", "layer4") goes with trainable="head+fpn+layer4+layer3" on resnet18:
+        the trunk engine gives C2 and C3 as with "frozen", then layer3 and layer4 run on the vtd_block_bn_train_* entries -- backbone.6's and
+        backbone.7's ten BatchNorms normalise with the statistics of the batch, and their 20 running buffers and 10 counters move every step.
         "frozen": as described below, the running statistics normalise and are never written.  "batch" (accepted only with
         trainable="head+fpn+layer4" on resnet18; every other combination raises ValueError): a forward in train mode runs the frozen trunk
         engine for C2..C4 exactly as with "frozen", then layer4 on csrc/resblock_bn_train.hip -- backbone.7's five BatchNorms normalise with
@@ -1233,7 +1296,12 @@ class DBNet(_EngineOwner, nn.Module):
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
-        if bn_mode not in ("frozen", "batch"):
+        if isinstance(bn_mode, (tuple, list)):
+            bn_mode = tuple(bn_mode)
+            fits = next((mode for stages, mode in _TRUNK_BN_STAGES.items() if stages == bn_mode), None)      # no hashing: any tuple may come
+            if self.backbone_name != "resnet18" or fits is None or fits != trainable:
+                raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r} on {self.backbone_name}: " + _TRUNK_BN_BUILT)
+        elif bn_mode not in ("frozen", "batch"):
             raise ValueError(f"trunk_bn must be 'frozen' or 'batch', got {bn_mode!r}")
         if bn_mode == "batch" and trainable != "head+fpn+layer4":
             raise ValueError(f"trunk_bn='batch' with trainable={trainable!r}: train-mode (batch-statistics) trunk BatchNorm is built for layer4 only, "
@@ -1389,8 +1457,10 @@ class DBNet(_EngineOwner, nn.Module):
         engine = self.trunk_engine()
         taps = [engine.forward_pool(x)] if k == 4 else engine.forward_trunk(x)[:4 - k]
         stages = {f"layer{j}": self.backbone[3 + j] for j in range(5 - k, 5)}
-        # trunk_bn="batch" is the layer4 mode's alone (set_trainable): layer4's running statistics move too; mark_dirty below covers them
-        out = self.fpn.forward_padded(taps, head=self.head, trunk_batch_stats=getattr(self, "trunk_bn", "frozen") == "batch", **stages)
+        # trunk_bn="batch" is the layer4 mode's alone and a tuple names the mode's own stages (set_trainable): the running statistics of those
+        # stages move too; mark_dirty below covers them
+        bn_mode = getattr(self, "trunk_bn", "frozen")
+        out = self.fpn.forward_padded(taps, head=self.head, trunk_batch_stats=bn_mode if isinstance(bn_mode, tuple) else bn_mode == "batch", **stages)
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
