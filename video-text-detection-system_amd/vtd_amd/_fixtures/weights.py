@@ -14,6 +14,8 @@
     layer1  block0: t = relu(255*x0 - 127.5)   block1: B = 2*relu(t) - 2*relu(t - 0.5)  in {0, ~1}
     FPN     only the C2 lateral feeds channel 0; smooth / head conv / ConvT pass it with unit centre taps
     ConvT6  logit = 16*B - 8
+* ``stress_detector_state_dict`` / ``stress_trocr_state_dict``  calibrated stress weights for the stage-isolated parity tests
+  (oracle/stage_bounds.py, oracle/trocr_bounds.py): activations O(1), biases of activation size, decisions that mean something.
 """
 from collections import OrderedDict
 
@@ -444,4 +446,162 @@ def trocr_state_dict(spec=None, seed=0, w_std=0.01, tok_std=1.0, pos_std=0.3, ou
     out = rn(s.vocab_size, D, std=out_std)
     out[s.eos_token_id] *= eos_gain
     sd["decoder.output_projection.weight"] = out
+    return sd
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Stress weights for the Transformer recogniser (the TrOCR analogue of stress_detector_state_dict).  trocr_state_dict keeps
+# every sublayer a small perturbation, which leaves all three attentions nearly uniform (encoder scores of std 0.12): a wrong
+# softmax scale, a missing q scale, a bad running-maximum rescale or a mask that admits padded keys hardly move its outputs.
+# Here every layer is calibrated on a seeded batch (fixture generation only: plain torch CPU ops) so that
+#   * pre-softmax scores of the encoder, the decoder's self-attention and its cross-attention have a set spread (q weights scaled),
+#   * GELU inputs have std ~1.6 and sublayer outputs are comparable with the residual stream they are added to; the last quarter of every
+#     feed-forward layer's units sits in GELU's left tail instead (inputs ~N(-3.2, 0.3), outputs of a few 1e-3) with fc2 columns scaled up
+#     so that they carry most of the layer's output: there an approximate GELU (tanh form: off by 5-25 % of the value) is far outside the
+#     fp16 rounding of the stored activation, while for the units around zero it is inside it,
+#   * LayerNorm gammas are log-uniform in [0.5, 2], betas and all biases are of the size of the activations they are added to,
+#   * logits have row RMS ~3, no fixed per-token offset, and the <eos> row is scaled by `eos_gain` (free-running rows then end at different steps).
+def stress_trocr_pixels(spec, n, seed=0):
+    """[n,3,S,S] pixel_values in [-1, 1], fp16-representable: blocky random images (patch-sized and quarter-patch-sized cells)."""
+    g = torch.Generator().manual_seed(77001 + seed)
+    s, p = spec.image_size, spec.patch_size
+    coarse = torch.rand(n, 3, s // p, s // p, generator=g) * 2 - 1
+    fine = torch.rand(n, 3, 4 * s // p, 4 * s // p, generator=g) * 2 - 1
+    x = 0.6 * coarse.repeat_interleave(p, 2).repeat_interleave(p, 3) + 0.4 * fine.repeat_interleave(p // 4, 2).repeat_interleave(p // 4, 3)
+    return x.clamp(-1, 1).half().float()
+
+
+def stress_trocr_ids(spec, n, length, seed=0):
+    """[n, length] forced token ids: the start token, then ids drawn from the whole vocabulary (the last id included)."""
+    g = torch.Generator().manual_seed(77101 + seed)
+    ids = torch.randint(4, spec.vocab_size, (n, length), generator=g)
+    ids[:, 0] = spec.decoder_start_token_id
+    if length > 2:
+        ids[0, 1] = spec.vocab_size - 1
+    return ids
+
+
+def stress_trocr_state_dict(spec, seed=0, enc_std=2.0, self_std=3.0, cross_std=2.5, eos_gain=1.0, calib=4, project=True):
+    """Same keys as trocr_state_dict, for any TrOCRSpec.  *_std: spread of the pre-softmax scores of the three attentions on the
+    calibration batch of `calib` crops; eos_gain: factor on the <eos> row of the output projection; project=False keeps the
+    logits' fixed per-token offset (smaller relative logit error: what the free-running compaction case decodes with)."""
+    import torch.nn.functional as F
+    s = spec
+    g = torch.Generator().manual_seed(88001 + seed)
+    sd = OrderedDict()
+    C, FF, D, DF, V = s.enc_hidden, s.enc_ffn, s.dec_hidden, s.dec_ffn, s.vocab_size
+
+    def rn(*shape):
+        return torch.randn(*shape, generator=g)
+
+    def ln(prefix, x, eps):
+        c = x.shape[-1]
+        sd[prefix + ".weight"] = torch.exp(torch.empty(c).uniform_(np.log(0.5), np.log(2.0), generator=g))
+        sd[prefix + ".bias"] = 0.5 * rn(c)
+        return F.layer_norm(x, (c,), sd[prefix + ".weight"], sd[prefix + ".bias"], eps)
+
+    def vstd(t):
+        """spread of an activation over crops and tokens (its fixed per-channel part removed)"""
+        return float((t - t.mean(tuple(range(t.dim() - 1)), keepdim=True)).std().clamp_min(1e-6))
+
+    def lin(prefix, x, n_out, target=None, bias=True):
+        """weight N(0, 1/K) scaled so that the output varies with std `target` (None: as it comes); the bias is of the output's size: it
+        takes the output's fixed per-channel part out (which would otherwise pile up in the residual stream and leave the LayerNorms
+        little that differs between tokens) and adds a random one of half the spread."""
+        w = rn(n_out, x.shape[-1]) / np.sqrt(x.shape[-1])
+        y = x @ w.t()
+        if target is not None:
+            k = target / vstd(y)
+            w, y = w * k, y * k
+        sd[prefix + ".weight"] = w
+        if bias:
+            sd[prefix + ".bias"] = 0.5 * vstd(y) * rn(n_out) - y.mean(tuple(range(y.dim() - 1)))
+            y = y + sd[prefix + ".bias"]
+        return y
+
+    def ffn(p1, p2, y, n_ff, n_out, target):
+        h = lin(p1, y, n_ff, 1.6)
+        tail = n_ff - n_ff // 4
+        sd[p1 + ".weight"][tail:] *= 0.3 / 1.6
+        sd[p1 + ".bias"][tail:] = -3.2 + 0.1 * rn(n_ff - tail)
+        h = F.gelu(y @ sd[p1 + ".weight"].t() + sd[p1 + ".bias"])
+        w = rn(n_out, n_ff) / np.sqrt(n_ff)
+        w[:, tail:] *= np.sqrt(3.0) * vstd(h[..., :tail] @ w[:, :tail].t()) / vstd(h[..., tail:] @ w[:, tail:].t())
+        out = h @ w.t()
+        k = target / vstd(out)
+        sd[p2 + ".weight"] = w * k
+        sd[p2 + ".bias"] = 0.5 * target * rn(n_out) - k * out.mean(tuple(range(out.dim() - 1)))
+        return out * k + sd[p2 + ".bias"]
+
+    def heads(x, h):
+        return x.view(x.shape[0], x.shape[1], h, 64).transpose(1, 2)
+
+    def sharpen(prefix, q, k, target, mask=None):
+        """scale q_proj (weight and bias) so that the scores q k^T / 8 have std `target` over the admitted keys"""
+        sc = q @ k.transpose(-1, -2) / 8.0
+        m = torch.ones_like(sc) if mask is None else mask.expand_as(sc)
+        mean = (sc * m).sum(-1, keepdim=True) / m.sum(-1, keepdim=True).clamp_min(1)
+        std = float((sc - mean)[m > 0].std())
+        f = target / max(std, 1e-6)
+        sd[prefix + ".weight"] = sd[prefix + ".weight"] * f
+        if prefix + ".bias" in sd:
+            sd[prefix + ".bias"] = sd[prefix + ".bias"] * f
+        return q * f
+
+    with torch.no_grad():
+        px = stress_trocr_pixels(s, calib, 900 + seed)
+        e = "encoder.embeddings."
+        w = rn(C, 3, s.patch_size, s.patch_size)
+        y = F.conv2d(px, w, None, stride=s.patch_size)
+        w = w / float(y.std())
+        sd[e + "cls_token"] = rn(1, 1, C)
+        sd[e + "position_embeddings"] = 0.5 * rn(1, s.enc_tokens, C)
+        sd[e + "patch_embeddings.projection.weight"] = w
+        sd[e + "patch_embeddings.projection.bias"] = 0.5 * rn(C)
+        x = F.conv2d(px, w, sd[e + "patch_embeddings.projection.bias"], stride=s.patch_size).flatten(2).transpose(1, 2)
+        x = torch.cat([sd[e + "cls_token"].expand(calib, -1, -1), x], 1) + sd[e + "position_embeddings"]
+        for i in range(s.enc_layers):
+            p = f"encoder.encoder.layer.{i}."
+            y = ln(p + "layernorm_before", x, s.enc_ln_eps)
+            a = p + "attention.attention."
+            q, k, v = (heads(lin(a + n, y, C, 1.0, s.enc_qkv_bias), s.enc_heads) for n in ("query", "key", "value"))
+            q = sharpen(a + "query", q, k, enc_std)
+            att = (torch.softmax(q @ k.transpose(-1, -2) / 8.0, -1) @ v).transpose(1, 2).reshape(x.shape)
+            x = x + lin(p + "attention.output.dense", att, C, 0.7 * vstd(x))
+            y = ln(p + "layernorm_after", x, s.enc_ln_eps)
+            x = x + ffn(p + "intermediate.dense", p + "output.dense", y, FF, C, vstd(x))
+        enc = ln("encoder.layernorm", x, s.enc_ln_eps)
+
+        dq = "decoder.model.decoder."
+        L = s.max_length - 1
+        ids = stress_trocr_ids(s, calib, L, 900 + seed)
+        sd[dq + "embed_tokens.weight"] = rn(V, D)
+        sd[dq + "embed_positions.weight"] = rn(s.max_positions + 2, D)
+        x = ln(dq + "layernorm_embedding", sd[dq + "embed_tokens.weight"][ids] + sd[dq + "embed_positions.weight"][2:2 + L], s.dec_ln_eps)
+        causal = torch.tril(torch.ones(L, L))
+        late = causal.clone()
+        late[:4] = 0   # calibrate on the steps that have at least five keys
+        for i in range(s.dec_layers):
+            p = dq + f"layers.{i}."
+            a = p + "self_attn."
+            q, k, v = (heads(lin(a + n, x, D, 1.0), s.dec_heads) for n in ("q_proj", "k_proj", "v_proj"))
+            q = sharpen(a + "q_proj", q, k, self_std, late if L > 4 else causal)
+            sc = (q @ k.transpose(-1, -2) / 8.0).masked_fill(causal == 0, float("-inf"))
+            att = (torch.softmax(sc, -1) @ v).transpose(1, 2).reshape(x.shape)
+            x = ln(p + "self_attn_layer_norm", x + lin(a + "out_proj", att, D, 0.7 * vstd(x)), s.dec_ln_eps)
+            a = p + "encoder_attn."
+            q = heads(lin(a + "q_proj", x, D, 1.0), s.dec_heads)
+            k, v = (heads(lin(a + n, enc, D, 1.0), s.dec_heads) for n in ("k_proj", "v_proj"))
+            q = sharpen(a + "q_proj", q, k, cross_std)
+            att = (torch.softmax(q @ k.transpose(-1, -2) / 8.0, -1) @ v).transpose(1, 2).reshape(x.shape)
+            x = ln(p + "encoder_attn_layer_norm", x + lin(a + "out_proj", att, D, 1.0 * vstd(x)), s.dec_ln_eps)
+            x = ln(p + "final_layer_norm", x + ffn(p + "fc1", p + "fc2", x, DF, D, vstd(x)), s.dec_ln_eps)
+        # (rows orthogonal to the mean final state: the logits are decided by what differs between crops and steps, not by a fixed offset)
+        out = rn(V, D) / np.sqrt(D)
+        mean = x.mean((0, 1))
+        if project:
+            out = out - torch.outer(out @ mean, mean) / float(mean @ mean)
+        out = out * (3.0 / float((x @ out.t()).std()))
+        out[s.eos_token_id] *= eos_gain
+        sd["decoder.output_projection.weight"] = out
     return sd

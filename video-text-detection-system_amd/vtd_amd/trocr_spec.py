@@ -57,6 +57,18 @@ BASE_PRINTED = TrOCRSpec()
 # reduced instance (same code paths: head_dim 64, token count not a multiple of 16, vocabulary not a multiple of 64)
 TINY = TrOCRSpec(image_size=96, enc_hidden=128, enc_layers=2, enc_heads=2, enc_ffn=256, dec_hidden=192, dec_layers=2, dec_heads=3,
                  dec_ffn=384, vocab_size=1000, max_positions=64)
+# Edge architectures for the stage-isolated parity tests (tests/test_gpu_trocr_stages.py, DESIGN section "TrOCR stage bounds"): one or two
+# layers per side, chosen for the dispatch branches they reach.
+#   A  65 tokens (one key in the second 64-key block), 16-byte LayerNorm path, cross-attention on 256-wide states, split-K 2 / 4, odd vocabulary
+#   B  145 tokens (17 queries in the second 128-query tile), cross-attention on 512-wide states (the default template), split-K 4 / 8
+#   C  257 tokens, scalar LayerNorm path, dense GEMM with partial 256-wide column tiles and K = 320 / 448, key / value form (320-wide states,
+#      17 heads), LayerNorm over more than 1024 decoder channels, unsplit K = 1088, self-attention over more than 64 keys
+STAGE_A = TrOCRSpec(image_size=64, patch_size=8, enc_hidden=256, enc_layers=2, enc_heads=4, enc_ffn=512, dec_hidden=512, dec_layers=2,
+                    dec_heads=8, dec_ffn=1024, vocab_size=1001, max_positions=64, max_length=24)
+STAGE_B = TrOCRSpec(image_size=192, patch_size=16, enc_hidden=512, enc_layers=1, enc_heads=8, enc_ffn=1024, dec_hidden=1024, dec_layers=1,
+                    dec_heads=16, dec_ffn=2048, vocab_size=1000, max_positions=64, max_length=12)
+STAGE_C = TrOCRSpec(image_size=256, patch_size=16, enc_hidden=320, enc_layers=1, enc_heads=5, enc_ffn=448, dec_hidden=1088, dec_layers=1,
+                    dec_heads=17, dec_ffn=1536, vocab_size=1000, max_positions=96, max_length=80)
 
 
 def hf5_key(key):
