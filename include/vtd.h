@@ -124,7 +124,8 @@ int vtd_copy_to_pinned_host(const void* src_dev, void* dst_pinned_host, int64_t 
  * sums5_dev (optional) = the five float64 sums behind them (BCE numerators, sum p*t, sum p, sum t).  thresh_dev / thresh_target_dev
  * may both be null (DiceLoss alone, or a detector run without its threshold branch): that term is then 0.  smooth = DiceLoss.smooth
  * (1e-5).  workspace_dev: vtd_dbloss_workspace_bytes() bytes, caller-owned, one per concurrent call.  fp64 accumulation in a fixed
- * order: bitwise repeatable.  AdamW and the plateau scheduler (trainer.py:107-128) are torch's, as in the reference. */
+ * order: bitwise repeatable.  The plateau scheduler (trainer.py:114-128) is torch's, as in the reference; the AdamW update
+ * (trainer.py:107-112) is torch's by default and vtd_adamw_step below on request. */
 int64_t vtd_dbloss_workspace_bytes(void);
 int vtd_dbloss_forward(const float* prob_dev, const float* thresh_dev, const float* prob_target_dev, const float* thresh_target_dev, int64_t numel,
                        float smooth, void* workspace_dev, float* out4_dev, double* sums5_dev, vtd_stream stream);
@@ -147,6 +148,43 @@ int vtd_dbloss_backward(const float* prob_dev, const float* thresh_dev, const fl
  * numel float32 each, 16-byte aligned.  Integer sums: the same counts on every run.  Errors -2721 (argument), -2722 (alignment). */
 int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev, int64_t numel, float threshold, int64_t* counts4_dev,
                                  vtd_stream stream);
+
+/* ---- AdamW step (app/ml/training/trainer.py:107-112 configure_optimizers: torch.optim.AdamW(self.parameters(), lr, weight_decay)) -------
+ * One multi-tensor pass: every tensor of the table is updated in place, 28 B of HBM traffic per element (p, g, m, v read; p, m, v written).
+ * Per element, all float32, every operation rounded once (no fused multiply-add), in torch's order:
+ *   p1  = p * decay
+ *   m'  = m + one_minus_beta1 * (g - m)
+ *   v'  = v * beta2 + (one_minus_beta2 * g) * g
+ *   den = sqrt(v') / bc2_sqrt + eps
+ *   p'  = p1 - step_size * (m' / den)
+ * with IEEE division and square root and subnormals kept.  The caller forms the scalars in double and rounds each once to float, as torch
+ * does with its Python scalars: decay = 1 - lr * weight_decay, step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step); step
+ * is per tensor (torch keeps one per parameter; a parameter without a gradient does not advance and is simply left out of the table).
+ * tensors: a HOST array of `count` entries whose p / g / m / v are device pointers to n float32 each (parameter, gradient, exp_avg,
+ * exp_avg_sq).  The table travels in kernel arguments, VTD_ADAMW_SLICE tensors a launch (ceil(count / 64) launches: 2 for the 96 tensors
+ * of the ResNet-18 detector): nothing is staged in device memory, nothing has to outlive the call, no host synchronisation, no
+ * allocation, no atomics; a workgroup takes VTD_ADAMW_CHUNK elements of one tensor at a time and the grid depends on the n values only:
+ * bitwise repeatable.  A tensor whose four pointers are all 16-byte aligned moves in 16-byte accesses (n % 4 elements singly); any
+ * other 4-byte aligned tensor (a view that starts mid-row) takes dword accesses with the same results.  Entries with n == 0 are
+ * skipped (their pointers are not looked at).
+ * Errors, all before any launch: -3601 for count < 0, a null tensors / hyper pointer, n < 0 or n >= 2^40, a non-finite or non-positive
+ * bc2_sqrt, a non-finite step_size or hyper-parameter, and, for entries with n > 0, a null pointer or one that is not 4-byte aligned.
+ * count == 0 returns 0 and launches nothing. */
+#define VTD_ADAMW_SLICE 64      /* tensors per launch */
+#define VTD_ADAMW_CHUNK 4096    /* elements one workgroup takes at a time (a multiple of 1024) */
+typedef struct vtd_adamw_tensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t n;
+    float step_size;
+    float bc2_sqrt;
+} vtd_adamw_tensor;   /* 48 bytes */
+typedef struct vtd_adamw_hyper {
+    float decay, one_minus_beta1, beta2, one_minus_beta2, eps;
+} vtd_adamw_hyper;
+int vtd_adamw_step(const vtd_adamw_tensor* tensors, int count, const vtd_adamw_hyper* hyper, vtd_stream stream);
 
 /* ---- DB head training, forward and backward (text_detector.py:58-86 DBHead, both branches, BatchNorm in train or eval mode) ---------
  * Fine-tunes the probability and threshold heads over a frozen trunk and FPN, and forms the gradient of the head's input: the features are P2 (fpn.layer_blocks.3's output, 256

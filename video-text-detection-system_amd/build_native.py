@@ -22,8 +22,9 @@ OBJ_DIR = os.path.join(HERE, f"build_{VARIANT}" if VARIANT else "build")
 # the VGPR form.  Same arithmetic, bit-identical outputs; the 4-wave launches run 2-6 % faster (classed head-entry border tiles 12 %).
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-mfma-vgpr-form",
           "-I" + CSRC] + EXTRA
-# the post-process geometry replays float32 arithmetic in a fixed order: no fused multiply-add there
-PER_FILE = {"postprocess.hip": ["-ffp-contract=off"]}
+# the post-process geometry replays float32 arithmetic in a fixed order: no fused multiply-add there; the AdamW update rounds every
+# operation once, as torch's recurrence is written
+PER_FILE = {"postprocess.hip": ["-ffp-contract=off"], "adamw.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -57,6 +57,7 @@ int vtd_launch_dbloss(const float* prob, const float* thresh, const float* prob_
 int vtd_launch_dbloss_backward(const float* prob, const float* thresh, const float* prob_t, const float* thresh_t, int64_t n, float smooth,
                                const double* sums5, const float* grad_out4, float* grad_prob, float* grad_thresh, hipStream_t stream);
 int vtd_launch_binary_counts(const float* pred, const float* target, int64_t n, float threshold, int64_t* counts4, hipStream_t stream);
+int vtd_launch_adamw(const vtd_adamw_tensor* tensors, int count, const vtd_adamw_hyper* hyper, hipStream_t stream);
 int64_t vtd_dbhead_ws_bytes(int n, int H, int W, int backward);
 int vtd_launch_dbhead_pack(const void* x, int dtype, int n, int H, int W, void* feats, hipStream_t s);
 int vtd_launch_dbhead_forward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, float momentum, float eps,
@@ -1474,6 +1475,8 @@ const char* vtd_strerror(int code) {
         case -3502: return "ResNet block batch-statistics training: misaligned buffer";
         case -3301: return "stem training: invalid argument or unsupported geometry (built: n >= 1, even image height and width >= 2)";
         case -3302: return "stem training: misaligned buffer";
+        case -3601: return "AdamW step: invalid argument (null or not 4-byte aligned pointer, count < 0, n outside [0, 2^40), non-finite scalar, "
+                           "bc2_sqrt <= 0)";
         default: break;
     }
     if (code <= -1000) {
@@ -1506,6 +1509,11 @@ int vtd_dbloss_backward(const float* prob_dev, const float* thresh_dev, const fl
 int vtd_binary_counts_accumulate(const float* pred_dev, const float* target_dev, int64_t numel, float threshold, int64_t* counts4_dev,
                                  vtd_stream stream) {
     return vtd_launch_binary_counts(pred_dev, target_dev, numel, threshold, counts4_dev, (hipStream_t)stream);
+}
+
+// ---- AdamW step (trainer.py:107-112; adamw.hip)
+int vtd_adamw_step(const vtd_adamw_tensor* tensors, int count, const vtd_adamw_hyper* hyper, vtd_stream stream) {
+    return vtd_launch_adamw(tensors, count, hyper, (hipStream_t)stream);
 }
 
 // ---- DB head training (dbhead_train.hip)

@@ -64,6 +64,20 @@ class StemParams(C.Structure):
 
 FpnTaps = C.c_void_p * 4   # padded taps C2, C3, C4, C5
 
+ADAMW_SLICE = 64     # VTD_ADAMW_SLICE of include/vtd.h
+ADAMW_CHUNK = 4096   # VTD_ADAMW_CHUNK
+
+
+class AdamwTensor(C.Structure):
+    """vtd_adamw_tensor of include/vtd.h (48 bytes): device pointers to one parameter's p, g, exp_avg, exp_avg_sq and its per-step scalars"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("step_size", C.c_float),
+                ("bc2_sqrt", C.c_float)]
+
+
+class AdamwHyper(C.Structure):
+    """vtd_adamw_hyper of include/vtd.h"""
+    _fields_ = [(k, C.c_float) for k in ("decay", "one_minus_beta1", "beta2", "one_minus_beta2", "eps")]
+
 
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vtd.h
 SIGNATURES = {
@@ -179,6 +193,7 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p]),
     "vtd_fpn_train_unpack_tap_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_binary_counts_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    "vtd_adamw_step": (C.c_int, [C.POINTER(AdamwTensor), C.c_int, C.POINTER(AdamwHyper), C.c_void_p]),
     "vtd_trocr_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vtd_trocr_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "vtd_trocr_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),

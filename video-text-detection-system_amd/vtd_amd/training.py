@@ -13,12 +13,16 @@ Both run as ONE HBM-bound HIP pass over the maps (include/vtd.h: vtd_dbloss_forw
 scalars are views of one autograd node whose backward is one element-wise HIP pass (vtd_dbloss_backward) that forms what torch autograd
 forms on the reference's graph; targets are constants (a target that requires grad is refused -- torch's BCELoss would differentiate it,
 no caller of the reference does).  The validation metrics are three integer counts per batch (vtd_binary_counts_accumulate), not the
-retained maps.  AdamW and ReduceLROnPlateau are torch's, as in the reference.  pytorch_lightning is not part of this build:
+retained maps.  ReduceLROnPlateau is torch's, as in the reference; the AdamW update is torch's by default and, with
+``TextDetectionLightningModule(..., optimizer="hip")``, one multi-tensor HIP pass per parameter group (``AdamW`` below: vtd_adamw_step,
+csrc/adamw.hip) behind torch.optim.AdamW's own state and interface.  pytorch_lightning is not part of this build:
 ``TextDetectionLightningModule`` is a plain ``nn.Module`` with the reference's step methods and ``ModelTrainer`` is a stub.  Like every
 other product entry there is no CPU fallback (tensors must live on the GPU, the library must be present).
 """
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
@@ -188,6 +192,181 @@ class BinaryMetricCounts:
         return {"precision": p, "recall": r, "f1": f1}
 
 
+# ---- optimiser (trainer.py:107-112) -------------------------------------------------------------------------------------------------
+
+class AdamW(torch.optim.AdamW):
+    """torch.optim.AdamW whose ``step`` is one multi-tensor HIP pass per parameter group (include/vtd.h: vtd_adamw_step): 28 B of HBM
+    traffic per element instead of torch's ten or so passes.  Everything but ``step`` is torch's: ``param_groups``, ``state_dict()`` /
+    ``load_state_dict()``, schedulers; the per-parameter state is what torch writes (``step`` a CPU float32 scalar, ``exp_avg``,
+    ``exp_avg_sq``), so optimiser state dicts move both ways between this class and torch.optim.AdamW; the ``step`` scalars of one
+    group's parameters are 0-d views of one CPU vector, so that a step advances them with one add.  Parameters without a gradient
+    are skipped and their ``step`` does not move; ``lr`` is read from the group at every step.  float32 arithmetic, every operation
+    rounded once (csrc/adamw.hip): the results agree with torch's float32 kernels to rounding, not bit for bit.
+
+    The constructor looks at hyper-parameters only (it can be built around CPU parameters); ``step`` checks the tensors before any
+    launch: a parameter with a gradient must be a contiguous float32 CUDA tensor with a dense contiguous float32 gradient on the same
+    device -- anything else raises ``_native.NativeError`` (no CPU path).  amsgrad, maximize, capturable, differentiable, fused and a
+    tensor ``lr`` are refused, by the constructor and again by every ``step`` (``load_state_dict`` replaces ``param_groups``)."""
+
+    _REFUSED = ("amsgrad", "maximize", "capturable", "differentiable", "fused")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        given = dict(amsgrad=amsgrad, maximize=maximize, capturable=capturable, differentiable=differentiable, fused=fused)
+        for k in self._REFUSED:
+            if given[k]:
+                raise ValueError(f"training.AdamW: {k}=True is not built (the HIP step is plain AdamW); use torch.optim.AdamW for it")
+        if torch.is_tensor(lr):
+            raise ValueError("training.AdamW: a tensor lr is not supported (the step reads lr on the host); pass a float")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=foreach,
+                         capturable=False, differentiable=False, fused=None)
+
+    @property
+    def _tables(self):
+        """group index -> _GroupTable, reused while the group's tensors stay what and where they are.  Not part of the pickled state
+        (torch's Optimizer.__getstate__ keeps defaults, state and param_groups): a copy starts with none."""
+        return self.__dict__.setdefault("_hip_tables", {})
+
+    def _check_group(self, group):
+        for k in self._REFUSED:
+            if group.get(k):
+                raise ValueError(f"training.AdamW: param_groups carry {k}=True (loaded from another optimiser's state dict?): not built")
+        if torch.is_tensor(group["lr"]) or any(torch.is_tensor(b) for b in group["betas"]):
+            raise ValueError("training.AdamW: tensor lr / betas are not supported (the step forms its scalars on the host)")
+
+    @staticmethod
+    def _check_tensor(t, what, device=None, shape=None):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _native.NativeError(f"training.AdamW: {what} is on {t.device if torch.is_tensor(t) else type(t).__name__}: a CUDA (HIP) "
+                                      "tensor is required -- the optimiser step has no CPU path")
+        if t.layout != torch.strided or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _native.NativeError(f"training.AdamW: {what} must be a dense contiguous float32 tensor (got {t.dtype}, {t.layout}, "
+                                      f"contiguous={t.layout == torch.strided and t.is_contiguous()})")
+        if device is not None and t.device != device:
+            raise _native.NativeError(f"training.AdamW: {what} is on {t.device}, its parameter on {device}")
+        if shape is not None and t.shape != shape:
+            raise _native.NativeError(f"training.AdamW: {what} has shape {tuple(t.shape)}, its parameter {tuple(shape)}")
+
+    def _build_table(self, gi, live):
+        """Full checks of the group's parameters and state (created here on first use, as torch.optim.Adam._init_group writes it), then the
+        reused table: p, m, v and n are written once, g and the two per-tensor floats at every step."""
+        dev = live[0].device
+        entries = []
+        for i, p in enumerate(live):
+            self._check_tensor(p, f"parameter {i} of group {gi}")
+            if p.device != dev:
+                raise _native.NativeError(f"training.AdamW: the parameters of group {gi} live on more than one device ({dev}, {p.device})")
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            for k in ("exp_avg", "exp_avg_sq"):
+                self._check_tensor(st.get(k), f"state {k} of parameter {i} of group {gi}", p.device, p.shape)
+            if not torch.is_tensor(st.get("step")) or st["step"].is_cuda or st["step"].dim() != 0:
+                raise _native.NativeError(f"training.AdamW: state step of parameter {i} of group {gi} must be a CPU scalar tensor, as "
+                                          "torch.optim.AdamW keeps it without capturable / fused")
+            entries.append([st, st["exp_avg"], st["exp_avg_sq"], st["step"]])
+        # the step counts of the table's parameters move into ONE CPU float32 vector and every state["step"] becomes a 0-d view of its
+        # element (still a CPU float32 scalar tensor, as torch keeps it): a step advances them with one add instead of one per parameter
+        steps = torch.tensor([float(e[3]) for e in entries], dtype=torch.float32)
+        for i, e in enumerate(entries):
+            e[0]["step"] = e[3] = steps[i]
+        table = (_native.AdamwTensor * len(live))()
+        rec = np.frombuffer(table, dtype=_ADAMW_RECORD)   # the same memory, for whole-column writes
+        rec["p"] = [p.data_ptr() for p in live]
+        rec["m"] = [e[1].data_ptr() for e in entries]
+        rec["v"] = [e[2].data_ptr() for e in entries]
+        rec["n"] = [p.numel() for p in live]
+        t = self._tables[gi] = _GroupTable(tuple(map(id, live)), self.state, entries, rec["p"].tolist(), steps, table, rec, dev)
+        return t
+
+    def _refuse(self, gi, group):
+        """The slow walk that names what the per-step check tripped over."""
+        live = [p for p in group["params"] if p.grad is not None]
+        for i, p in enumerate(live):
+            self._check_tensor(p, f"parameter {i} of group {gi}")
+            self._check_tensor(p.grad, f"the gradient of parameter {i} of group {gi}", p.device, p.shape)
+        raise _native.NativeError(f"training.AdamW: group {gi} holds a tensor the HIP step cannot take")
+
+    def _prepare(self, gi, group):
+        """Checks one group and returns (table, gradients) without launching anything; None when no parameter has a gradient.  Per step
+        and tensor this looks at what can change between steps: the gradient (a new tensor every time: dense and contiguous; its dtype,
+        shape and device torch itself holds to the parameter's), the identity of the parameter and of its state tensors and the parameter's
+        address.  Everything else was checked when the table was built, and any change of those rebuilds it."""
+        self._check_group(group)
+        live, grads = [], []
+        try:
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not g.is_contiguous():   # False for sparse COO; the compressed sparse layouts raise
+                    self._refuse(gi, group)
+                live.append(p)
+                grads.append(g)
+        except RuntimeError as e:
+            if isinstance(e, _native.NativeError):
+                raise
+            self._refuse(gi, group)
+        if not live:
+            return None
+        t = self._tables.get(gi)
+        fresh = t is not None and t.state is self.state and t.ids == tuple(map(id, live))
+        if fresh:
+            get = self.state.get
+            for p, (st, m, v, k), ptr in zip(live, t.entries, t.pptrs):
+                if get(p) is not st or st.get("exp_avg") is not m or st.get("exp_avg_sq") is not v or st.get("step") is not k or p.data_ptr() != ptr:
+                    fresh = False
+                    break
+        if not fresh:
+            t = self._build_table(gi, live)
+        return t, grads
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        # every group and tensor is checked before the first launch
+        work = [(group, w) for group, w in ((group, self._prepare(gi, group)) for gi, group in enumerate(self.param_groups)) if w is not None]
+        if not work:
+            return loss
+        lib = _native.require()
+        for group, (t, grads) in work:
+            lr, (beta1, beta2) = float(group["lr"]), group["betas"]
+            counts = t.steps.add_(1.0).tolist()
+            rec = t.rec
+            rec["g"] = [g.data_ptr() for g in grads]
+            if min(counts) == max(counts):   # the usual case: one step count for the whole group
+                k = counts[0]
+                rec["step_size"], rec["bc2_sqrt"] = lr / (1.0 - beta1 ** k), math.sqrt(1.0 - beta2 ** k)
+            else:
+                rec["step_size"] = [lr / (1.0 - beta1 ** k) for k in counts]
+                rec["bc2_sqrt"] = [math.sqrt(1.0 - beta2 ** k) for k in counts]
+            hyper = _native.AdamwHyper(1.0 - lr * float(group["weight_decay"]), 1.0 - beta1, beta2, 1.0 - beta2, float(group["eps"]))
+            with torch.cuda.device(t.device):
+                _native.check(lib.vtd_adamw_step(t.table, len(grads), C.byref(hyper), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                              "vtd_adamw_step")
+        return loss
+
+
+# vtd_adamw_tensor as a numpy record, to write a column of the table at once
+_ADAMW_RECORD = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"), ("bc2_sqrt", "<f4")])
+assert _ADAMW_RECORD.itemsize == C.sizeof(_native.AdamwTensor) == 48
+
+
+class _GroupTable:
+    """One parameter group's reused vtd_adamw_tensor table and what it was built from (identities of the parameters, of the state dict
+    and of its tensors, the parameters' addresses): any change rebuilds it."""
+    __slots__ = ("ids", "state", "entries", "pptrs", "steps", "table", "rec", "device")
+
+    def __init__(self, *values):
+        for k, v in zip(self.__slots__, values):
+            setattr(self, k, v)
+
+
 # ---- trainer surface (trainer.py:14-30, 32-128, 144-219) ---------------------------------------------------------------------------
 
 class TextDetectionDataset(Dataset):
@@ -215,8 +394,14 @@ class TextDetectionLightningModule(nn.Module):
     product DBNet runs forward-only on the HIP engine).  ``log`` keeps the latest value per name in ``self.logged`` (device tensors
     detached, no sync per step).  Validation keeps the per-batch loss scalars and device counts, never the maps."""
 
-    def __init__(self, model: nn.Module, learning_rate: float = 1e-4, weight_decay: float = 1e-5):
+    OPTIMIZERS = ("torch", "hip")
+
+    def __init__(self, model: nn.Module, learning_rate: float = 1e-4, weight_decay: float = 1e-5, optimizer: str = "torch"):
         super().__init__()
+        if optimizer not in self.OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {self.OPTIMIZERS} (got {optimizer!r}): 'torch' is torch.optim.AdamW as in the "
+                             "reference, 'hip' the same update as one HIP pass per parameter group (training.AdamW)")
+        self.optimizer = optimizer
         self.model = model
         self.learning_rate = learning_rate
         self.weight_decay = weight_decay
@@ -274,7 +459,8 @@ class TextDetectionLightningModule(nn.Module):
         self.log("val_f1", m["f1"])
 
     def configure_optimizers(self):
-        optimizer = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay)
+        cls = AdamW if self.optimizer == "hip" else torch.optim.AdamW
+        optimizer = cls(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay)
         # the reference also passes verbose=True, which torch 2.10 no longer accepts
         scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=5)
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": scheduler, "monitor": "val_loss"}}
