@@ -428,6 +428,32 @@ int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
                                 int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                 const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- The same with layer2's width too (csrc/resblock_bn_train.hip, the same launch functions): vtd_trunk_bn_train_* take the arguments of
+ * vtd_block_bn_train_*, one for one, and build six geometries: layer2's (cin 64, width 128, stride 2, even h_in and w_in, with downsample)
+ * and (cin 128, width 128, stride 1), and the four of vtd_block_bn_train_*; every other geometry is refused with -3701.  This is the family
+ * that later stages (layer1, the stem) join; the older families keep their gates and their bits.  training = 0 hands the call to
+ * vtd_resblock_train_forward / _backward: their bits.  For the four geometries of vtd_block_bn_train_* every output -- y, the statistics, the
+ * running update, every parameter gradient and the dx of either stride -- is the bits of vtd_block_bn_train_*.
+ * The per-channel reductions of a 128-wide z (the statistics' partials and the backward's s1, s2): 32 threads x 4 channels cover the width,
+ * so the 256 threads of a workgroup are eight parts of its r rows.  Part k sums rows ceil(k r / 8) .. ceil((k + 1) r / 8) - 1 in row order
+ * in fp64; the workgroup's partial is ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)); the workgroups -- min(256, ceil(n h w / 256)) of
+ * ceil(n h w / workgroups) consecutive rows, as at the other widths -- are combined in workgroup order (Chan's combination for the
+ * statistics).  Shape-only, no atomics.
+ * The weight gradients of a 128-wide block have one 128-column tile, so each of the block's launches takes its own slab count, the rule of
+ * vtd_resblock_train_*'s 128-wide blocks: ceil(ksz^2 cin / 128) q-tiles (a tap per 64-column group over layer2.0's 64-channel input: K = 576
+ * is 4.5 q-tiles, K = 64 half of one) and min(ceil(512 / q-tiles), ceil(n h w / 1024)) slabs of rows, summed in slab order in fp64.  The
+ * wider blocks keep min(8, ceil(n h w / 4096)) slabs for every launch.
+ * dx_dev is accepted at either stride, as in vtd_block_bn_train_*; layer2.0's is NHWC float32 [n][h_in][w_in][64].  The statistics are still
+ * not fused into the convolution's epilogue: z makes one round trip through HBM per pair and direction.  Bitwise repeatable.
+ * Errors, before any launch: -3701 (argument / unsupported geometry / training outside {0, 1} / training = 1 with n h w < 2 / momentum
+ * outside [0, 1] / dx_dev without dxscale_dev), -3702 (alignment). */
+int64_t vtd_trunk_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_trunk_bn_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               int training, float momentum, float eps, void* workspace_dev, void* y_dev, float* stats_dev, vtd_stream stream);
+int vtd_trunk_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
 /* ---- ResNet stem training with frozen-statistics BatchNorm (csrc/stem_train.hip): pool = maxpool3x3/s2/p1(relu(bn(conv7x7/s2/p3(x)))) on an
  * image x [n,3,height,width]; height and width are the image's, even and at least 2 (the product's 640 is not built in).  hc x wc = height / 2
  * x width / 2 is the conv map, hp x wp = ceil(hc / 2) x ceil(wc / 2) the pooled map.  The running statistics normalise and are never written;

@@ -1,10 +1,12 @@
 // ResNet BasicBlock training with batch-statistics BatchNorm (torch's train() mode: the statistics of the batch normalise, the running
-// statistics are updated in place), forward and backward, for the blocks of ResNet-18's layer3 and layer4: (128 -> 256, stride 2,
-// downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W below is the block's width (256 or
-// 512), a template argument of every kernel.  Two entry families share the launch functions, told apart by their error base as in
-// resblock_train.hip: vtd_resblock_bn_train_* (-3400: layer4's two geometries, no input gradient of the stride-2 block, -3403) and
-// vtd_block_bn_train_* (-3500: the four geometries, the input gradient of either stride).  With training = 0 the entries hand the call to
-// the frozen-statistics path (resblock_train.hip) unchanged: the first family to vtd_basicblock_train_*, the second to vtd_resblock_train_*.
+// statistics are updated in place), forward and backward, for the blocks of ResNet-18's layer2, layer3 and layer4: (64 -> 128, stride 2,
+// downsample), (128 -> 128, stride 1), (128 -> 256, stride 2, downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and
+// (512 -> 512, stride 1).  W below is the block's width (128, 256 or 512), a template argument of every kernel.  Three entry families share
+// the launch functions, told apart by their error base as in resblock_train.hip: vtd_resblock_bn_train_* (-3400: layer4's two geometries,
+// no input gradient of the stride-2 block, -3403), vtd_block_bn_train_* (-3500: layer3's and layer4's four geometries, the input gradient
+// of either stride) and vtd_trunk_bn_train_* (-3700: the six geometries, the input gradient of either stride; the family that later stages
+// join).  With training = 0 the entries hand the call to the frozen-statistics path (resblock_train.hip) unchanged: the first family to
+// vtd_basicblock_train_*, the other two to vtd_resblock_train_*.
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
 //
 // Forward, per convolution + BatchNorm pair (conv1 / bn1, the downsample, conv2 / bn2):
@@ -14,7 +16,7 @@
 //                    width, 4 channels each with 16-byte loads, so the 256 threads are P = 1024 / W parts of the workgroup's r rows: part k
 //                    sums rows ceil(k r / P) .. ceil((k + 1) r / P) - 1 in row order, sums of z and z^2 in fp64.
 //                    W = 512: two halves, lower + upper.  W = 256: four quarters, (q0 + q1) + (q2 + q3) -- the rule of rb_reduce64_kernel.
-//                    Then (count, mean, M2) per channel
+//                    W = 128: eight eighths, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)).  Then (count, mean, M2) per channel
 //   stats finish     one thread per channel: Chan's combination of the partials in workgroup order (fp64) -> mu, biased sigma^2; the running
 //                    values mean <- (1 - m) mean + m mu, var <- (1 - m) var + m sigma^2 M / (M - 1); table {mu, rstd, gamma, beta} [4][W]
 //   apply            relu(((z - mu) rstd) gamma + beta [+ id]) -> ring-padded fp16 tap; the downsample's has no ReLU.  One thread = 8 channels
@@ -26,14 +28,16 @@
 //                    power-of-two multiplier from max_c |gamma rstd| (max |g| + |s1| / M + max |xh| |s2| / M), which bounds |dz|
 //   form             dz = gamma rstd (g - s1 / M - xh s2 / M) in fp32, times the multiplier, as fp16: flat [M][W] and ring-padded
 //   wgrad<3>         G[c][k] = sum_m dz[m][c] x[m][k] on wgrad_mfma.h, min(8, ceil(M / 4096)) slabs; dW = the slabs summed in order in fp64
-//                    with the scale undone: dz carries gamma rstd, no factor follows
+//                    with the scale undone: dz carries gamma rstd, no factor follows.  W = 128 has one column tile, so it takes the rule
+//                    of resblock_train.hip's 128-wide blocks: wgrad<4> over layer2.0's 64-channel input (a tap per 64-column group), wgrad<3>
+//                    otherwise, ceil(ksz^2 cin / 128) q-tiles and per launch min(ceil(512 / q-tiles), ceil(M / 1024)) slabs
 //   dgrad            da1 = conv2^T(dz2): conv_igemm.hip on the raw weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
 //   dx (stride 1)    conv1^T(dz1) the same way, plus g2 brought to the same scale
-//   dx (stride 2)    (vtd_block_bn_train_* only) the construction of resblock_train.hip on the batch-statistics quantities: dz1 goes to the even
-//                    positions of a zeroed ring-padded plane of the input's 2h x 2w pixels (`form` with dil = 2), the stride-1 3x3 dgrad runs
-//                    over that plane on the raw conv1 weights, rotated and transposed.  The downsample's transpose is a 1x1 GEMM of dz_d, the
-//                    downsample BatchNorm's own dz (not g2, not dz2: each pair has its own statistics), on the transposed raw downsample
-//                    weights; it runs right after the downsample pair's `form`, into a buffer of its own, because the dz planes are reused
+//   dx (stride 2)    (vtd_block_bn_train_* and vtd_trunk_bn_train_*) the construction of resblock_train.hip on the batch-statistics
+//                    quantities: dz1 goes to the even positions of a zeroed ring-padded plane of the input's 2h x 2w pixels (`form` with
+//                    dil = 2), the stride-1 3x3 dgrad runs over that plane on the raw conv1 weights, rotated and transposed.  The
+//                    downsample's transpose is a 1x1 GEMM of dz_d, the downsample BatchNorm's own dz (not g2, not dz2: each pair has
+//                    its own statistics), on the transposed raw downsample weights; it runs right after the downsample pair's `form`, into a buffer of its own, because the dz planes are reused
 //                    by bn1.  dz_d carries its own power-of-two multiplier scd[2]; the product is added at the even (row, column) positions
 //                    times sc2[2] sc1[2] / scd[2], which brings it to dz1's scale exactly
 // Nothing divides by gamma or sigma.  No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
@@ -59,8 +63,9 @@ namespace {
 constexpr int BT_THREADS = RB_THREADS;
 constexpr int BT_MAX_RED = 256;
 // error bases: the vtd_resblock_bn_train_* entries (layer4's two geometries, no strided dx) answer -3401 / -3402 / -3403, the
-// vtd_block_bn_train_* entries (four geometries) -3501 / -3502
-constexpr int BT_LEGACY = -3400, BT_GENERAL = -3500;
+// vtd_block_bn_train_* entries (four geometries) -3501 / -3502, the vtd_trunk_bn_train_* entries (six geometries: layer2's 128-wide
+// blocks under this base alone) -3701 / -3702
+constexpr int BT_LEGACY = -3400, BT_GENERAL = -3500, BT_TRUNK = -3700;
 
 typedef double doublex4 __attribute__((ext_vector_type(4)));
 
@@ -74,7 +79,7 @@ struct Geo {
 
 bool make_geo(int n, int hin, int win, int cin, int width, int stride, int base, Geo& g) {
     if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096) return false;
-    if (width != 512 && (base == BT_LEGACY || width != 256)) return false;
+    if (width != 512 && (base == BT_LEGACY || width != 256) && (base != BT_TRUNK || width != 128)) return false;
     if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
     g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.width = width; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w;
@@ -118,7 +123,14 @@ BwdLayout bwd_layout(const Geo& g, bool strided) {
     L.part = take((int64_t)BT_MAX_RED * 2 * W * 8); L.pmax = take((int64_t)BT_MAX_RED * 2 * W * 4);
     L.coef = take(3 * W * 4);
     L.sc = take(3 * 4 * 4);
-    L.slab = take((int64_t)wg_slabs(g.m) * W * 9 * W * 4);
+    int64_t slab = (int64_t)wg_slabs(g.m) * W * 9 * W;
+    if (W == 128) {   // per launch (conv2, conv1, the downsample), as resblock_train.hip sizes it: the largest of the three
+        slab = (int64_t)wg_slabs128(g.m, wg_nqt(3, 128)) * W * 9 * 128;
+        const int64_t c1 = (int64_t)wg_slabs128(g.m, wg_nqt(3, g.cin)) * W * 9 * g.cin, dsl = g.ds ? (int64_t)wg_slabs128(g.m, wg_nqt(1, g.cin)) * W * g.cin : 0;
+        slab = c1 > slab ? c1 : slab;
+        slab = dsl > slab ? dsl : slab;
+    }
+    L.slab = take(slab * 4);
     L.zp = take(strided ? (int64_t)g.n * (g.hin + 2) * (g.win + 2) * W * 2 : 0);
     L.wdt = take(strided ? (int64_t)g.cin * W * 2 : 0);
     L.dst = take(strided ? g.m * g.cin * 4 : 0);
@@ -144,7 +156,7 @@ __global__ __launch_bounds__(BT_THREADS) void bt_pack_kernel(const float* w, int
 }
 
 // the rows [lo, hi) of part `grp` of the P = 1024 / W parts of workgroup `blk`'s r rows: ceil(grp r / P) .. ceil((grp + 1) r / P) - 1.  W = 512:
-// the lower half (the first ceil(r / 2) rows) and the upper; W = 256: four quarters
+// the lower half (the first ceil(r / 2) rows) and the upper; W = 256: four quarters; W = 128: eight eighths
 template <int W>
 __device__ __forceinline__ void bt_rows(int64_t rows, int64_t per, int grp, int64_t& m0, int64_t& m1, int64_t& lo, int64_t& hi) {
     constexpr int P = 4 * BT_THREADS / W;
@@ -156,11 +168,13 @@ __device__ __forceinline__ void bt_rows(int64_t rows, int64_t per, int grp, int6
 }
 
 // the parts of one workgroup, part 0 in registers and the others in LDS [part - 1][value][lane]: lower + upper for two parts,
-// (q0 + q1) + (q2 + q3) for four
+// (q0 + q1) + (q2 + q3) for four, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)) for eight
 template <int P, int L>
 __device__ __forceinline__ double bt_join(double own, double (*sh)[8][L], int v, int j) {
-    if (P == 2) return own + sh[0][v][j];
-    return (own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j]);
+    static_assert(P == 2 || P == 4 || P == 8, "a fixed order is written out for two, four and eight parts");
+    if constexpr (P == 2) return own + sh[0][v][j];
+    else if constexpr (P == 4) return (own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j]);
+    else return ((own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j])) + ((sh[3][v][j] + sh[4][v][j]) + (sh[5][v][j] + sh[6][v][j]));
 }
 
 // z [rows][W] fp32 -> part[g][c] = {count, mean, M2} (fp64).  LDS [part][value][lane]: consecutive lanes, consecutive doubles
@@ -201,6 +215,7 @@ template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_stats_finish_kernel(const double* part, int G, const float* gam, const float* bet, float* rmean, float* rvar,
                                                                      float momentum, float eps, float* tab, float* stats_out) {
     const int c = blockIdx.x * BT_THREADS + threadIdx.x;
+    if (c >= W) return;      // W = 128: half of the one workgroup
     double n = 0.0, mu = 0.0, m2 = 0.0;
     for (int g = 0; g < G; ++g) {
         const double* q = part + ((int64_t)g * W + c) * 3;
@@ -465,7 +480,7 @@ int forward_launches(const void* x, const Geo& g, const vtd_basicblock_params* P
         const int rc = conv_f32(in, ic, hi, wi, ksz, st, wp, z);
         if (rc) return rc;
         hipLaunchKernelGGL(bt_stats_partial_kernel<W>, dim3(g.red), dim3(BT_THREADS), 0, s, (const float*)z, M, g.per, part);
-        hipLaunchKernelGGL(bt_stats_finish_kernel<W>, dim3(W / BT_THREADS), dim3(BT_THREADS), 0, s, (const double*)part, g.red, gam, bet, rmean, rvar, momentum,
+        hipLaunchKernelGGL(bt_stats_finish_kernel<W>, dim3((W + BT_THREADS - 1) / BT_THREADS), dim3(BT_THREADS), 0, s, (const double*)part, g.red, gam, bet, rmean, rvar, momentum,
                            eps, tab + row * 4 * W, stats ? stats + row * 2 * W : (float*)nullptr);
         hipLaunchKernelGGL(bt_apply_kernel<W>, dim3(nblk(M * (W / 8))), dim3(BT_THREADS), 0, s, (const float*)z, M, (const float*)(tab + row * 4 * W), res,
                            relu, g.h, g.w, out);
@@ -487,6 +502,7 @@ int launch_forward(const void* x, int n, int hin, int win, int cin, int width, i
     if (!training)
         return base == BT_LEGACY ? vtd_launch_basicblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s)
                                  : vtd_launch_resblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+    if (width == 128) return forward_launches<128>(x, g, P, momentum, eps, ws, y, stats, s);
     return width == 256 ? forward_launches<256>(x, g, P, momentum, eps, ws, y, stats, s) : forward_launches<512>(x, g, P, momentum, eps, ws, y, stats, s);
 }
 
@@ -525,9 +541,14 @@ int backward_launches(const void* x, const Geo& g, const vtd_basicblock_params* 
     auto wgrad = [&](const half_t* xin, int xc, int hi, int wi, int ksz, int st, const float* scl, float* dw) {
         WgArgs wa;
         wa.a = dzh; wa.lda = W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
-        wa.slab_len = slab_rows(M, S); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
-        hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(ksz * ksz * xc / 128 * S, W / 128), dim3(WG_THREADS), 0, s, wa);
-        hipLaunchKernelGGL(bt_dw_kernel, dim3(W), dim3(BT_THREADS), 0, s, (const float*)slab, S, xc, ksz * ksz, scl, dw);
+        // W = 128: one column tile, so the slabs of each launch by its own q-tiles (the rule of resblock_train.hip's 128-wide blocks)
+        const int nqt = W == 128 ? wg_nqt(ksz, xc) : ksz * ksz * xc / 128, Sl = W == 128 ? wg_slabs128(M, nqt) : S;
+        wa.slab_len = slab_rows(M, Sl); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
+        if (xc & 127)   // layer2.0's 64-channel input: a tap per 64-column group
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<4>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
+        else
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
+        hipLaunchKernelGGL(bt_dw_kernel, dim3(W), dim3(BT_THREADS), 0, s, (const float*)slab, Sl, xc, ksz * ksz, scl, dw);
     };
     // conv^T of a padded dz plane of hp x wp pixels (W channels) into [n hp wp][rows] fp32: the raw weights of a conv with `rows` input
     // channels, rotated and transposed into `panel`
@@ -586,6 +607,7 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
     if (!training)
         return legacy ? vtd_launch_basicblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s)
                       : vtd_launch_resblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+    if (width == 128) return backward_launches<128>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy);
     return width == 256 ? backward_launches<256>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy)
                         : backward_launches<512>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy);
 }
@@ -621,4 +643,20 @@ int vtd_launch_block_bn_backward(const void* x, int n, int hin, int win, int cin
                                  float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
                                  void* scratch, float* dx, float* dxscale, hipStream_t s) {
     return launch_backward(x, n, hin, win, cin, width, stride, P, training, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, BT_GENERAL);
+}
+
+// the six geometries of layer2, layer3 and layer4, with the input gradient of the stride-2 blocks: the family that later stages join
+int64_t vtd_trunk_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(n, hin, win, cin, width, stride, mode, BT_TRUNK);
+}
+
+int vtd_launch_trunk_bn_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                float momentum, float eps, void* ws, void* y, float* stats, hipStream_t s) {
+    return launch_forward(x, n, hin, win, cin, width, stride, P, training, momentum, eps, ws, y, stats, s, BT_TRUNK);
+}
+
+int vtd_launch_trunk_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                 float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
+                                 void* scratch, float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(x, n, hin, win, cin, width, stride, P, training, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, BT_TRUNK);
 }

@@ -1,5 +1,6 @@
 // What the two ResNet BasicBlock training files share (resblock_train.hip: frozen-statistics BatchNorm; resblock_bn_train.hip: batch
-// statistics): the padded-tap helpers, the ReLU mask, the identity add, the argument checks and the convolution descriptor.
+// statistics): the padded-tap helpers, the ReLU mask, the identity add, the weight-gradient slab rules, the argument checks and the
+// convolution descriptor.
 #ifndef VTD_RESBLOCK_COMMON_H
 #define VTD_RESBLOCK_COMMON_H
 #include "vtd_common.h"
@@ -18,6 +19,12 @@ inline unsigned nblk(int64_t items) { return (unsigned)((items + RB_THREADS - 1)
 
 inline int wg_slabs(int64_t rows) { int64_t s = (rows + 4095) / 4096; return (int)(s < 1 ? 1 : s > 8 ? 8 : s); }
 inline int64_t slab_rows(int64_t rows, int s) { return ((rows + s - 1) / s + WG_KC - 1) / WG_KC * WG_KC; }
+// W = 128 (one column tile): the slabs of a launch of `nqt` q-tiles.  Shape-only: 512 workgroups when the rows allow slabs of 1024
+inline int wg_slabs128(int64_t rows, int nqt) {
+    const int64_t want = (512 + nqt - 1) / nqt, can = (rows + 1023) / 1024;
+    return (int)(want < can ? want : can < 1 ? 1 : can);
+}
+inline int wg_nqt(int ksz, int xc) { return (ksz * ksz * xc + 127) / 128; }
 
 // the one-pixel ring of a padded NHWC fp16 tensor of W channels.  One thread = 8 channels of one ring pixel.
 __global__ __launch_bounds__(RB_THREADS) void rb_zero_ring_kernel(half_t* t, int n, int H, int Wd, int W) {

@@ -87,13 +87,6 @@ FwdLayout fwd_layout(const Geo& g) {
     return L;
 }
 
-// W = 128 (one column tile): the slabs of a launch of `nqt` q-tiles.  Shape-only: 512 workgroups when the rows allow slabs of 1024
-inline int wg_slabs128(int64_t rows, int nqt) {
-    const int64_t want = (512 + nqt - 1) / nqt, can = (rows + 1023) / 1024;
-    return (int)(want < can ? want : can < 1 ? 1 : can);
-}
-inline int wg_nqt(int ksz, int xc) { return (ksz * ksz * xc + 127) / 128; }
-
 // `strided`: room for the stride-2 block's input gradient (the zero-inserted plane and the downsample's transposed panel), at the end
 BwdLayout bwd_layout(const Geo& g, bool strided) {
     BwdLayout L;

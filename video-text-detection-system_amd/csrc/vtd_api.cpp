@@ -100,6 +100,12 @@ int vtd_launch_block_bn_forward(const void* x, int n, int hin, int win, int cin,
 int vtd_launch_block_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
                                  float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
                                  void* scratch, float* dx, float* dxscale, hipStream_t s);
+int64_t vtd_trunk_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_trunk_bn_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                float momentum, float eps, void* ws, void* y, float* stats, hipStream_t s);
+int vtd_launch_trunk_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, int training,
+                                 float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp,
+                                 void* scratch, float* dx, float* dxscale, hipStream_t s);
 int vtd_launch_stem_pack_input(const void* x, int dtype, int n, int H, int W, void* tap, hipStream_t s);
 int64_t vtd_stem_ws_bytes(int n, int H, int W, int mode);
 int vtd_launch_stem_forward(const void* x, int n, int H, int W, const vtd_stem_params* P, float eps, void* ws, void* pool, void* idx, hipStream_t s);
@@ -1473,6 +1479,9 @@ const char* vtd_strerror(int code) {
         case -3501: return "ResNet block batch-statistics training: invalid argument or unsupported geometry (built: 128 -> 256 and 256 -> 512 "
                            "stride 2 with even extents, 256 -> 256 and 512 -> 512 stride 1; training = 1 needs n h w >= 2)";
         case -3502: return "ResNet block batch-statistics training: misaligned buffer";
+        case -3701: return "trunk block batch-statistics training: invalid argument or unsupported geometry (built: 64 -> 128, 128 -> 256 and "
+                           "256 -> 512 stride 2 with even extents, 128 -> 128, 256 -> 256 and 512 -> 512 stride 1; training = 1 needs n h w >= 2)";
+        case -3702: return "trunk block batch-statistics training: misaligned buffer";
         case -3301: return "stem training: invalid argument or unsupported geometry (built: n >= 1, even image height and width >= 2)";
         case -3302: return "stem training: misaligned buffer";
         case -3601: return "AdamW step: invalid argument (null or not 4-byte aligned pointer, count < 0, n outside [0, 2^40), non-finite scalar, "
@@ -1654,6 +1663,24 @@ int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
                                 int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                 const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
     return vtd_launch_block_bn_backward(x_dev, n, h_in, w_in, cin, width, stride, params, training, eps, workspace_dev, y_dev, dy_dev, dscale_dev,
+                                        grads, scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+// the six geometries of layer2, layer3 and layer4: the family that later stages join
+int64_t vtd_trunk_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_trunk_bn_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_trunk_bn_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                               int training, float momentum, float eps, void* workspace_dev, void* y_dev, float* stats_dev, vtd_stream stream) {
+    return vtd_launch_trunk_bn_forward(x_dev, n, h_in, w_in, cin, width, stride, params, training, momentum, eps, workspace_dev, y_dev, stats_dev,
+                                       (hipStream_t)stream);
+}
+
+int vtd_trunk_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_basicblock_params* params,
+                                int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
+    return vtd_launch_trunk_bn_backward(x_dev, n, h_in, w_in, cin, width, stride, params, training, eps, workspace_dev, y_dev, dy_dev, dscale_dev,
                                         grads, scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 

@@ -124,7 +124,22 @@ _BLOCK_BN_BUILT = ("basic_block_bn_train (train-mode, batch-statistics BatchNorm
 _TRUNK_BN_STAGES = {("layer4",): "head+fpn+layer4", ("layer3", "layer4"): "head+fpn+layer4+layer3"}
 _TRUNK_BN_BUILT = ("train-mode (batch-statistics) trunk BatchNorm is built for ('layer4',) with trainable='head+fpn+layer4' and for "
                    "('layer3', 'layer4') with trainable='head+fpn+layer4+layer3', on resnet18; the tuple names exactly the residual stages that "
-                   "train; layer2, layer1 and the stem keep frozen statistics")
+                   "train; layer2, layer1 and the stem keep frozen statistics under a tuple; with layer2 too the spellings are "
+                   "forward_padded(..., trunk_batch_stats=('layer2', 'layer3', 'layer4')) and DBNet(trainable='head+fpn+layer4+layer3+layer2', "
+                   "trunk_bn='trained')")
+# the same on the vtd_trunk_bn_train_* entries, the family later stages join: layer2's two geometries too
+_TRUNK_BLOCK_BN_GEOMETRIES = ((64, 128, 2, True), (128, 128, 1, False)) + _BLOCK_BN_GEOMETRIES
+_TRUNK_BLOCK_BN_BUILT = ("trunk_block_bn_train (train-mode, batch-statistics BatchNorm) is built for the BasicBlocks of ResNet-18's layer2, layer3 and "
+                         "layer4 (64 -> 128, 128 -> 256 and 256 -> 512 stride 2 with downsample, 128 -> 128, 256 -> 256 and 512 -> 512 stride 1); "
+                         "layer1, the stem and Bottleneck blocks keep frozen statistics")
+# the stage tuples forward_padded's trunk_batch_stats takes; the last is the layer2 -> layer3 -> layer4 -> FPN -> head node, which DBNet spells
+# trunk_bn="trained"
+_NODE_BN_STAGES = (("layer4",), ("layer3", "layer4"), ("layer2", "layer3", "layer4"))
+# DBNet's trunk_bn="trained": every residual stage the mode trains runs its BatchNorms in train mode
+_TRAINED_BN_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2")
+_TRAINED_BN_BUILT = ("trunk_bn='trained' (train-mode, batch-statistics BatchNorm in every residual stage the mode trains) is built for "
+                     "trainable='head+fpn+layer4', 'head+fpn+layer4+layer3' and 'head+fpn+layer4+layer3+layer2' on resnet18; layer1 and the stem "
+                     "keep frozen statistics")
 
 
 def _block_bn_check(block, geometries=_BN_TRAIN_GEOMETRIES, built=_BN_TRAIN_BUILT):
@@ -188,7 +203,24 @@ def basic_block_bn_train(block, x):
     return _basic_block_bn_train(block, x, bns, general=True)
 
 
-def _basic_block_bn_train(block, x, bns, general=False):
+def trunk_block_bn_train(block, x):
+    """``basic_block_bn_train`` on the vtd_trunk_bn_train_* entries, the family later stages join: layer2's two geometries too (64 -> 128 at
+    stride 2 with downsample and even extents, 128 -> 128 at stride 1), six in all.  The same module semantics: ``block.training`` selects
+    batch or frozen statistics, the block's BatchNorms need one fixed momentum, the running statistics are updated in place and
+    ``num_batches_tracked`` advances in train mode, and the result is differentiable w.r.t. the block's learnable tensors and w.r.t. ``x``
+    at either stride.  For the four geometries of layer3 and layer4 every output is the bits of ``basic_block_bn_train``; in ``eval()``
+    mode it gives the bits of ``basic_block_train(block, x)`` and writes no buffer."""
+    if not isinstance(block, BasicBlock):
+        raise RuntimeError("trunk_block_bn_train: Bottleneck training is not built; " + _TRUNK_BLOCK_BN_BUILT)
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != block.conv1.in_channels:
+        raise ValueError(f"BasicBlock input must be a [n,{block.conv1.in_channels},H,W] tensor")
+    bns = _block_bn_check(block, _TRUNK_BLOCK_BN_GEOMETRIES, _TRUNK_BLOCK_BN_BUILT)   # what is built, before anything about the device
+    if not x.is_cuda:
+        raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    return _basic_block_bn_train(block, x, bns, general=True, entry=_TRUNK_BN)
+
+
+def _basic_block_bn_train(block, x, bns, general=False, entry=None):
     (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=general)
     n, _, hin, win = x.shape
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
@@ -200,7 +232,7 @@ def _basic_block_bn_train(block, x, bns, general=False):
                            "built with batch-statistics BatchNorm; pass x.detach()")
     src = x if x.requires_grad and torch.is_grad_enabled() else None
     out = _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats),
-                              _BLOCK_BN if general else _RESBLOCK_BN, (bool(block.training), float(bns[0].momentum)), *learn)
+                              entry or (_BLOCK_BN if general else _RESBLOCK_BN), (bool(block.training), float(bns[0].momentum)), *learn)
     if block.training:
         with torch.no_grad():
             for bn in bns:
@@ -315,7 +347,12 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False):
-        """`trunk_batch_stats` may also be a tuple or list of stage names.  ("layer4",) means what True means.  ("layer3", "layer4") goes with
+        """`trunk_batch_stats=("layer2", "layer3", "layer4")` goes with the tap [C2], `layer2`, `layer3`, `layer4` and `head` and nothing lower:
+        the layer2 -> layer3 -> layer4 -> FPN -> head node with all six blocks on the vtd_trunk_bn_train_* entries, in one mode (train() or
+        eval()) with one momentum and one eps, else ValueError before the device is looked at.  layer3.0 and layer4.0 form their input
+        gradients (dC3 and dC4 are those plus the FPN's); layer2.0 forms none.
+
+        `trunk_batch_stats` may also be a tuple or list of stage names.  ("layer4",) means what True means.  ("layer3", "layer4") goes with
         taps [C2, C3], `layer3`, `layer4` and `head` and nothing lower: the four blocks run on the vtd_block_bn_train_* entries, in one mode
         (train() or eval()) with one momentum and one eps, else ValueError; layer4.0 forms its input gradient (dz1 through the strided dgrad
         plus the downsample's transpose of its own dz), which is combined with the FPN's dC4; layer3.0 forms none.  Any other tuple raises
@@ -358,7 +395,7 @@ class FeaturePyramidNetwork(nn.Module):
         bn_stages = ()
         if isinstance(trunk_batch_stats, (tuple, list)):
             bn_stages = tuple(trunk_batch_stats)
-            if not any(bn_stages == stages for stages in _TRUNK_BN_STAGES):      # no hashing: any tuple may come
+            if not any(bn_stages == stages for stages in _NODE_BN_STAGES):      # no hashing: any tuple may come
                 raise ValueError(f"forward_padded(..., trunk_batch_stats={trunk_batch_stats!r}): " + _TRUNK_BN_BUILT)
         elif trunk_batch_stats:
             bn_stages = ("layer4",)
@@ -367,6 +404,9 @@ class FeaturePyramidNetwork(nn.Module):
         if len(bn_stages) == 2 and (layer4 is None or layer3 is None or any(m is not None for m in (layer2, layer1, stem))):
             raise ValueError("forward_padded(..., trunk_batch_stats=('layer3', 'layer4')) is the layer3 -> layer4 -> FPN -> head node on the taps "
                              "[C2, C3]: it needs layer3, layer4 and the head and takes no lower stage; " + _TRUNK_BN_BUILT)
+        if len(bn_stages) == 3 and (layer4 is None or layer3 is None or layer2 is None or layer1 is not None or stem is not None):
+            raise ValueError("forward_padded(..., trunk_batch_stats=('layer2', 'layer3', 'layer4')) is the layer2 -> layer3 -> layer4 -> FPN -> head "
+                             "node on the tap [C2]: it needs layer2, layer3, layer4 and the head and takes no lower stage; " + _TRUNK_BN_BUILT)
         if stem is not None or any(m is not None for m in layers):
             return self._forward_padded_trunk(taps, head, layers, stem, bn_stages)
         if not isinstance(taps, (list, tuple)) or len(taps) != 4:
@@ -390,7 +430,8 @@ class FeaturePyramidNetwork(nn.Module):
     def _forward_padded_trunk(self, taps, head, layers, stem, bn_stages):
         """forward_padded with trunk stages: `layers` is (layer1, layer2, layer3, layer4), the node starts at the lowest one given (with `stem`:
         at the stem) and needs every stage above it and the head.  `bn_stages`: () or the stages (all of the node's) that run with batch
-        statistics, ("layer4",) on the vtd_resblock_bn_train_* entries or ("layer3", "layer4") on vtd_block_bn_train_*."""
+        statistics, ("layer4",) on the vtd_resblock_bn_train_* entries, ("layer3", "layer4") on vtd_block_bn_train_* or ("layer2", "layer3",
+        "layer4") on vtd_trunk_bn_train_*."""
         low = 0 if stem is not None else next(i for i, m in enumerate(layers) if m is not None)
         above = _STAGES[0 if stem is not None else low + 1:]
         if head is None or any(m is None for m in layers[4 - len(above):]):
@@ -398,11 +439,16 @@ class FeaturePyramidNetwork(nn.Module):
                              + ", ".join(st.name for st in above) + (" and " if above else "") + "the DBHead too")
         if stem is not None and (not isinstance(stem, (list, tuple)) or len(stem) != 2):
             raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
-        deep_bn = len(bn_stages) == 2
-        if deep_bn:      # the plan is node-wide: one eps over the four blocks (one mode and one momentum are checked below)
+        if len(bn_stages) == 2:      # the plan is node-wide: one eps over the four blocks (one mode and one momentum are checked below)
             eps_all = {m.eps for layer in layers[2:] for m in layer.modules() if isinstance(m, nn.BatchNorm2d)}
             if len(eps_all) > 1:
                 raise ValueError("layer3's and layer4's four blocks must have one BatchNorm eps")
+        if len(bn_stages) == 3:      # the same over the six blocks, with the mode and the momentum: all before the device is looked at
+            bnm = [m for layer in layers[1:] for m in layer.modules() if isinstance(m, nn.BatchNorm2d)]
+            if len({m.eps for m in bnm}) > 1:
+                raise ValueError("layer2's, layer3's and layer4's six blocks must have one BatchNorm eps")
+            if len({m.training for m in bnm}) > 1 or any(m.momentum is None or m.momentum != bnm[0].momentum for m in bnm):
+                raise ValueError("layer2's, layer3's and layer4's six blocks must be in one mode (train() or eval()) with one fixed BatchNorm momentum")
         # the taps the node reads: the FPN levels below the lowest stage's output, the last of them that stage's input; layer1 reads the pooled
         # stem output and the stem the image, neither an FPN level
         names = ["image"] if stem is not None else [st.tap for st in _STAGES[1:low + 1]] or [_STAGES[0].tap]
@@ -433,10 +479,10 @@ class FeaturePyramidNetwork(nn.Module):
         bn, bbns = None, []
         if bn_stages:
             blocks = [blk for o in ops for blk in o[0]]      # the node's stages are exactly bn_stages (forward_padded)
-            check = (_BLOCK_BN_GEOMETRIES, _BLOCK_BN_BUILT) if deep_bn else ()
+            check = ((), (_BLOCK_BN_GEOMETRIES, _BLOCK_BN_BUILT), (_TRUNK_BLOCK_BN_GEOMETRIES, _TRUNK_BLOCK_BN_BUILT))[len(bn_stages) - 1]
             bbns = [b for blk in blocks for b in _block_bn_check(blk, *check)]
             if any(blk.training != blocks[0].training for blk in blocks) or any(b.momentum != bbns[0].momentum for b in bbns):
-                raise ValueError(("layer3's and layer4's four" if deep_bn else "layer4's two") +
+                raise ValueError(("layer4's two", "layer3's and layer4's four", "layer2's, layer3's and layer4's six")[len(bn_stages) - 1] +
                                  " blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
             n, _, h5, w5 = outs[-1]
             if blocks[0].training and n * h5 * w5 < 2:
@@ -446,7 +492,7 @@ class FeaturePyramidNetwork(nn.Module):
         for _, geoms, _, learn, stats in ops:
             for g, lr, s in zip(geoms, learn, stats):
                 # a node of one stage runs on that stage's own entry family, as forward_<stage>_padded does; a deeper one on the block's by width
-                entry = (_BLOCK_BN if deep_bn else _RESBLOCK_BN) if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
+                entry = (_RESBLOCK_BN, _BLOCK_BN, _TRUNK_BN)[len(bn_stages) - 1] if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
                 blocks.append((_BlockPlan(g, s, entry, len(lr)), lr))
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, tuple(b for b, _ in blocks), beps, bn)
         out = self._run_node(head, bns, plan, *slearn, *(t for _, lr in blocks for t in lr), *params, *hparams)
@@ -782,6 +828,8 @@ _RESBLOCK = "vtd_resblock_train"       # the entry family of the six geometries 
 _BLOCK64 = "vtd_block64_train"         # the entry family of layer1's 64 -> 64 block
 _RESBLOCK_BN = "vtd_resblock_bn_train"   # layer4's two geometries with batch-statistics BatchNorm (csrc/resblock_bn_train.hip)
 _BLOCK_BN = "vtd_block_bn_train"         # layer3's and layer4's four with batch-statistics BatchNorm, and the strided dx (the same file)
+_TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two as well, six in all: the family later stages join (the same file)
+_BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
 def _block_entry(geom):
@@ -795,7 +843,7 @@ def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None)
     parameters, and the result has a third member: the batch
     statistics [3,2,width] fp32 -- mu and the biased variance of bn1, bn2 and the downsample's BatchNorm; rows the call does not write are
     NaN.  In training mode the running statistics in `stats` are then updated in place."""
-    entry = entry if bn is None or entry == _BLOCK_BN else _RESBLOCK_BN
+    entry = entry if bn is None or entry in _BN_FAMILIES else _RESBLOCK_BN
     C, _native, lib, ws = _native_workspace(entry + "_workspace_bytes", (*geom, 0), tap.device)
     n, hin, win, cin, width, stride = geom
     y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
@@ -813,7 +861,7 @@ def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx
     dx is NHWC fp32 [n,h_in,w_in,cin] times dxscale[0], or None.  With `bn` = (training, momentum) it is vtd_resblock_bn_train_backward,
     which takes the mode after the parameters and forms dx for the stride-1 block only, or when `entry` names that family
     vtd_block_bn_train_backward, which forms dx for either stride."""
-    entry = entry if bn is None or entry == _BLOCK_BN else _RESBLOCK_BN
+    entry = entry if bn is None or entry in _BN_FAMILIES else _RESBLOCK_BN
     grads = [torch.empty_like(p) for p in learn]
     C, _native, lib, scratch = _native_workspace(entry + "_workspace_bytes", (*geom, 1), tap.device)
     n, hin, win, cin, width, stride = geom
@@ -1247,8 +1295,14 @@ class DBNet(_EngineOwner, nn.Module):
         self.set_trainable(trainable, trunk_bn)
 
     def set_trainable(self, trainable, trunk_bn=None):
-        """`trunk_bn` ("frozen", the default, "batch", or a tuple of stage names; None keeps the current value) is the mode of the trained trunk
-        stages' BatchNorms.  A tuple names exactly the residual stages the mode trains, else ValueError: ("layer4",) goes with
+        """`trunk_bn` ("frozen", the default, "batch", "trained", or a tuple of stage names; None keeps the current value) is the mode of the
+        trained trunk stages' BatchNorms.  "trained" (resnet18 with trainable="head+fpn+layer4", "head+fpn+layer4+layer3" or
+        "head+fpn+layer4+layer3+layer2"; anything else raises ValueError and leaves the network as it was): every residual stage the mode
+        trains runs its BatchNorms in train mode.  On the first two modes it behaves as the tuples ("layer4",) and ("layer3", "layer4") do.  On
+        the third the trunk engine gives C2 as with "frozen", then layer2, layer3 and layer4 run on the vtd_trunk_bn_train_* entries --
+        backbone.5 .. backbone.7's fifteen BatchNorms normalise with the statistics of the batch, and their 30 running buffers and 15 counters
+        move every step; a following eval() forward rebuilds the inference engine on the new statistics.
+        A tuple names exactly the residual stages the mode trains, else ValueError: ("layer4",) goes with
         trainable="head+fpn+layer4" and is equivalent to "batch"; ("layer3", "layer4") goes with trainable="head+fpn+layer4+layer3" on resnet18:
         the trunk engine gives C2 and C3 as with "frozen", then layer3 and layer4 run on the vtd_block_bn_train_* entries -- backbone.6's and
         backbone.7's ten BatchNorms normalise with the statistics of the batch, and their 20 running buffers and 10 counters move every step.
@@ -1301,8 +1355,10 @@ class DBNet(_EngineOwner, nn.Module):
             fits = next((mode for stages, mode in _TRUNK_BN_STAGES.items() if stages == bn_mode), None)      # no hashing: any tuple may come
             if self.backbone_name != "resnet18" or fits is None or fits != trainable:
                 raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r} on {self.backbone_name}: " + _TRUNK_BN_BUILT)
-        elif bn_mode not in ("frozen", "batch"):
-            raise ValueError(f"trunk_bn must be 'frozen' or 'batch', got {bn_mode!r}")
+        elif not isinstance(bn_mode, str) or bn_mode not in ("frozen", "batch", "trained"):
+            raise ValueError(f"trunk_bn must be 'frozen' or 'batch' (or 'trained', or a tuple of stage names), got {bn_mode!r}")
+        if bn_mode == "trained" and (self.backbone_name != "resnet18" or trainable not in _TRAINED_BN_MODES):
+            raise ValueError(f"trunk_bn='trained' with trainable={trainable!r} on {self.backbone_name}: " + _TRAINED_BN_BUILT)
         if bn_mode == "batch" and trainable != "head+fpn+layer4":
             raise ValueError(f"trunk_bn='batch' with trainable={trainable!r}: train-mode (batch-statistics) trunk BatchNorm is built for layer4 only, "
                              "that is for trainable='head+fpn+layer4' on resnet18; layer3, layer2, layer1 and the stem keep frozen statistics")
@@ -1460,6 +1516,8 @@ class DBNet(_EngineOwner, nn.Module):
         # trunk_bn="batch" is the layer4 mode's alone and a tuple names the mode's own stages (set_trainable): the running statistics of those
         # stages move too; mark_dirty below covers them
         bn_mode = getattr(self, "trunk_bn", "frozen")
+        if bn_mode == "trained":      # every stage the mode trains (set_trainable: layer2 at the lowest); the three-stage tuple is the new node
+            bn_mode = tuple(stages)
         out = self.fpn.forward_padded(taps, head=self.head, trunk_batch_stats=bn_mode if isinstance(bn_mode, tuple) else bn_mode == "batch", **stages)
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
