@@ -430,9 +430,9 @@ int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
 
 /* ---- The same with layer2's width too (csrc/resblock_bn_train.hip, the same launch functions): vtd_trunk_bn_train_* take the arguments of
  * vtd_block_bn_train_*, one for one, and build six geometries: layer2's (cin 64, width 128, stride 2, even h_in and w_in, with downsample)
- * and (cin 128, width 128, stride 1), and the four of vtd_block_bn_train_*; every other geometry is refused with -3701.  This is the family
- * that later stages (layer1, the stem) join; the older families keep their gates and their bits.  training = 0 hands the call to
- * vtd_resblock_train_forward / _backward: their bits.  For the four geometries of vtd_block_bn_train_* every output -- y, the statistics, the
+ * and (cin 128, width 128, stride 1), and the four of vtd_block_bn_train_* (and layer1's, below); every other geometry is refused with
+ * -3701.  This is the family that later stages (layer1: below; the stem) join; the older families keep their gates and their bits.
+ * training = 0 hands the call to vtd_resblock_train_forward / _backward: their bits.  For the four geometries of vtd_block_bn_train_* every output -- y, the statistics, the
  * running update, every parameter gradient and the dx of either stride -- is the bits of vtd_block_bn_train_*.
  * The per-channel reductions of a 128-wide z (the statistics' partials and the backward's s1, s2): 32 threads x 4 channels cover the width,
  * so the 256 threads of a workgroup are eight parts of its r rows.  Part k sums rows ceil(k r / 8) .. ceil((k + 1) r / 8) - 1 in row order
@@ -445,6 +445,21 @@ int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
  * wider blocks keep min(8, ceil(n h w / 4096)) slabs for every launch.
  * dx_dev is accepted at either stride, as in vtd_block_bn_train_*; layer2.0's is NHWC float32 [n][h_in][w_in][64].  The statistics are still
  * not fused into the convolution's epilogue: z makes one round trip through HBM per pair and direction.  Bitwise repeatable.
+ * A seventh geometry, ResNet-18's layer1: (cin 64, width 64, stride 1, identity: ds_* ignored).  The gate names it alone: (64, 64, 2) and
+ * (32, 64, 2) are refused with -3701, and the older families keep refusing (64, 64, 1) with -3401 / -3501.  training = 0 hands the call to
+ * vtd_block64_train_forward / _backward (the frozen 64-wide path): their bits, nothing written; the workspace query answers at least
+ * vtd_block64_train_workspace_bytes, so either value of `training` runs in one allocation.  training = 1 is the batch path of the other
+ * widths -- raw weights rounded to fp16 per call, z kept in fp32, stats_dev rows 0 and 1 (row 2 untouched), the running update with the
+ * unbiased variance, the full BatchNorm backward, dx_dev (optional) as NHWC float32 [n][h][w][64] -- with the convolutions and the dgrad at 64
+ * output channels, as the frozen 64-wide block runs them.
+ * The per-channel reductions of a 64-wide z: 16 threads x 4 channels cover the width, so the 256 threads of a workgroup are sixteen parts of
+ * its r rows.  Part k sums rows ceil(k r / 16) .. ceil((k + 1) r / 16) - 1 in row order in fp64 (a part without rows, r < 16, contributes
+ * exact zeros); the workgroup's partial is the balanced pairwise tree, the eight-part order on each half and then lower + upper:
+ * (((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7))) + (((q8 + q9) + (q10 + q11)) + ((q12 + q13) + (q14 + q15))); workgroups and their
+ * combination as at the other widths.
+ * Its two weight-gradient launches (conv2 and conv1, K = 9 x 64 = 576) run the 64-row tile on dz [n h w][64], which already carries gamma
+ * rstd, by the slab rule of vtd_block64_train_*: five q-tiles, min(ceil(512 / 5), ceil(n h w / 1024)) slabs of [64][576] floats, summed in
+ * slab order in fp64.  The statistics stay unfused from the convolution's epilogue at this width too.
  * Errors, before any launch: -3701 (argument / unsupported geometry / training outside {0, 1} / training = 1 with n h w < 2 / momentum
  * outside [0, 1] / dx_dev without dxscale_dev), -3702 (alignment). */
 int64_t vtd_trunk_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);

@@ -1,12 +1,13 @@
 // ResNet BasicBlock training with batch-statistics BatchNorm (torch's train() mode: the statistics of the batch normalise, the running
-// statistics are updated in place), forward and backward, for the blocks of ResNet-18's layer2, layer3 and layer4: (64 -> 128, stride 2,
-// downsample), (128 -> 128, stride 1), (128 -> 256, stride 2, downsample), (256 -> 256, stride 1), (256 -> 512, stride 2, downsample) and
-// (512 -> 512, stride 1).  W below is the block's width (128, 256 or 512), a template argument of every kernel.  Three entry families share
-// the launch functions, told apart by their error base as in resblock_train.hip: vtd_resblock_bn_train_* (-3400: layer4's two geometries,
-// no input gradient of the stride-2 block, -3403), vtd_block_bn_train_* (-3500: layer3's and layer4's four geometries, the input gradient
-// of either stride) and vtd_trunk_bn_train_* (-3700: the six geometries, the input gradient of either stride; the family that later stages
-// join).  With training = 0 the entries hand the call to the frozen-statistics path (resblock_train.hip) unchanged: the first family to
-// vtd_basicblock_train_*, the other two to vtd_resblock_train_*.
+// statistics are updated in place), forward and backward, for the blocks of ResNet-18's layer1, layer2, layer3 and layer4: (64 -> 64,
+// stride 1), (64 -> 128, stride 2, downsample), (128 -> 128, stride 1), (128 -> 256, stride 2, downsample), (256 -> 256, stride 1),
+// (256 -> 512, stride 2, downsample) and (512 -> 512, stride 1).  W below is the block's width (64, 128, 256 or 512), a template argument
+// of every kernel.  Three entry families share the launch functions, told apart by their error base as in resblock_train.hip:
+// vtd_resblock_bn_train_* (-3400: layer4's two geometries, no input gradient of the stride-2 block, -3403), vtd_block_bn_train_* (-3500:
+// layer3's and layer4's four geometries, the input gradient of either stride) and vtd_trunk_bn_train_* (-3700: the seven geometries, layer1's
+// (64 -> 64, stride 1) and layer2's two under this base alone, the input gradient of either stride; the family that the stem joins later).
+// With training = 0 the entries hand the call to the frozen-statistics path (resblock_train.hip) unchanged: the first family to
+// vtd_basicblock_train_*, the other two to vtd_resblock_train_*, and the 64-wide geometry to vtd_block64_train_*.
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn2(conv2(relu(bn1(conv1(x))))) + id), id = x or ds_bn(ds(x)).
 //
 // Forward, per convolution + BatchNorm pair (conv1 / bn1, the downsample, conv2 / bn2):
@@ -16,7 +17,10 @@
 //                    width, 4 channels each with 16-byte loads, so the 256 threads are P = 1024 / W parts of the workgroup's r rows: part k
 //                    sums rows ceil(k r / P) .. ceil((k + 1) r / P) - 1 in row order, sums of z and z^2 in fp64.
 //                    W = 512: two halves, lower + upper.  W = 256: four quarters, (q0 + q1) + (q2 + q3) -- the rule of rb_reduce64_kernel.
-//                    W = 128: eight eighths, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)).  Then (count, mean, M2) per channel
+//                    W = 128: eight eighths, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)).  W = 64: sixteen parts of 16 lanes, the
+//                    eight-part order on each half, then lower + upper: (((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7))) +
+//                    (((q8 + q9) + (q10 + q11)) + ((q12 + q13) + (q14 + q15))).  A part without rows (r < P) adds exact zeros.
+//                    Then (count, mean, M2) per channel
 //   stats finish     one thread per channel: Chan's combination of the partials in workgroup order (fp64) -> mu, biased sigma^2; the running
 //                    values mean <- (1 - m) mean + m mu, var <- (1 - m) var + m sigma^2 M / (M - 1); table {mu, rstd, gamma, beta} [4][W]
 //   apply            relu(((z - mu) rstd) gamma + beta [+ id]) -> ring-padded fp16 tap; the downsample's has no ReLU.  One thread = 8 channels
@@ -31,6 +35,9 @@
 //                    with the scale undone: dz carries gamma rstd, no factor follows.  W = 128 has one column tile, so it takes the rule
 //                    of resblock_train.hip's 128-wide blocks: wgrad<4> over layer2.0's 64-channel input (a tap per 64-column group), wgrad<3>
 //                    otherwise, ceil(ksz^2 cin / 128) q-tiles and per launch min(ceil(512 / q-tiles), ceil(M / 1024)) slabs
+//   wgrad<5>         W = 64 (layer1): the 64-row tile over dz [M][64] (lda = 64) and the 64-channel input, K = 576 = 5 q-tiles for conv2
+//                    and conv1 alike, min(ceil(512 / 5), ceil(M / 1024)) slabs of [64][576] floats: the rule of resblock_train.hip's
+//                    64-wide block
 //   dgrad            da1 = conv2^T(dz2): conv_igemm.hip on the raw weights rotated by 180 degrees and transposed; g1 = da1 (a1 > 0)
 //   dx (stride 1)    conv1^T(dz1) the same way, plus g2 brought to the same scale
 //   dx (stride 2)    (vtd_block_bn_train_* and vtd_trunk_bn_train_*) the construction of resblock_train.hip on the batch-statistics
@@ -51,6 +58,13 @@ int vtd_launch_basicblock_backward(const void* x, int n, int hin, int win, int c
                                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
                                    float* dx, float* dxscale, hipStream_t s);
 
+int64_t vtd_block64_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_block64_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
+                               void* y, hipStream_t s);
+int vtd_launch_block64_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
+                                const void* ws, const void* y, const float* dy, const float* dscale, const vtd_basicblock_params* Gp, void* scratch,
+                                float* dx, float* dxscale, hipStream_t s);
+
 int64_t vtd_resblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
 int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
                                 void* y, hipStream_t s);
@@ -63,8 +77,8 @@ namespace {
 constexpr int BT_THREADS = RB_THREADS;
 constexpr int BT_MAX_RED = 256;
 // error bases: the vtd_resblock_bn_train_* entries (layer4's two geometries, no strided dx) answer -3401 / -3402 / -3403, the
-// vtd_block_bn_train_* entries (four geometries) -3501 / -3502, the vtd_trunk_bn_train_* entries (six geometries: layer2's 128-wide
-// blocks under this base alone) -3701 / -3702
+// vtd_block_bn_train_* entries (four geometries) -3501 / -3502, the vtd_trunk_bn_train_* entries (seven geometries: layer2's 128-wide
+// blocks and layer1's 64-wide block under this base alone) -3701 / -3702
 constexpr int BT_LEGACY = -3400, BT_GENERAL = -3500, BT_TRUNK = -3700;
 
 typedef double doublex4 __attribute__((ext_vector_type(4)));
@@ -79,8 +93,12 @@ struct Geo {
 
 bool make_geo(int n, int hin, int win, int cin, int width, int stride, int base, Geo& g) {
     if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096) return false;
-    if (width != 512 && (base == BT_LEGACY || width != 256) && (base != BT_TRUNK || width != 128)) return false;
-    if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
+    if (width == 64) {   // layer1's block alone, written out: the rule below would admit (32, 64, 2)
+        if (base != BT_TRUNK || cin != 64 || stride != 1) return false;
+    } else {
+        if (width != 512 && (base == BT_LEGACY || width != 256) && (base != BT_TRUNK || width != 128)) return false;
+        if (!((cin == width / 2 && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == width && stride == 1))) return false;
+    }
     g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.width = width; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w;
     g.ds = stride == 2;
@@ -124,6 +142,7 @@ BwdLayout bwd_layout(const Geo& g, bool strided) {
     L.coef = take(3 * W * 4);
     L.sc = take(3 * 4 * 4);
     int64_t slab = (int64_t)wg_slabs(g.m) * W * 9 * W;
+    if (W == 64) slab = (int64_t)wg_slabs128(g.m, wg_nqt(3, 64)) * 64 * 9 * 64;   // conv2 and conv1 alike: 5 q-tiles, slab [64][576]
     if (W == 128) {   // per launch (conv2, conv1, the downsample), as resblock_train.hip sizes it: the largest of the three
         slab = (int64_t)wg_slabs128(g.m, wg_nqt(3, 128)) * W * 9 * 128;
         const int64_t c1 = (int64_t)wg_slabs128(g.m, wg_nqt(3, g.cin)) * W * 9 * g.cin, dsl = g.ds ? (int64_t)wg_slabs128(g.m, wg_nqt(1, g.cin)) * W * g.cin : 0;
@@ -156,7 +175,7 @@ __global__ __launch_bounds__(BT_THREADS) void bt_pack_kernel(const float* w, int
 }
 
 // the rows [lo, hi) of part `grp` of the P = 1024 / W parts of workgroup `blk`'s r rows: ceil(grp r / P) .. ceil((grp + 1) r / P) - 1.  W = 512:
-// the lower half (the first ceil(r / 2) rows) and the upper; W = 256: four quarters; W = 128: eight eighths
+// the lower half (the first ceil(r / 2) rows) and the upper; W = 256: four quarters; W = 128: eight eighths; W = 64: sixteen parts
 template <int W>
 __device__ __forceinline__ void bt_rows(int64_t rows, int64_t per, int grp, int64_t& m0, int64_t& m1, int64_t& lo, int64_t& hi) {
     constexpr int P = 4 * BT_THREADS / W;
@@ -168,13 +187,20 @@ __device__ __forceinline__ void bt_rows(int64_t rows, int64_t per, int grp, int6
 }
 
 // the parts of one workgroup, part 0 in registers and the others in LDS [part - 1][value][lane]: lower + upper for two parts,
-// (q0 + q1) + (q2 + q3) for four, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)) for eight
+// (q0 + q1) + (q2 + q3) for four, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)) for eight; for sixteen the eight-part order on
+// q0 .. q7 and on q8 .. q15, then lower + upper
 template <int P, int L>
 __device__ __forceinline__ double bt_join(double own, double (*sh)[8][L], int v, int j) {
-    static_assert(P == 2 || P == 4 || P == 8, "a fixed order is written out for two, four and eight parts");
+    static_assert(P == 2 || P == 4 || P == 8 || P == 16, "a fixed order is written out for two, four, eight and sixteen parts");
     if constexpr (P == 2) return own + sh[0][v][j];
     else if constexpr (P == 4) return (own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j]);
-    else return ((own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j])) + ((sh[3][v][j] + sh[4][v][j]) + (sh[5][v][j] + sh[6][v][j]));
+    else if constexpr (P == 8)
+        return ((own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j])) + ((sh[3][v][j] + sh[4][v][j]) + (sh[5][v][j] + sh[6][v][j]));
+    else {
+        const double lower = ((own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j])) + ((sh[3][v][j] + sh[4][v][j]) + (sh[5][v][j] + sh[6][v][j]));
+        const double upper = ((sh[7][v][j] + sh[8][v][j]) + (sh[9][v][j] + sh[10][v][j])) + ((sh[11][v][j] + sh[12][v][j]) + (sh[13][v][j] + sh[14][v][j]));
+        return lower + upper;
+    }
 }
 
 // z [rows][W] fp32 -> part[g][c] = {count, mean, M2} (fp64).  LDS [part][value][lane]: consecutive lanes, consecutive doubles
@@ -215,7 +241,7 @@ template <int W>
 __global__ __launch_bounds__(BT_THREADS) void bt_stats_finish_kernel(const double* part, int G, const float* gam, const float* bet, float* rmean, float* rvar,
                                                                      float momentum, float eps, float* tab, float* stats_out) {
     const int c = blockIdx.x * BT_THREADS + threadIdx.x;
-    if (c >= W) return;      // W = 128: half of the one workgroup
+    if (c >= W) return;      // W = 128: half of the one workgroup, W = 64: a quarter
     double n = 0.0, mu = 0.0, m2 = 0.0;
     for (int g = 0; g < G; ++g) {
         const double* q = part + ((int64_t)g * W + c) * 3;
@@ -442,8 +468,9 @@ int64_t ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mo
     if (!make_geo(n, hin, win, cin, width, stride, base, g) || mode < 0 || mode > 1) return base - 1;
     const bool general = base != BT_LEGACY;
     // either mode of `training` runs in one allocation: the frozen path's layout starts at offset 0 too
-    const int64_t frozen = general ? vtd_resblock_ws_bytes(n, hin, win, cin, width, stride, mode)
-                                   : vtd_basicblock_ws_bytes(n, hin, win, cin, width, stride, mode);
+    const int64_t frozen = width == 64 ? vtd_block64_ws_bytes(n, hin, win, cin, width, stride, mode)
+                           : general   ? vtd_resblock_ws_bytes(n, hin, win, cin, width, stride, mode)
+                                       : vtd_basicblock_ws_bytes(n, hin, win, cin, width, stride, mode);
     const int64_t own = mode ? bwd_layout(g, general && g.ds).total : fwd_layout(g).total;
     if (frozen < 0) return base - 1;
     return frozen > own ? frozen : own;
@@ -499,9 +526,11 @@ int launch_forward(const void* x, int n, int hin, int win, int cin, int width, i
         return base - 1;
     if (training && (g.m < 2 || !(momentum >= 0.f && momentum <= 1.f))) return base - 1;
     if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)stats & 3)) return base - 2;
+    if (!training && width == 64) return vtd_launch_block64_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
     if (!training)
         return base == BT_LEGACY ? vtd_launch_basicblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s)
                                  : vtd_launch_resblock_forward(x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+    if (width == 64) return forward_launches<64>(x, g, P, momentum, eps, ws, y, stats, s);
     if (width == 128) return forward_launches<128>(x, g, P, momentum, eps, ws, y, stats, s);
     return width == 256 ? forward_launches<256>(x, g, P, momentum, eps, ws, y, stats, s) : forward_launches<512>(x, g, P, momentum, eps, ws, y, stats, s);
 }
@@ -541,10 +570,12 @@ int backward_launches(const void* x, const Geo& g, const vtd_basicblock_params* 
     auto wgrad = [&](const half_t* xin, int xc, int hi, int wi, int ksz, int st, const float* scl, float* dw) {
         WgArgs wa;
         wa.a = dzh; wa.lda = W; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = g.h; wa.W = g.w; wa.rows = M; wa.slab = slab;
-        // W = 128: one column tile, so the slabs of each launch by its own q-tiles (the rule of resblock_train.hip's 128-wide blocks)
-        const int nqt = W == 128 ? wg_nqt(ksz, xc) : ksz * ksz * xc / 128, Sl = W == 128 ? wg_slabs128(M, nqt) : S;
+        // W <= 128: one column tile, so the slabs of each launch by its own q-tiles (the rule of resblock_train.hip's 128- and 64-wide blocks)
+        const int nqt = W <= 128 ? wg_nqt(ksz, xc) : ksz * ksz * xc / 128, Sl = W <= 128 ? wg_slabs128(M, nqt) : S;
         wa.slab_len = slab_rows(M, Sl); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
-        if (xc & 127)   // layer2.0's 64-channel input: a tap per 64-column group
+        if (W == 64)   // layer1: the 64-row tile, one column tile, slab [64][576]
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<5>, dim3(nqt * Sl, 1), dim3(WG_THREADS), 0, s, wa);
+        else if (xc & 127)   // layer2.0's 64-channel input: a tap per 64-column group
             hipLaunchKernelGGL(dbhead_train_wgrad_kernel<4>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
         else
             hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, W / 128), dim3(WG_THREADS), 0, s, wa);
@@ -604,9 +635,11 @@ int launch_backward(const void* x, int n, int hin, int win, int cin, int width, 
     if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dy & 15) || ((uintptr_t)dscale & 7) ||
         ((uintptr_t)dx & 15) || ((uintptr_t)dxscale & 7))
         return base - 2;
+    if (!training && width == 64) return vtd_launch_block64_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
     if (!training)
         return legacy ? vtd_launch_basicblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s)
                       : vtd_launch_resblock_backward(x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+    if (width == 64) return backward_launches<64>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy);
     if (width == 128) return backward_launches<128>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy);
     return width == 256 ? backward_launches<256>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy)
                         : backward_launches<512>(x, g, P, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, !legacy);
@@ -645,7 +678,7 @@ int vtd_launch_block_bn_backward(const void* x, int n, int hin, int win, int cin
     return launch_backward(x, n, hin, win, cin, width, stride, P, training, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s, BT_GENERAL);
 }
 
-// the six geometries of layer2, layer3 and layer4, with the input gradient of the stride-2 blocks: the family that later stages join
+// the seven geometries of layer1, layer2, layer3 and layer4, with the input gradient of the stride-2 blocks: the family that the stem joins
 int64_t vtd_trunk_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
     return ws_bytes(n, hin, win, cin, width, stride, mode, BT_TRUNK);
 }

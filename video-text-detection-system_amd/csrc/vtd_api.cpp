@@ -1666,7 +1666,7 @@ int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
                                         grads, scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 
-// the six geometries of layer2, layer3 and layer4: the family that later stages join
+// the six geometries of layer2, layer3 and layer4 and layer1's (64 -> 64, stride 1): the family that later stages join
 int64_t vtd_trunk_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
     return vtd_trunk_bn_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
 }

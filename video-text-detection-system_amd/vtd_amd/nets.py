@@ -126,20 +126,21 @@ _TRUNK_BN_BUILT = ("train-mode (batch-statistics) trunk BatchNorm is built for (
                    "('layer3', 'layer4') with trainable='head+fpn+layer4+layer3', on resnet18; the tuple names exactly the residual stages that "
                    "train; layer2, layer1 and the stem keep frozen statistics under a tuple; with layer2 too the spellings are "
                    "forward_padded(..., trunk_batch_stats=('layer2', 'layer3', 'layer4')) and DBNet(trainable='head+fpn+layer4+layer3+layer2', "
-                   "trunk_bn='trained')")
-# the same on the vtd_trunk_bn_train_* entries, the family later stages join: layer2's two geometries too
-_TRUNK_BLOCK_BN_GEOMETRIES = ((64, 128, 2, True), (128, 128, 1, False)) + _BLOCK_BN_GEOMETRIES
-_TRUNK_BLOCK_BN_BUILT = ("trunk_block_bn_train (train-mode, batch-statistics BatchNorm) is built for the BasicBlocks of ResNet-18's layer2, layer3 and "
-                         "layer4 (64 -> 128, 128 -> 256 and 256 -> 512 stride 2 with downsample, 128 -> 128, 256 -> 256 and 512 -> 512 stride 1); "
-                         "layer1, the stem and Bottleneck blocks keep frozen statistics")
-# the stage tuples forward_padded's trunk_batch_stats takes; the last is the layer2 -> layer3 -> layer4 -> FPN -> head node, which DBNet spells
-# trunk_bn="trained"
-_NODE_BN_STAGES = (("layer4",), ("layer3", "layer4"), ("layer2", "layer3", "layer4"))
+                   "trunk_bn='trained'), with layer1 too forward_padded(..., trunk_batch_stats=('layer1', 'layer2', 'layer3', 'layer4')) and "
+                   "DBNet(trainable='head+fpn+layer4+layer3+layer2+layer1', trunk_bn='trained')")
+# the same on the vtd_trunk_bn_train_* entries, the family later stages join: layer2's two geometries and layer1's one too
+_TRUNK_BLOCK_BN_GEOMETRIES = ((64, 64, 1, False), (64, 128, 2, True), (128, 128, 1, False)) + _BLOCK_BN_GEOMETRIES
+_TRUNK_BLOCK_BN_BUILT = ("trunk_block_bn_train (train-mode, batch-statistics BatchNorm) is built for the BasicBlocks of ResNet-18's layer1, layer2, "
+                         "layer3 and layer4 (64 -> 64 stride 1, 64 -> 128, 128 -> 256 and 256 -> 512 stride 2 with downsample, 128 -> 128, "
+                         "256 -> 256 and 512 -> 512 stride 1); the stem and Bottleneck blocks keep frozen statistics")
+# the stage tuples forward_padded's trunk_batch_stats takes; the last two are the layer2 -> layer3 -> layer4 -> FPN -> head node and the
+# layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head node, which DBNet spells trunk_bn="trained"
+_NODE_BN_STAGES = (("layer4",), ("layer3", "layer4"), ("layer2", "layer3", "layer4"), ("layer1", "layer2", "layer3", "layer4"))
 # DBNet's trunk_bn="trained": every residual stage the mode trains runs its BatchNorms in train mode
-_TRAINED_BN_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2")
+_TRAINED_BN_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2", "head+fpn+layer4+layer3+layer2+layer1")
 _TRAINED_BN_BUILT = ("trunk_bn='trained' (train-mode, batch-statistics BatchNorm in every residual stage the mode trains) is built for "
-                     "trainable='head+fpn+layer4', 'head+fpn+layer4+layer3' and 'head+fpn+layer4+layer3+layer2' on resnet18; layer1 and the stem "
-                     "keep frozen statistics")
+                     "trainable='head+fpn+layer4', 'head+fpn+layer4+layer3', 'head+fpn+layer4+layer3+layer2' and "
+                     "'head+fpn+layer4+layer3+layer2+layer1' on resnet18; the stem keeps frozen statistics")
 
 
 def _block_bn_check(block, geometries=_BN_TRAIN_GEOMETRIES, built=_BN_TRAIN_BUILT):
@@ -205,8 +206,8 @@ def basic_block_bn_train(block, x):
 
 def trunk_block_bn_train(block, x):
     """``basic_block_bn_train`` on the vtd_trunk_bn_train_* entries, the family later stages join: layer2's two geometries too (64 -> 128 at
-    stride 2 with downsample and even extents, 128 -> 128 at stride 1), six in all.  The same module semantics: ``block.training`` selects
-    batch or frozen statistics, the block's BatchNorms need one fixed momentum, the running statistics are updated in place and
+    stride 2 with downsample and even extents, 128 -> 128 at stride 1) and layer1's 64 -> 64 at stride 1, seven in all.  The same module
+    semantics: ``block.training`` selects batch or frozen statistics, the block's BatchNorms need one fixed momentum, the running statistics are updated in place and
     ``num_batches_tracked`` advances in train mode, and the result is differentiable w.r.t. the block's learnable tensors and w.r.t. ``x``
     at either stride.  For the four geometries of layer3 and layer4 every output is the bits of ``basic_block_bn_train``; in ``eval()``
     mode it gives the bits of ``basic_block_train(block, x)`` and writes no buffer."""
@@ -217,11 +218,11 @@ def trunk_block_bn_train(block, x):
     bns = _block_bn_check(block, _TRUNK_BLOCK_BN_GEOMETRIES, _TRUNK_BLOCK_BN_BUILT)   # what is built, before anything about the device
     if not x.is_cuda:
         raise ValueError("BasicBlock runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
-    return _basic_block_bn_train(block, x, bns, general=True, entry=_TRUNK_BN)
+    return _basic_block_bn_train(block, x, bns, general=True, entry=_TRUNK_BN, narrow=True)
 
 
-def _basic_block_bn_train(block, x, bns, general=False, entry=None):
-    (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=general)
+def _basic_block_bn_train(block, x, bns, general=False, entry=None, narrow=False):
+    (cin, width, stride), eps, learn, stats = block._train_operands(x.device, general=general, narrow=narrow)
     n, _, hin, win = x.shape
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
         raise RuntimeError(f"BasicBlock(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
@@ -347,7 +348,12 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False):
-        """`trunk_batch_stats=("layer2", "layer3", "layer4")` goes with the tap [C2], `layer2`, `layer3`, `layer4` and `head` and nothing lower:
+        """`trunk_batch_stats=("layer1", "layer2", "layer3", "layer4")` goes with the tap [pool], `layer1` .. `layer4` and `head` and no `stem`:
+        the layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head node with all eight blocks on the vtd_trunk_bn_train_* entries, in one mode with
+        one momentum and one eps, else ValueError before the device is looked at.  layer2.0, layer3.0 and layer4.0 form their input gradients
+        (dC2 is layer2.0's plus the FPN's dC2, as in the frozen layer1 node); layer1.0 forms none.
+
+        `trunk_batch_stats=("layer2", "layer3", "layer4")` goes with the tap [C2], `layer2`, `layer3`, `layer4` and `head` and nothing lower:
         the layer2 -> layer3 -> layer4 -> FPN -> head node with all six blocks on the vtd_trunk_bn_train_* entries, in one mode (train() or
         eval()) with one momentum and one eps, else ValueError before the device is looked at.  layer3.0 and layer4.0 form their input
         gradients (dC3 and dC4 are those plus the FPN's); layer2.0 forms none.
@@ -407,6 +413,10 @@ class FeaturePyramidNetwork(nn.Module):
         if len(bn_stages) == 3 and (layer4 is None or layer3 is None or layer2 is None or layer1 is not None or stem is not None):
             raise ValueError("forward_padded(..., trunk_batch_stats=('layer2', 'layer3', 'layer4')) is the layer2 -> layer3 -> layer4 -> FPN -> head "
                              "node on the tap [C2]: it needs layer2, layer3, layer4 and the head and takes no lower stage; " + _TRUNK_BN_BUILT)
+        if len(bn_stages) == 4 and (any(m is None for m in layers) or stem is not None):
+            raise ValueError("forward_padded(..., trunk_batch_stats=('layer1', 'layer2', 'layer3', 'layer4')) is the layer1 -> layer2 -> layer3 -> "
+                             "layer4 -> FPN -> head node on the tap [pool]: it needs layer1, layer2, layer3, layer4 and the head and takes no stem, "
+                             "which keeps frozen statistics; " + _TRUNK_BN_BUILT)
         if stem is not None or any(m is not None for m in layers):
             return self._forward_padded_trunk(taps, head, layers, stem, bn_stages)
         if not isinstance(taps, (list, tuple)) or len(taps) != 4:
@@ -430,8 +440,8 @@ class FeaturePyramidNetwork(nn.Module):
     def _forward_padded_trunk(self, taps, head, layers, stem, bn_stages):
         """forward_padded with trunk stages: `layers` is (layer1, layer2, layer3, layer4), the node starts at the lowest one given (with `stem`:
         at the stem) and needs every stage above it and the head.  `bn_stages`: () or the stages (all of the node's) that run with batch
-        statistics, ("layer4",) on the vtd_resblock_bn_train_* entries, ("layer3", "layer4") on vtd_block_bn_train_* or ("layer2", "layer3",
-        "layer4") on vtd_trunk_bn_train_*."""
+        statistics, ("layer4",) on the vtd_resblock_bn_train_* entries, ("layer3", "layer4") on vtd_block_bn_train_*, ("layer2", "layer3",
+        "layer4") or ("layer1", "layer2", "layer3", "layer4") on vtd_trunk_bn_train_*."""
         low = 0 if stem is not None else next(i for i, m in enumerate(layers) if m is not None)
         above = _STAGES[0 if stem is not None else low + 1:]
         if head is None or any(m is None for m in layers[4 - len(above):]):
@@ -443,12 +453,13 @@ class FeaturePyramidNetwork(nn.Module):
             eps_all = {m.eps for layer in layers[2:] for m in layer.modules() if isinstance(m, nn.BatchNorm2d)}
             if len(eps_all) > 1:
                 raise ValueError("layer3's and layer4's four blocks must have one BatchNorm eps")
-        if len(bn_stages) == 3:      # the same over the six blocks, with the mode and the momentum: all before the device is looked at
-            bnm = [m for layer in layers[1:] for m in layer.modules() if isinstance(m, nn.BatchNorm2d)]
+        if len(bn_stages) >= 3:      # the same over the six or eight blocks, with the mode and the momentum: all before the device is looked at
+            bnm = [m for layer in layers[4 - len(bn_stages):] for m in layer.modules() if isinstance(m, nn.BatchNorm2d)]
+            whose = "layer2's, layer3's and layer4's six" if len(bn_stages) == 3 else "layer1's, layer2's, layer3's and layer4's eight"
             if len({m.eps for m in bnm}) > 1:
-                raise ValueError("layer2's, layer3's and layer4's six blocks must have one BatchNorm eps")
+                raise ValueError(whose + " blocks must have one BatchNorm eps")
             if len({m.training for m in bnm}) > 1 or any(m.momentum is None or m.momentum != bnm[0].momentum for m in bnm):
-                raise ValueError("layer2's, layer3's and layer4's six blocks must be in one mode (train() or eval()) with one fixed BatchNorm momentum")
+                raise ValueError(whose + " blocks must be in one mode (train() or eval()) with one fixed BatchNorm momentum")
         # the taps the node reads: the FPN levels below the lowest stage's output, the last of them that stage's input; layer1 reads the pooled
         # stem output and the stem the image, neither an FPN level
         names = ["image"] if stem is not None else [st.tap for st in _STAGES[1:low + 1]] or [_STAGES[0].tap]
@@ -479,10 +490,12 @@ class FeaturePyramidNetwork(nn.Module):
         bn, bbns = None, []
         if bn_stages:
             blocks = [blk for o in ops for blk in o[0]]      # the node's stages are exactly bn_stages (forward_padded)
-            check = ((), (_BLOCK_BN_GEOMETRIES, _BLOCK_BN_BUILT), (_TRUNK_BLOCK_BN_GEOMETRIES, _TRUNK_BLOCK_BN_BUILT))[len(bn_stages) - 1]
+            trunk_check = (_TRUNK_BLOCK_BN_GEOMETRIES, _TRUNK_BLOCK_BN_BUILT)
+            check = ((), (_BLOCK_BN_GEOMETRIES, _BLOCK_BN_BUILT), trunk_check, trunk_check)[len(bn_stages) - 1]
             bbns = [b for blk in blocks for b in _block_bn_check(blk, *check)]
             if any(blk.training != blocks[0].training for blk in blocks) or any(b.momentum != bbns[0].momentum for b in bbns):
-                raise ValueError(("layer4's two", "layer3's and layer4's four", "layer2's, layer3's and layer4's six")[len(bn_stages) - 1] +
+                raise ValueError(("layer4's two", "layer3's and layer4's four", "layer2's, layer3's and layer4's six",
+                                  "layer1's, layer2's, layer3's and layer4's eight")[len(bn_stages) - 1] +
                                  " blocks must be in one mode (train() or eval()) with one BatchNorm momentum")
             n, _, h5, w5 = outs[-1]
             if blocks[0].training and n * h5 * w5 < 2:
@@ -492,7 +505,7 @@ class FeaturePyramidNetwork(nn.Module):
         for _, geoms, _, learn, stats in ops:
             for g, lr, s in zip(geoms, learn, stats):
                 # a node of one stage runs on that stage's own entry family, as forward_<stage>_padded does; a deeper one on the block's by width
-                entry = (_RESBLOCK_BN, _BLOCK_BN, _TRUNK_BN)[len(bn_stages) - 1] if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
+                entry = (_RESBLOCK_BN, _BLOCK_BN, _TRUNK_BN, _TRUNK_BN)[len(bn_stages) - 1] if bn is not None else _STAGES[low].entry if len(ops) == 1 else _block_entry(g)
                 blocks.append((_BlockPlan(g, s, entry, len(lr)), lr))
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, tuple(b for b, _ in blocks), beps, bn)
         out = self._run_node(head, bns, plan, *slearn, *(t for _, lr in blocks for t in lr), *params, *hparams)
@@ -828,7 +841,7 @@ _RESBLOCK = "vtd_resblock_train"       # the entry family of the six geometries 
 _BLOCK64 = "vtd_block64_train"         # the entry family of layer1's 64 -> 64 block
 _RESBLOCK_BN = "vtd_resblock_bn_train"   # layer4's two geometries with batch-statistics BatchNorm (csrc/resblock_bn_train.hip)
 _BLOCK_BN = "vtd_block_bn_train"         # layer3's and layer4's four with batch-statistics BatchNorm, and the strided dx (the same file)
-_TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two as well, six in all: the family later stages join (the same file)
+_TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two and layer1's one as well, seven in all: the family the stem joins (the same file)
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
@@ -1296,12 +1309,15 @@ class DBNet(_EngineOwner, nn.Module):
 
     def set_trainable(self, trainable, trunk_bn=None):
         """`trunk_bn` ("frozen", the default, "batch", "trained", or a tuple of stage names; None keeps the current value) is the mode of the
-        trained trunk stages' BatchNorms.  "trained" (resnet18 with trainable="head+fpn+layer4", "head+fpn+layer4+layer3" or
-        "head+fpn+layer4+layer3+layer2"; anything else raises ValueError and leaves the network as it was): every residual stage the mode
-        trains runs its BatchNorms in train mode.  On the first two modes it behaves as the tuples ("layer4",) and ("layer3", "layer4") do.  On
-        the third the trunk engine gives C2 as with "frozen", then layer2, layer3 and layer4 run on the vtd_trunk_bn_train_* entries --
-        backbone.5 .. backbone.7's fifteen BatchNorms normalise with the statistics of the batch, and their 30 running buffers and 15 counters
-        move every step; a following eval() forward rebuilds the inference engine on the new statistics.
+        trained trunk stages' BatchNorms.  "trained" (resnet18 with trainable="head+fpn+layer4", "head+fpn+layer4+layer3",
+        "head+fpn+layer4+layer3+layer2" or "head+fpn+layer4+layer3+layer2+layer1"; anything else raises ValueError and leaves the network as it
+        was): every residual stage the mode trains runs its BatchNorms in train mode.  On the first two modes it behaves as the tuples
+        ("layer4",) and ("layer3", "layer4") do.  On the third the trunk engine gives C2 as with "frozen", then layer2, layer3 and layer4 run on
+        the vtd_trunk_bn_train_* entries -- backbone.5 .. backbone.7's fifteen BatchNorms normalise with the statistics of the batch, and their
+        30 running buffers and 15 counters move every step; a following eval() forward rebuilds the inference engine on the new statistics.
+        On the fourth the trunk engine gives the pooled stem output as with "frozen", then layer1 .. layer4 run on the same entries:
+        backbone.4 .. backbone.7's nineteen BatchNorms (layer1's blocks have no downsample), 38 running buffers and 19 counters.  The stem keeps frozen statistics: "head+fpn+backbone"
+        with "trained" is refused.
         A tuple names exactly the residual stages the mode trains, else ValueError: ("layer4",) goes with
         trainable="head+fpn+layer4" and is equivalent to "batch"; ("layer3", "layer4") goes with trainable="head+fpn+layer4+layer3" on resnet18:
         the trunk engine gives C2 and C3 as with "frozen", then layer3 and layer4 run on the vtd_block_bn_train_* entries -- backbone.6's and
@@ -1516,7 +1532,7 @@ class DBNet(_EngineOwner, nn.Module):
         # trunk_bn="batch" is the layer4 mode's alone and a tuple names the mode's own stages (set_trainable): the running statistics of those
         # stages move too; mark_dirty below covers them
         bn_mode = getattr(self, "trunk_bn", "frozen")
-        if bn_mode == "trained":      # every stage the mode trains (set_trainable: layer2 at the lowest); the three-stage tuple is the new node
+        if bn_mode == "trained":      # every stage the mode trains (set_trainable: layer1 at the lowest), on the node of that many stages
             bn_mode = tuple(stages)
         out = self.fpn.forward_padded(taps, head=self.head, trunk_batch_stats=bn_mode if isinstance(bn_mode, tuple) else bn_mode == "batch", **stages)
         self.mark_dirty()   # the kernels updated the head's running statistics in place
