@@ -431,7 +431,8 @@ int vtd_block_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
 /* ---- The same with layer2's width too (csrc/resblock_bn_train.hip, the same launch functions): vtd_trunk_bn_train_* take the arguments of
  * vtd_block_bn_train_*, one for one, and build six geometries: layer2's (cin 64, width 128, stride 2, even h_in and w_in, with downsample)
  * and (cin 128, width 128, stride 1), and the four of vtd_block_bn_train_* (and layer1's, below); every other geometry is refused with
- * -3701.  This is the family that later stages (layer1: below; the stem) join; the older families keep their gates and their bits.
+ * -3701.  This is the family that later stages join (layer1: below; the stem: vtd_stem_bn_train_*, further down, behind entries of its own);
+ * the older families keep their gates and their bits.
  * training = 0 hands the call to vtd_resblock_train_forward / _backward: their bits.  For the four geometries of vtd_block_bn_train_* every output -- y, the statistics, the
  * running update, every parameter gradient and the dx of either stride -- is the bits of vtd_block_bn_train_*.
  * The per-channel reductions of a 128-wide z (the statistics' partials and the backward's s1, s2): 32 threads x 4 channels cover the width,
@@ -500,6 +501,45 @@ int vtd_stem_train_forward(const void* x_tap_dev, int n, int height, int width, 
 int vtd_stem_train_backward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, float eps, const void* workspace_dev,
                             const void* pool_tap_dev, const void* idx_dev, const float* dpool_dev, const float* dscale_dev, const vtd_stem_params* grads,
                             void* scratch_dev, vtd_stream stream);
+
+/* ---- The stem with batch-statistics BatchNorm (csrc/stem_train.hip, torch's train() mode): the stem joins the batch-statistics family of
+ * vtd_trunk_bn_train_*, behind entries of its own because its tensors are the stem's (an image tap in, the pooled tap and the index bytes
+ * out).  The arguments are those of vtd_stem_train_*, plus `training`, `momentum` and stats_dev.  training = 0 hands the call to
+ * vtd_stem_train_forward / _backward: their bits, and nothing is written to the statistics.  The workspace query (mode 0 = the forward's
+ * workspace, kept for the backward; mode 1 = the backward's scratch) answers at least vtd_stem_train_workspace_bytes, so either value of
+ * `training` runs in one allocation.
+ * vtd_stem_bn_train_forward, training = 1: the raw 7x7 weights are rounded to fp16 per call into the frozen path's fragment layout (no fold:
+ * gamma rstd is not known yet, no bias); the convolution runs in the frozen forward's tiling (7 x 8 pooled pixels = 15 x 17 conv outputs
+ * per workgroup on v_mfma_f32_16x16x32_f16) and writes its fp32 accumulators to z [n hc wc][64] in the workspace.  Neighbouring tiles share
+ * one conv row and one conv column; a tile writes its local rows 1 .. 14 and columns 1 .. 16, so conv pixel (y, x) is written by tile
+ * (y / 14, x / 16) alone.  The statistics of z over its M = n hc wc rows take the 64-wide order documented above for layer1: min(256,
+ * ceil(M / 256)) workgroups of ceil(M / workgroups) consecutive rows, sixteen parts each joined by the balanced pairwise tree, (count,
+ * mean, M2) combined by Chan's rule in workgroup order, all in fp64; the same pass takes each channel's minimum and maximum of z, from which
+ * the backward has max |xh|.  params->mean and params->var are updated in place: mean <- (1 - momentum) mean + momentum mu, var <- (1 -
+ * momentum) var + momentum sigma^2 M / (M - 1); the caller advances num_batches_tracked.  stats_dev (optional, float32 [2][64]) receives mu
+ * and the biased sigma^2.  Then a = half(relu(((z - mu) rstd) gamma + beta)) is pooled 3x3/s2/p1 straight from z (a is not stored):
+ * pool_tap_dev and idx_dev as vtd_stem_train_forward writes them, by the same rule -- the first maximum in (ky, kx) scan order, only in-image
+ * positions, the byte unspecified where the pooled value is 0.
+ * vtd_stem_bn_train_backward, training = 1: dpool_dev / dscale_dev as in vtd_stem_train_backward; m = dpool (pool > 0).  Every live pooled
+ * element routes to exactly one conv position, so the sums over the conv map of g and g xh (g the gradient at the BatchNorm's output
+ * behind the ReLU, xh = (z - mu) rstd) are s1 = sum m and s2 = sum m xh[the position idx names], taken at pooled resolution with z
+ * gathered, in the row order of vtd_stem_train_backward's reduction (at most 256 workgroups of consecutive pooled pixels, four quarters as
+ * (q0 + q1) + (q2 + q3), partials in workgroup order, fp64).  An element whose pooled value is 0 adds nothing and its byte is not decoded.
+ * grads->beta = s1, grads->gamma = s2 (scale undone).  dZ [n hc wc][64] fp16 = gamma rstd (g - s1 / M - xh s2 / M) times a power of two,
+ * M = n hc wc (the conv rows, not the pooled ones); g is gathered from the 1, 2 or 4 windows that hold the conv pixel and whose idx names
+ * it, added in (py, px) order, nothing is scattered.  The power of two comes from the bound max_c |gamma rstd| (4 max |m| + |s1| / M + max
+ * |xh| |s2| / M) under the block kernels' target 16384.  The weight-gradient kernel of vtd_stem_train_backward runs unchanged on this dZ with
+ * the same slab rule; grads->w = G / scale: dZ carries gamma rstd, so no factor follows, and the result is exact for gamma = 0 and gamma <
+ * 0 -- nothing divides by gamma or sigma.  Gradients are written, not accumulated (grads->mean / var are ignored).  z makes one round trip
+ * through HBM per direction; the statistics are not fused into the convolution's epilogue.  No atomics, shape-only grids: bitwise repeatable.
+ * Errors, before any launch: -3801 (a null pointer, odd or too small extents, eps <= 0, training outside {0, 1}, momentum outside [0, 1],
+ * training = 1 with n hc wc < 2, a mode outside {0, 1} in the workspace query), -3802 (alignment). */
+int64_t vtd_stem_bn_train_workspace_bytes(int n, int height, int width, int mode);
+int vtd_stem_bn_train_forward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, int training, float momentum, float eps,
+                              void* workspace_dev, void* pool_tap_dev, void* idx_dev, float* stats_dev, vtd_stream stream);
+int vtd_stem_bn_train_backward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, int training, float eps,
+                               const void* workspace_dev, const void* pool_tap_dev, const void* idx_dev, const float* dpool_dev, const float* dscale_dev,
+                               const vtd_stem_params* grads, void* scratch_dev, vtd_stream stream);
 
 /* ---- recogniser: CRNN (app/ml/models/text_recognizer.py:12-37,114-167) --------------------------- */
 /* vocab_size = len(TextRecognizer.vocab) = 97 (text_recognizer.py:86-91); max_crops text regions per call. */

@@ -32,6 +32,19 @@
 //   param            slabs summed in slab order in fp64; dW = gamma rstd G (the eighth pixel and the fourth channel dropped: 147 of 224
 //                    columns), dbeta = s, dgamma = rstd (sum_k w G - mean s): no division by gamma
 // No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
+//
+// The same stage with batch-statistics BatchNorm (torch's train() mode) behind the vtd_stem_bn_train_* entries, in the second half of this
+// file; training = 0 hands the call to the launches above.  The statistics need the whole conv map before anything is normalised, so z
+// [n hc wc][64] fp32 makes one round trip through HBM per direction:
+//   pack             half(w) into fold's fragment layout: no gamma rstd, no bias
+//   conv             the forward kernel's tiling and K walk with ZOUT: the fp32 accumulators to z, each conv pixel by the one tile that owns it
+//   stats            (count, mean, M2) per channel in resblock_bn_train.hip's 64-wide order, with the channel's min and max of z; finish: Chan's
+//                    combination, the running update, the table {mu, rstd, gamma, beta, max |xh|}
+//   pool             a = half(relu(((z - mu) rstd) gamma + beta)) pooled straight from z by the frozen kernel's index rule; a is not stored
+//   reduce / finish  s1 = sum m and s2 = sum m xh[the position idx names] at pooled resolution in st_reduce_kernel's row order; dbeta, dgamma,
+//                    coef = {gamma rstd, s1 / M, s2 / M} with M the conv rows, the power-of-two multiplier
+//   form             dZ = gamma rstd (g - s1 / M - xh s2 / M), g gathered by st_form_kernel's membership rule, dense fp16
+//   wgrad / dw       stem_train_wgrad_kernel unchanged; dW = G / scale
 #include "vtd_common.h"
 #include "../../include/vtd.h"
 
@@ -154,11 +167,16 @@ struct StemFwdParams {
     const float* bias;   // [64]
     half_t* out;         // [n][pool_h + 2][pool_w + 2][64], ring 1
     uint8_t* idx;        // [n][pool_h][pool_w][64]
+    float* z;            // ZOUT: [n conv_h conv_w][64] fp32, the raw convolution (no bias, no activation, nothing pooled)
     int n, in_hp, in_wp, conv_h, conv_w, pool_h, pool_w, tiles_x, tiles_y;
 };
 
+// ZOUT (the batch-statistics forward): the same patch, fragments and K walk on raw fp16 weights from zero accumulators; the fp32 accumulators
+// go to p.z and nothing else is written.  Neighbouring tiles share one conv row and one conv column, so a tile writes its local rows 1 .. 14
+// and columns 1 .. 16 only: conv pixel (y, x) belongs to tile (y / 14, x / 16) and to no other.
+template <bool ZOUT>
 __global__ __launch_bounds__(ST_THREADS, 2) void stem_train_forward_kernel(const StemFwdParams p) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[ST_PATCH_BYTES + 256 * ST_CT_PITCH + 256];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[ZOUT ? ST_PATCH_BYTES : ST_PATCH_BYTES + 256 * ST_CT_PITCH + 256];
     unsigned char* const patch = smem;                                   // [37][40] pixels of 8 bytes
     unsigned char* const ctile = smem + ST_PATCH_BYTES;                  // [256][ST_CT_PITCH]
     float* const bias_lds = (float*)(ctile + 256 * ST_CT_PITCH);         // [64]
@@ -175,7 +193,9 @@ __global__ __launch_bounds__(ST_THREADS, 2) void stem_train_forward_kernel(const
     for (int ky = 0; ky < 7; ++ky)
 #pragma unroll
         for (int i = 0; i < 4; ++i) wreg[ky][i] = *(const half8*)(p.w + ((ky * 4 + i) * 64 + lane) * 8);
-    if (tid < 64) bias_lds[tid] = p.bias[tid];
+    if constexpr (!ZOUT) {
+        if (tid < 64) bias_lds[tid] = p.bias[tid];
+    }
     // The patch: input rows 4 py0 - 2 .., columns 4 px0 - 2 .., in units of two pixels (16 bytes; the tap's row pitch is even).  Coordinates
     // outside the padded image are clamped, not zero-filled: such pixels only feed conv outputs outside the conv map, which the epilogue
     // replaces by 0, or the zero weights of the eighth tap -- and what is read instead is a finite fp16 of the same tensor.
@@ -203,7 +223,10 @@ __global__ __launch_bounds__(ST_THREADS, 2) void stem_train_forward_kernel(const
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = *(const floatx4*)(bias_lds + st_chan(i, fq * 4));
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (ZOUT) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+            else acc[i][j] = *(const floatx4*)(bias_lds + st_chan(i, fq * 4));
+        }
 #pragma unroll
     for (int ky = 0; ky < 7; ++ky) {
         half8 af[4];
@@ -215,6 +238,23 @@ __global__ __launch_bounds__(ST_THREADS, 2) void stem_train_forward_kernel(const
             for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wreg[ky][i], af[j], acc[i][j], 0, 0, 0);
     }
 
+    if constexpr (ZOUT) {
+        // lane (fr, fq) holds channels 32 k + 8 fq .. + 7 of its pixel in the accumulators of the tile pair (2k, 2k + 1): 32 contiguous bytes
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int pix = wv * 64 + j * 16 + fr;
+            const int c_row = pix / ST_CT_COLS, c_col = pix - c_row * ST_CT_COLS;
+            const int cy = 2 * py0 - 1 + c_row, cx = 2 * px0 - 1 + c_col;
+            if (c_row < 1 || c_row > 2 * ST_PT_ROWS || c_col < 1 || c_col > 2 * ST_PT_COLS || cy >= p.conv_h || cx >= p.conv_w) continue;
+            float* dst = p.z + (((int64_t)img * p.conv_h + cy) * p.conv_w + cx) * 64 + 8 * fq;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                *(floatx4*)(dst + 32 * k) = acc[2 * k][j];
+                *(floatx4*)(dst + 32 * k + 4) = acc[2 * k + 1][j];
+            }
+        }
+        return;
+    }
     // ReLU after the fp16 convert (every negative half, -0 included, is a negative int16), zero outside the conv map -> LDS conv tile: lane
     // (fr, fq) holds channels 32 k + 8 fq .. + 7 of its pixel in the accumulators of the tile pair (2k, 2k + 1)
 #pragma unroll
@@ -492,6 +532,327 @@ __global__ __launch_bounds__(ST_THREADS) void st_param_kernel(const float* slab,
     }
 }
 
+// ---- batch-statistics BatchNorm (training = 1) --------------------------------------------------------------------------------------------
+// The conventions of resblock_bn_train.hip at width 64: raw weights rounded to fp16 per call, z kept in fp32, fixed fp64 summation orders.
+
+constexpr int SB_ARG = -3801, SB_ALIGN = -3802;
+constexpr float SB_SCALE_TARGET = 4.f * ST_SCALE_TARGET;   // the block kernels' 16384: the bound on |dz| counts the four windows itself
+constexpr int SB_PARTS = 16, SB_LANES = 16;                // sixteen parts of 16 lanes x 4 channels
+
+typedef double doublex4 __attribute__((ext_vector_type(4)));
+
+// the workspace of a training = 1 forward.  w sits where the frozen layout keeps its folded image.  tab: {mu, rstd, gamma, beta, max |xh|} [5][64]
+struct BnFwdLayout { int64_t w, tab, part, pmm, z, total; };
+struct BnBwdLayout { int64_t dz, part, pmax, coef, sc, slab, total; };
+
+BnFwdLayout bn_fwd_layout(const Geo& g) {
+    BnFwdLayout L;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
+    L.w = take(ST_WFRAG * 2); L.tab = take(5 * 64 * 4);
+    L.part = take((int64_t)ST_MAX_RED * 64 * 3 * 8); L.pmm = take((int64_t)ST_MAX_RED * 2 * 64 * 4);
+    L.z = take(g.mc * 64 * 4);
+    L.total = o;
+    return L;
+}
+
+BnBwdLayout bn_bwd_layout(const Geo& g) {
+    BnBwdLayout L;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
+    L.dz = take(g.mc * 64 * 2);
+    L.part = take((int64_t)ST_MAX_RED * 2 * 64 * 8); L.pmax = take((int64_t)ST_MAX_RED * 64 * 4);
+    L.coef = take(3 * 64 * 4); L.sc = take(4 * 4);
+    L.slab = take((int64_t)wg_slabs(g.mc) * SW_P * SW_Q * 4);
+    L.total = o;
+    return L;
+}
+
+// workgroups over the M rows of z: min(256, ceil(M / 256)) of ceil(M / workgroups) consecutive rows
+inline int bn_red(int64_t rows) { const int64_t r = (rows + 255) / 256; return (int)(r < 1 ? 1 : r > ST_MAX_RED ? ST_MAX_RED : r); }
+
+// NaN-keeping maximum, as the reduce kernels above take it
+__device__ __forceinline__ float st_nmax(float m, float a) { return a > m || a != a ? a : m; }
+
+// st_fold_kernel's fragment image of the raw weights: half(w), no gamma rstd, no bias
+__global__ __launch_bounds__(ST_THREADS) void sb_pack_kernel(const float* w, half_t* wfrag) {
+    const int i = blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= ST_WFRAG) return;
+    const int e = i & 7, lane = (i >> 3) & 63, tile = (i >> 9) & 3, ky = i >> 11;
+    const int fr = lane & 15, fq = lane >> 4, co = st_chan(tile, fr), kx = 2 * fq + (e >> 2), c = e & 3;
+    wfrag[i] = (half_t)((kx < 7 && c < 3) ? w[((co * 3 + c) * 7 + ky) * 7 + kx] : 0.f);
+}
+
+// the sixteen parts of one workgroup, part 0 in registers and the others in LDS [part - 1][value][lane]: the balanced pairwise tree, the
+// eight-part order on q0 .. q7 and on q8 .. q15, then lower + upper (resblock_bn_train.hip: bt_join at sixteen parts)
+__device__ __forceinline__ double sb_join(double own, double (*sh)[8][SB_LANES], int v, int j) {
+    const double lower = ((own + sh[0][v][j]) + (sh[1][v][j] + sh[2][v][j])) + ((sh[3][v][j] + sh[4][v][j]) + (sh[5][v][j] + sh[6][v][j]));
+    const double upper = ((sh[7][v][j] + sh[8][v][j]) + (sh[9][v][j] + sh[10][v][j])) + ((sh[11][v][j] + sh[12][v][j]) + (sh[13][v][j] + sh[14][v][j]));
+    return lower + upper;
+}
+
+// z [rows][64] fp32 -> part[g][c] = {count, mean, M2} (fp64) in the 64-wide order of resblock_bn_train.hip (bt_stats_partial_kernel<64>):
+// thread (part k = t / 16, lane j = t % 16) sums channels 4 j .. 4 j + 3 over rows ceil(k r / 16) .. ceil((k + 1) r / 16) - 1 of the
+// workgroup's r rows.  The same pass takes the channel's minimum and maximum of z, pmm[g] = {min[64], max[64]}: the backward reads z at
+// pooled resolution only and has max |xh| from these
+__global__ __launch_bounds__(ST_THREADS) void sb_stats_partial_kernel(const float* z, int64_t rows, int64_t per, double* part, float* pmm) {
+    const int t = threadIdx.x, j = t % SB_LANES, grp = t / SB_LANES;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t r = m1 - m0, lo = m0 + (grp * r + SB_PARTS - 1) / SB_PARTS, hi = m0 + ((grp + 1) * r + SB_PARTS - 1) / SB_PARTS;
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    floatx4 mn = {INFINITY, INFINITY, INFINITY, INFINITY}, mx = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll 4
+    for (int64_t m = lo; m < hi; ++m) {
+        const floatx4 v = *(const floatx4*)(z + m * 64 + 4 * j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double a = (double)v[e];
+            s[e] += a; q[e] += a * a;
+            mn[e] = fminf(mn[e], v[e]); mx[e] = fmaxf(mx[e], v[e]);
+        }
+    }
+    __shared__ double sh[SB_PARTS - 1][8][SB_LANES];
+    __shared__ float shm[SB_PARTS - 1][8][SB_LANES];
+    if (grp) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            sh[grp - 1][e][j] = s[e]; sh[grp - 1][4 + e][j] = q[e];
+            shm[grp - 1][e][j] = mn[e]; shm[grp - 1][4 + e][j] = mx[e];
+        }
+    }
+    __syncthreads();
+    if (!grp) {
+        const double cnt = (double)r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double S = sb_join(s[e], sh, e, j), Q = sb_join(q[e], sh, 4 + e, j);
+            const double mean = cnt > 0 ? S / cnt : 0.0;
+            double* o = part + ((int64_t)blockIdx.x * 64 + 4 * j + e) * 3;
+            o[0] = cnt; o[1] = mean; o[2] = cnt > 0 ? fmax(Q - S * mean, 0.0) : 0.0;
+#pragma unroll
+            for (int k = 0; k < SB_PARTS - 1; ++k) { mn[e] = fminf(mn[e], shm[k][e][j]); mx[e] = fmaxf(mx[e], shm[k][4 + e][j]); }
+        }
+        *(floatx4*)(pmm + (int64_t)blockIdx.x * 128 + 4 * j) = mn;
+        *(floatx4*)(pmm + (int64_t)blockIdx.x * 128 + 64 + 4 * j) = mx;
+    }
+}
+
+// One workgroup per channel: Chan's combination of the partials in workgroup order (fp64), torch's running-statistics update with the
+// unbiased variance, the table {mu, rstd, gamma, beta, max |xh|} [5][64] (xh = (z - mu) rstd in fp32, as the other kernels form it: its
+// extremes sit at the extremes of z) and (optionally) stats_out = {mu, sigma^2} [2][64].  The combination is a serial chain; thread g brings
+// partial g (G <= 256) into LDS first so that the chain, on thread 0, does not wait for HBM at every step
+__global__ __launch_bounds__(ST_THREADS) void sb_stats_finish_kernel(const double* part, const float* pmm, int G, const float* gam, const float* bet,
+                                                                     float* rmean, float* rvar, float momentum, float eps, float* tab, float* stats_out) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    __shared__ double sp[ST_MAX_RED][3];
+    __shared__ float sm[ST_MAX_RED][2];
+    if (t < G) {
+        const double* q = part + ((int64_t)t * 64 + c) * 3;
+        sp[t][0] = q[0]; sp[t][1] = q[1]; sp[t][2] = q[2];
+        sm[t][0] = pmm[(int64_t)t * 128 + c]; sm[t][1] = pmm[(int64_t)t * 128 + 64 + c];
+    }
+    __syncthreads();
+    if (t) return;
+    double n = 0.0, mu = 0.0, m2 = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int g = 0; g < G; ++g) {
+        const double nb = sp[g][0];
+        if (nb <= 0.0) continue;
+        const double tot = n + nb, d = sp[g][1] - mu;
+        mu += d * (nb / tot);
+        m2 += sp[g][2] + d * d * (n * nb / tot);
+        n = tot;
+        mn = fminf(mn, sm[g][0]); mx = fmaxf(mx, sm[g][1]);
+    }
+    const double var = m2 / n, unbiased = m2 / (n - 1.0);   // n >= 2: the entry refuses fewer rows
+    rmean[c] = (float)((1.0 - (double)momentum) * (double)rmean[c] + (double)momentum * mu);
+    rvar[c] = (float)((1.0 - (double)momentum) * (double)rvar[c] + (double)momentum * unbiased);
+    const float muf = (float)mu, rs = (float)(1.0 / sqrt(var + (double)eps));
+    tab[c] = muf;
+    tab[64 + c] = rs;
+    tab[128 + c] = gam[c];
+    tab[192 + c] = bet[c];
+    tab[256 + c] = fmaxf(fabsf((mn - muf) * rs), fabsf((mx - muf) * rs));
+    if (stats_out) {
+        stats_out[c] = muf;
+        stats_out[64 + c] = (float)var;
+    }
+}
+
+// a = half(relu(((z - mu) rstd) gamma + beta)) (bt_apply_kernel's expression), pooled 3x3/s2/p1 by the frozen kernel's rule: positions outside
+// the conv map hold 0, the scan (ky, then kx) keeps a later position only when it is strictly greater.  One thread = 8 channels of one
+// pooled pixel; a is not stored.
+__global__ __launch_bounds__(ST_THREADS) void sb_pool_kernel(const float* z, const float* tab, int64_t prow, int hc, int wc, int hp, int wp, half_t* pool,
+                                                             uint8_t* idx) {
+    const int64_t i = (int64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= prow * 8) return;
+    const int c0 = (int)(i & 7) * 8;
+    const int64_t m = i >> 3;
+    const int HW = hp * wp, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), py = rem / wp, px = rem - py * wp;
+    float mu[8], rs[8], gm[8], bt[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = tab[c0 + e]; rs[e] = tab[64 + c0 + e]; gm[e] = tab[128 + c0 + e]; bt[e] = tab[192 + c0 + e]; }
+    half8 best;
+    uint32_t id[8];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        const int y = 2 * py - 1 + q / 3, x = 2 * px - 1 + q % 3;
+        half8 a = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (y >= 0 && y < hc && x >= 0 && x < wc) {
+            const float* src = z + (((int64_t)img * hc + y) * wc + x) * 64 + c0;
+            const floatx4 v0 = *(const floatx4*)src, v1 = *(const floatx4*)(src + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float v = e < 4 ? v0[e] : v1[e - 4];
+                const float f = ((v - mu[e]) * rs[e]) * gm[e] + bt[e];
+                a[e] = (half_t)(f > 0.f ? f : 0.f);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (q == 0) { best[e] = a[e]; id[e] = 0; }
+            else if ((float)a[e] > (float)best[e]) { best[e] = a[e]; id[e] = q; }
+        }
+    }
+    *(half8*)(pool + (((int64_t)img * (hp + 2) + py + 1) * (wp + 2) + px + 1) * 64 + c0) = best;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { lo |= id[e] << (8 * e); hi |= id[4 + e] << (8 * e); }
+    *(uint2*)(idx + m * 64 + c0) = make_uint2(lo, hi);
+}
+
+// m = dpool (pool > 0) at pooled resolution in st_reduce_kernel's row order: part[g][0][c] = sum m, part[g][1][c] = sum m xh at the conv
+// position the element's idx byte names, xh = (z - mu) rstd gathered from z; pmax[g][c] = max |m|.  A live element's byte is an in-image
+// position by the forward's rule; where the pooled value is 0 the byte is unspecified: it adds nothing and is not decoded.  The decoded
+// position is checked against the conv map all the same, so no byte can make an address outside z
+__global__ __launch_bounds__(ST_THREADS) void sb_reduce_kernel(const float* dpool, const half_t* pool, const uint8_t* idx, const float* z, const float* tab,
+                                                               int64_t rows, int64_t per, int hc, int wc, int hp, int wp, double* part, float* pmax) {
+    const int t = threadIdx.x, c = t & 63, k = t >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t r = m1 - m0, lo = m0 + (k * r + 3) / 4, hi = m0 + ((k + 1) * r + 3) / 4;
+    const int HW = hp * wp;
+    const float mu = tab[c], rs = tab[64 + c];
+    double s1 = 0.0, s2 = 0.0;
+    float mx = 0.f;
+    if (lo < hi) {
+        int img = (int)(lo / HW), rem = (int)(lo - (int64_t)img * HW), y = rem / wp, x = rem - y * wp;
+        for (int64_t m = lo; m < hi; ++m) {
+            const bool live = (float)pool[(((int64_t)img * (hp + 2) + y + 1) * (wp + 2) + x + 1) * 64 + c] > 0.f;
+            if (live) {
+                const float a = dpool[m * 64 + c];
+                const int code = idx[m * 64 + c], cy = 2 * y - 1 + code / 3, cx = 2 * x - 1 + code % 3;
+                s1 += (double)a;
+                mx = st_nmax(mx, fabsf(a));
+                if (code < 9 && cy >= 0 && cy < hc && cx >= 0 && cx < wc) {
+                    const float xh = (z[(((int64_t)img * hc + cy) * wc + cx) * 64 + c] - mu) * rs;
+                    s2 += (double)a * (double)xh;
+                }
+            }
+            if (++x == wp) { x = 0; if (++y == hp) { y = 0; ++img; } }
+        }
+    }
+    __shared__ double sh1[ST_THREADS], sh2[ST_THREADS];
+    __shared__ float shm[ST_THREADS];
+    sh1[t] = s1; sh2[t] = s2; shm[t] = mx;
+    __syncthreads();
+    if (k == 0) {
+        part[(int64_t)blockIdx.x * 128 + c] = (sh1[c] + sh1[64 + c]) + (sh1[128 + c] + sh1[192 + c]);
+        part[(int64_t)blockIdx.x * 128 + 64 + c] = (sh2[c] + sh2[64 + c]) + (sh2[128 + c] + sh2[192 + c]);
+        pmax[(int64_t)blockIdx.x * 64 + c] = st_nmax(st_nmax(shm[c], shm[64 + c]), st_nmax(shm[128 + c], shm[192 + c]));
+    }
+}
+
+// One workgroup of 64 threads, thread c = channel c.  The partials in workgroup order (fp64).  dbeta = s1, dgamma = s2 with the incoming
+// scale undone; coef = {gamma rstd, s1 / M, s2 / M} [3][64] at the incoming scale, M the conv rows; out_sc = {total scale, 1 / total, this
+// stage's multiplier, 0}: a power of two from the bound max_c |gamma rstd| (4 max |m| + |s1| / M + max |xh| |s2| / M) >= max |dz| -- up to
+// four windows add into one conv position -- (1 when that is zero or not finite)
+__global__ __launch_bounds__(64) void sb_finish_kernel(const double* part, const float* pmax, int G, double inv_m, const float* tab, const float* in_sc,
+                                                       float* coef, float* dgam, float* dbet, float* out_sc) {
+    const int c = threadIdx.x;
+    double s1 = 0.0, s2 = 0.0;
+    float mg = 0.f;
+#pragma unroll 8
+    for (int g = 0; g < G; ++g) {
+        s1 += part[(int64_t)g * 128 + c]; s2 += part[(int64_t)g * 128 + 64 + c];
+        mg = st_nmax(mg, pmax[(int64_t)g * 64 + c]);
+    }
+    const float A = tab[128 + c] * tab[64 + c], B = (float)(s1 * inv_m), C = (float)(s2 * inv_m), mx = tab[256 + c];
+    coef[c] = A; coef[64 + c] = B; coef[128 + c] = C;
+    dbet[c] = (float)(s1 * (double)in_sc[1]);
+    dgam[c] = (float)(s2 * (double)in_sc[1]);
+    __shared__ float sh[64];
+    sh[c] = (float)(fabs((double)A) * (4.0 * (double)mg + fabs((double)B) + (double)mx * fabs((double)C)));
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) {
+        if (c < o) sh[c] = st_nmax(sh[c], sh[c + o]);
+        __syncthreads();
+    }
+    if (c == 0) {
+        const float bound = sh[0];
+        const double tin = (double)in_sc[0];
+        int e = 0;
+        if (bound > 0.f && isfinite(bound)) e = (int)floor(log2((double)SB_SCALE_TARGET / (double)bound));
+        const int ein = (tin > 0.0 && isfinite(tin)) ? ilogb(tin) : 0;
+        int et = ein + e;
+        et = et < -120 ? -120 : et > 120 ? 120 : et;
+        e = et - ein;
+        const double tot = tin * ldexp(1.0, e);
+        out_sc[0] = (float)tot; out_sc[1] = (float)(1.0 / tot); out_sc[2] = ldexpf(1.0f, e); out_sc[3] = 0.f;
+    }
+}
+
+// dZ[row][c] = gamma rstd (g - s1 / M - xh s2 / M) in fp32, times the multiplier, as fp16, for conv pixel row = (img, y, x): g is m gathered
+// by st_form_kernel's membership rule, the 1, 2 or 4 windows that hold the pixel and whose idx names it, added in (py, px) order; xh from
+// the saved z.  Nothing is scattered.  One thread = 8 channels of one conv pixel.
+__global__ __launch_bounds__(ST_THREADS) void sb_form_kernel(const float* dpool, const half_t* pool, const uint8_t* idx, const float* z, const float* tab,
+                                                             const float* coef, const float* sc, int64_t rows, int hc, int wc, int hp, int wp, half_t* dz) {
+    const int64_t i = (int64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= rows * 8) return;
+    const int c0 = (int)(i & 7) * 8;
+    const int64_t m = i >> 3;
+    const int HW = hc * wc, img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / wc, x = rem - y * wc;
+    const float mul = sc[2];
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int py0 = y >> 1, py1 = (y + 1) >> 1, px0 = x >> 1, px1 = (x + 1) >> 1;
+    for (int py = py0; py <= py1 && py < hp; ++py)
+        for (int px = px0; px <= px1 && px < wp; ++px) {
+            const int code = 3 * (y - 2 * py + 1) + (x - 2 * px + 1);
+            const int64_t pp = ((int64_t)img * hp + py) * wp + px;
+            const uint2 ib = *(const uint2*)(idx + pp * 64 + c0);
+            const half8 pv = *(const half8*)(pool + (((int64_t)img * (hp + 2) + py + 1) * (wp + 2) + px + 1) * 64 + c0);
+            const floatx4 d0 = *(const floatx4*)(dpool + pp * 64 + c0), d1 = *(const floatx4*)(dpool + pp * 64 + c0 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if ((int)((ib.x >> (8 * e)) & 0xff) == code && (float)pv[e] > 0.f) acc[e] += d0[e];
+                if ((int)((ib.y >> (8 * e)) & 0xff) == code && (float)pv[4 + e] > 0.f) acc[4 + e] += d1[e];
+            }
+        }
+    half8 h;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const floatx4 zv = *(const floatx4*)(z + i * 8 + 4 * k);
+        const floatx4 mu = *(const floatx4*)(tab + c0 + 4 * k), rs = *(const floatx4*)(tab + 64 + c0 + 4 * k);
+        const floatx4 A = *(const floatx4*)(coef + c0 + 4 * k), B = *(const floatx4*)(coef + 64 + c0 + 4 * k), C = *(const floatx4*)(coef + 128 + c0 + 4 * k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xh = (zv[e] - mu[e]) * rs[e];
+            h[4 * k + e] = (half_t)(A[e] * (acc[4 * k + e] - B[e] - xh * C[e]) * mul);
+        }
+    }
+    *(half8*)(dz + i * 8) = h;
+}
+
+// One workgroup per output channel c, thread k < 147 = (ci, ky, kx) in the weight's own order: dW = the slabs summed in slab order (fp64)
+// with the scale undone, read at column 32 ky + 4 kx + ci.  dz carries gamma rstd: no factor follows
+__global__ __launch_bounds__(ST_THREADS) void sb_dw_kernel(const float* slab, int S, const float* sc, float* dw) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    if (t >= 147) return;
+    const int ci = t / 49, ky = (t % 49) / 7, kx = t % 7, q = 32 * ky + 4 * kx + ci;
+    double G = 0.0;
+    for (int s = 0; s < S; ++s) G += (double)slab[((int64_t)s * SW_P + c) * SW_Q + q];
+    dw[c * 147 + t] = (float)(G * (double)sc[1]);
+}
+
 bool params_ok(const vtd_stem_params* p) {
     return p && p->w && p->gamma && p->beta && p->mean && p->var &&
            !(((uintptr_t)p->w | (uintptr_t)p->gamma | (uintptr_t)p->beta | (uintptr_t)p->mean | (uintptr_t)p->var) & 3);
@@ -528,13 +889,13 @@ int vtd_launch_stem_forward(const void* x, int n, int H, int W, const vtd_stem_p
                        (const float*)P->mean, (const float*)P->var, eps, wfrag, bias);
     hipLaunchKernelGGL(st_zero_ring_kernel, dim3(nblk((int64_t)n * (2 * (g.wp + 2) + 2 * g.hp) * 8)), dim3(ST_THREADS), 0, s, (half_t*)pool, n, g.hp, g.wp);
     StemFwdParams p;
-    p.in = (const half_t*)x; p.w = wfrag; p.bias = bias; p.out = (half_t*)pool; p.idx = (uint8_t*)idx;
+    p.in = (const half_t*)x; p.w = wfrag; p.bias = bias; p.out = (half_t*)pool; p.idx = (uint8_t*)idx; p.z = nullptr;
     p.n = n; p.in_hp = H + 6; p.in_wp = W + 6; p.conv_h = g.hc; p.conv_w = g.wc; p.pool_h = g.hp; p.pool_w = g.wp;
     p.tiles_x = (g.wp + ST_PT_COLS - 1) / ST_PT_COLS;
     p.tiles_y = (g.hp + ST_PT_ROWS - 1) / ST_PT_ROWS;
     const int64_t tiles = (int64_t)n * p.tiles_x * p.tiles_y;
     if (tiles >= (1ll << 31)) return ST_ARG;
-    hipLaunchKernelGGL(stem_train_forward_kernel, dim3((unsigned)tiles), dim3(ST_THREADS), 0, s, p);
+    hipLaunchKernelGGL(stem_train_forward_kernel<false>, dim3((unsigned)tiles), dim3(ST_THREADS), 0, s, p);
     return -(int)hipGetLastError();
 }
 
@@ -567,5 +928,84 @@ int vtd_launch_stem_backward(const void* x, int n, int H, int W, const vtd_stem_
     hipLaunchKernelGGL(stem_train_wgrad_kernel, dim3(S), dim3(ST_THREADS), 0, s, wa);
     hipLaunchKernelGGL(st_param_kernel, dim3(64), dim3(ST_THREADS), 0, s, (const float*)slab, S, (const float*)sc, (const double*)sum, (const float*)P->w,
                        (const float*)P->gamma, (const float*)P->mean, (const float*)P->var, eps, Gp->w, Gp->gamma, Gp->beta);
+    return -(int)hipGetLastError();
+}
+
+// ---- the batch-statistics entries: training = 0 is the frozen path above, its bits ----------------------------------------------------------
+int64_t vtd_stem_bn_ws_bytes(int n, int H, int W, int mode) {
+    Geo g;
+    if (!make_geo(n, H, W, g) || mode < 0 || mode > 1) return SB_ARG;
+    // either value of `training` runs in one allocation: the frozen layout starts at offset 0 too
+    const int64_t frozen = mode ? bwd_layout(g).total : fwd_layout().total, own = mode ? bn_bwd_layout(g).total : bn_fwd_layout(g).total;
+    return frozen > own ? frozen : own;
+}
+
+int vtd_launch_stem_bn_forward(const void* x, int n, int H, int W, const vtd_stem_params* P, int training, float momentum, float eps, void* ws, void* pool,
+                               void* idx, float* stats, hipStream_t s) {
+    Geo g;
+    if (!x || !ws || !pool || !idx || !make_geo(n, H, W, g) || !params_ok(P) || !(eps > 0.f) || (training != 0 && training != 1)) return SB_ARG;
+    if (training && (g.mc < 2 || !(momentum >= 0.f && momentum <= 1.f))) return SB_ARG;
+    if (((uintptr_t)x & 15) || ((uintptr_t)pool & 15) || ((uintptr_t)idx & 7) || ((uintptr_t)ws & 255) || ((uintptr_t)stats & 3)) return SB_ALIGN;
+    if (!training) return vtd_launch_stem_forward(x, n, H, W, P, eps, ws, pool, idx, s);
+    const BnFwdLayout L = bn_fwd_layout(g);
+    char* w = (char*)ws;
+    half_t* wfrag = (half_t*)(w + L.w);
+    float *tab = (float*)(w + L.tab), *pmm = (float*)(w + L.pmm), *z = (float*)(w + L.z);
+    double* part = (double*)(w + L.part);
+    hipLaunchKernelGGL(sb_pack_kernel, dim3(nblk(ST_WFRAG)), dim3(ST_THREADS), 0, s, (const float*)P->w, wfrag);
+    hipLaunchKernelGGL(st_zero_ring_kernel, dim3(nblk((int64_t)n * (2 * (g.wp + 2) + 2 * g.hp) * 8)), dim3(ST_THREADS), 0, s, (half_t*)pool, n, g.hp, g.wp);
+    StemFwdParams p;
+    p.in = (const half_t*)x; p.w = wfrag; p.bias = nullptr; p.out = nullptr; p.idx = nullptr; p.z = z;
+    p.n = n; p.in_hp = H + 6; p.in_wp = W + 6; p.conv_h = g.hc; p.conv_w = g.wc; p.pool_h = g.hp; p.pool_w = g.wp;
+    p.tiles_x = (g.wp + ST_PT_COLS - 1) / ST_PT_COLS;
+    p.tiles_y = (g.hp + ST_PT_ROWS - 1) / ST_PT_ROWS;
+    const int64_t tiles = (int64_t)n * p.tiles_x * p.tiles_y;
+    if (tiles >= (1ll << 31)) return SB_ARG;
+    hipLaunchKernelGGL(stem_train_forward_kernel<true>, dim3((unsigned)tiles), dim3(ST_THREADS), 0, s, p);
+    VTD_HIP_CHECK(hipGetLastError());
+    const int Gr = bn_red(g.mc);
+    const int64_t per = (g.mc + Gr - 1) / Gr;
+    hipLaunchKernelGGL(sb_stats_partial_kernel, dim3(Gr), dim3(ST_THREADS), 0, s, (const float*)z, g.mc, per, part, pmm);
+    hipLaunchKernelGGL(sb_stats_finish_kernel, dim3(64), dim3(ST_THREADS), 0, s, (const double*)part, (const float*)pmm, Gr, (const float*)P->gamma, (const float*)P->beta,
+                       P->mean, P->var, momentum, eps, tab, stats);
+    hipLaunchKernelGGL(sb_pool_kernel, dim3(nblk(g.mp * 8)), dim3(ST_THREADS), 0, s, (const float*)z, (const float*)tab, g.mp, g.hc, g.wc, g.hp, g.wp,
+                       (half_t*)pool, (uint8_t*)idx);
+    return -(int)hipGetLastError();
+}
+
+int vtd_launch_stem_bn_backward(const void* x, int n, int H, int W, const vtd_stem_params* P, int training, float eps, const void* ws, const void* pool,
+                                const void* idx, const float* dpool, const float* dscale, const vtd_stem_params* Gp, void* scratch, hipStream_t s) {
+    Geo g;
+    if (!x || !ws || !pool || !idx || !dpool || !dscale || !scratch || !make_geo(n, H, W, g) || !params_ok(P) || !Gp || !Gp->w || !Gp->gamma || !Gp->beta ||
+        !(eps > 0.f) || (training != 0 && training != 1) || (training && g.mc < 2))
+        return SB_ARG;
+    if (((uintptr_t)x & 15) || ((uintptr_t)pool & 15) || ((uintptr_t)idx & 7) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dpool & 15) ||
+        ((uintptr_t)dscale & 7) || (((uintptr_t)Gp->w | (uintptr_t)Gp->gamma | (uintptr_t)Gp->beta) & 3))
+        return SB_ALIGN;
+    if (!training) return vtd_launch_stem_backward(x, n, H, W, P, eps, ws, pool, idx, dpool, dscale, Gp, scratch, s);
+    const BnFwdLayout L = bn_fwd_layout(g);
+    const BnBwdLayout B = bn_bwd_layout(g);
+    const char* w = (const char*)ws;
+    char* q = (char*)scratch;
+    const float *z = (const float*)(w + L.z), *tab = (const float*)(w + L.tab);
+    half_t* dz = (half_t*)(q + B.dz);
+    double* part = (double*)(q + B.part);
+    float *pmax = (float*)(q + B.pmax), *coef = (float*)(q + B.coef), *sc = (float*)(q + B.sc), *slab = (float*)(q + B.slab);
+    int Gr = (int)((g.mp + 255) / 256);      // st_reduce_kernel's rows: the pooled pixels
+    Gr = Gr < 1 ? 1 : Gr > ST_MAX_RED ? ST_MAX_RED : Gr;
+    const int64_t per = (g.mp + Gr - 1) / Gr;
+    hipLaunchKernelGGL(sb_reduce_kernel, dim3(Gr), dim3(ST_THREADS), 0, s, dpool, (const half_t*)pool, (const uint8_t*)idx, z, tab, g.mp, per, g.hc, g.wc, g.hp,
+                       g.wp, part, pmax);
+    hipLaunchKernelGGL(sb_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)part, (const float*)pmax, Gr, 1.0 / (double)g.mc, tab, dscale, coef, Gp->gamma,
+                       Gp->beta, sc);
+    hipLaunchKernelGGL(sb_form_kernel, dim3(nblk(g.mc * 8)), dim3(ST_THREADS), 0, s, dpool, (const half_t*)pool, (const uint8_t*)idx, z, tab, (const float*)coef,
+                       (const float*)sc, g.mc, g.hc, g.wc, g.hp, g.wp, dz);
+    VTD_HIP_CHECK(hipGetLastError());
+    const int S = wg_slabs(g.mc);
+    StemWgArgs wa;
+    wa.dz = dz; wa.x = (const half_t*)x; wa.hc = g.hc; wa.wc = g.wc; wa.in_hp = H + 6; wa.in_wp = W + 6; wa.rows = g.mc; wa.slab_len = slab_rows(g.mc, S);
+    wa.slab = slab;
+    hipLaunchKernelGGL(stem_train_wgrad_kernel, dim3(S), dim3(ST_THREADS), 0, s, wa);
+    hipLaunchKernelGGL(sb_dw_kernel, dim3(64), dim3(ST_THREADS), 0, s, (const float*)slab, S, (const float*)sc, Gp->w);
     return -(int)hipGetLastError();
 }

@@ -111,6 +111,11 @@ int64_t vtd_stem_ws_bytes(int n, int H, int W, int mode);
 int vtd_launch_stem_forward(const void* x, int n, int H, int W, const vtd_stem_params* P, float eps, void* ws, void* pool, void* idx, hipStream_t s);
 int vtd_launch_stem_backward(const void* x, int n, int H, int W, const vtd_stem_params* P, float eps, const void* ws, const void* pool, const void* idx,
                              const float* dpool, const float* dscale, const vtd_stem_params* Gp, void* scratch, hipStream_t s);
+int64_t vtd_stem_bn_ws_bytes(int n, int H, int W, int mode);
+int vtd_launch_stem_bn_forward(const void* x, int n, int H, int W, const vtd_stem_params* P, int training, float momentum, float eps, void* ws, void* pool,
+                               void* idx, float* stats, hipStream_t s);
+int vtd_launch_stem_bn_backward(const void* x, int n, int H, int W, const vtd_stem_params* P, int training, float eps, const void* ws, const void* pool,
+                                const void* idx, const float* dpool, const float* dscale, const vtd_stem_params* Gp, void* scratch, hipStream_t s);
 int vtd_launch_resblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps, void* ws,
                                 void* y, hipStream_t s);
 int vtd_launch_resblock_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
@@ -1484,6 +1489,9 @@ const char* vtd_strerror(int code) {
         case -3702: return "trunk block batch-statistics training: misaligned buffer";
         case -3301: return "stem training: invalid argument or unsupported geometry (built: n >= 1, even image height and width >= 2)";
         case -3302: return "stem training: misaligned buffer";
+        case -3801: return "stem batch-statistics training: invalid argument or unsupported geometry (built: n >= 1, even image height and width >= 2; "
+                           "eps > 0, training 0 or 1, momentum in [0, 1]; training = 1 needs n hc wc >= 2 conv pixels)";
+        case -3802: return "stem batch-statistics training: misaligned buffer";
         case -3601: return "AdamW step: invalid argument (null or not 4-byte aligned pointer, count < 0, n outside [0, 2^40), non-finite scalar, "
                            "bc2_sqrt <= 0)";
         default: break;
@@ -1700,6 +1708,21 @@ int vtd_stem_train_backward(const void* x_tap_dev, int n, int height, int width,
                             void* scratch_dev, vtd_stream stream) {
     return vtd_launch_stem_backward(x_tap_dev, n, height, width, params, eps, workspace_dev, pool_tap_dev, idx_dev, dpool_dev, dscale_dev, grads,
                                     scratch_dev, (hipStream_t)stream);
+}
+
+int64_t vtd_stem_bn_train_workspace_bytes(int n, int height, int width, int mode) { return vtd_stem_bn_ws_bytes(n, height, width, mode); }
+
+int vtd_stem_bn_train_forward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, int training, float momentum, float eps,
+                              void* workspace_dev, void* pool_tap_dev, void* idx_dev, float* stats_dev, vtd_stream stream) {
+    return vtd_launch_stem_bn_forward(x_tap_dev, n, height, width, params, training, momentum, eps, workspace_dev, pool_tap_dev, idx_dev, stats_dev,
+                                      (hipStream_t)stream);
+}
+
+int vtd_stem_bn_train_backward(const void* x_tap_dev, int n, int height, int width, const vtd_stem_params* params, int training, float eps,
+                               const void* workspace_dev, const void* pool_tap_dev, const void* idx_dev, const float* dpool_dev, const float* dscale_dev,
+                               const vtd_stem_params* grads, void* scratch_dev, vtd_stream stream) {
+    return vtd_launch_stem_bn_backward(x_tap_dev, n, height, width, params, training, eps, workspace_dev, pool_tap_dev, idx_dev, dpool_dev, dscale_dev,
+                                       grads, scratch_dev, (hipStream_t)stream);
 }
 
 int64_t vtd_fpn_train_input_workspace_bytes(int n, int h5, int w5, int c5_channels) { return vtd_fpn_input_ws_bytes(n, h5, w5, c5_channels); }

@@ -193,6 +193,11 @@ SIGNATURES = {
                                          C.c_void_p]),
     "vtd_stem_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(StemParams), C.c_void_p, C.c_void_p]),
+    "vtd_stem_bn_train_workspace_bytes": (C.c_int64, [C.c_int] * 4),
+    "vtd_stem_bn_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_stem_bn_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StemParams), C.c_void_p, C.c_void_p]),
     "vtd_detector_forward_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_fpn_train_input_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtd_fpn_train_backward_input": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_int, C.POINTER(FpnTaps),

@@ -140,7 +140,11 @@ _NODE_BN_STAGES = (("layer4",), ("layer3", "layer4"), ("layer2", "layer3", "laye
 _TRAINED_BN_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2", "head+fpn+layer4+layer3+layer2+layer1")
 _TRAINED_BN_BUILT = ("trunk_bn='trained' (train-mode, batch-statistics BatchNorm in every residual stage the mode trains) is built for "
                      "trainable='head+fpn+layer4', 'head+fpn+layer4+layer3', 'head+fpn+layer4+layer3+layer2' and "
-                     "'head+fpn+layer4+layer3+layer2+layer1' on resnet18; the stem keeps frozen statistics")
+                     "'head+fpn+layer4+layer3+layer2+layer1' on resnet18; the stem keeps frozen statistics under 'trained': "
+                     "DBNet(trainable='head+fpn+backbone', trunk_bn='backbone') is the spelling that trains the stem's statistics too")
+# DBNet's trunk_bn="backbone": all twenty BatchNorms of the trunk, the stem's too (csrc/stem_train.hip: vtd_stem_bn_train_*), in train mode
+_BACKBONE_BN_BUILT = ("trunk_bn='backbone' (train-mode, batch-statistics BatchNorm in the stem and in every residual stage) is built for "
+                      "trainable='head+fpn+backbone' on resnet18")
 
 
 def _block_bn_check(block, geometries=_BN_TRAIN_GEOMETRIES, built=_BN_TRAIN_BUILT):
@@ -347,8 +351,16 @@ class FeaturePyramidNetwork(nn.Module):
         srcs = [t if input_grad and t.requires_grad and torch.is_grad_enabled() else None for t in features]
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
-    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False):
-        """`trunk_batch_stats=("layer1", "layer2", "layer3", "layer4")` goes with the tap [pool], `layer1` .. `layer4` and `head` and no `stem`:
+    def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False,
+                       stem_batch_stats=False):
+        """`stem_batch_stats=True` goes with `stem`, `layer1` .. `layer4`, `head`, `trunk_batch_stats=("layer1", "layer2", "layer3", "layer4")` and
+        the tap [image]: the stem -> layer1 -> .. -> layer4 -> FPN -> head node with the stem on the vtd_stem_bn_train_* entries and the eight
+        blocks on vtd_trunk_bn_train_*, so every BatchNorm of the trunk behaves as torch's does in the mode it is in.  The stem's BatchNorm
+        must be in the mode of the eight blocks and keeps its own eps and momentum; anything else raises ValueError before the device is looked
+        at.  The other eighty-seven gradients and the stages' buffers are the bits of the four-stage batch node below on the pooled tap the
+        stem wrote.  Without the keyword every call behaves as before.
+
+        `trunk_batch_stats=("layer1", "layer2", "layer3", "layer4")` goes with the tap [pool], `layer1` .. `layer4` and `head` and no `stem`:
         the layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head node with all eight blocks on the vtd_trunk_bn_train_* entries, in one mode with
         one momentum and one eps, else ValueError before the device is looked at.  layer2.0, layer3.0 and layer4.0 form their input gradients
         (dC2 is layer2.0's plus the FPN's dC2, as in the frozen layer1 node); layer1.0 forms none.
@@ -398,6 +410,8 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
+        if stem_batch_stats:
+            return self._forward_padded_batch_stem(taps, head, layers, stem, trunk_batch_stats, stem_batch_stats)
         bn_stages = ()
         if isinstance(trunk_batch_stats, (tuple, list)):
             bn_stages = tuple(trunk_batch_stats)
@@ -431,17 +445,37 @@ class FeaturePyramidNetwork(nn.Module):
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, (), None, None)      # no trunk stage
         return self._run_node(head, bns, plan, *params, *hparams)
 
+    def _forward_padded_batch_stem(self, taps, head, layers, stem, trunk_batch_stats, stem_batch_stats):
+        """forward_padded(..., stem_batch_stats=True): the whole-backbone node with batch statistics in the stem too."""
+        node = ("forward_padded(..., stem=(conv, bn), trunk_batch_stats=('layer1', 'layer2', 'layer3', 'layer4'), stem_batch_stats=True) is the "
+                "stem -> layer1 -> layer2 -> layer3 -> layer4 -> FPN -> head node with batch statistics in all twenty BatchNorms of the trunk")
+        if stem_batch_stats is not True:
+            raise ValueError(node + f": stem_batch_stats is True or False, got {stem_batch_stats!r}")
+        if not isinstance(trunk_batch_stats, (tuple, list)) or tuple(trunk_batch_stats) != _NODE_BN_STAGES[3]:
+            raise ValueError(node + f": it takes the four-stage tuple, got trunk_batch_stats={trunk_batch_stats!r}")
+        if head is None or any(m is None for m in layers) or not isinstance(stem, (list, tuple)) or len(stem) != 2:
+            raise ValueError(node + ": it needs stem (the pair (conv, bn) of the trunk's first two modules), layer1, layer2, layer3, layer4 and the head")
+        sbn = stem[1]
+        bnm = [m for layer in layers for m in layer.modules() if isinstance(m, nn.BatchNorm2d)]
+        if isinstance(sbn, nn.BatchNorm2d):
+            if sbn.momentum is None:
+                raise ValueError(_STEM_BN_MOMENTUM)
+            if any(m.training != sbn.training for m in bnm):
+                raise ValueError(node + ": the stem's BatchNorm must be in the mode (train() or eval()) of the eight blocks")
+        return self._forward_padded_trunk(taps, head, layers, stem, _NODE_BN_STAGES[3], stem_bn=True)
+
     @staticmethod
     def _run_node(head, bns, plan, *learn):
         prob, thresh, _ = _TrunkFPNHeadTrainFn.apply(plan, *learn)
         head._batches_seen(bns)
         return {"probability": prob, "threshold": thresh}
 
-    def _forward_padded_trunk(self, taps, head, layers, stem, bn_stages):
+    def _forward_padded_trunk(self, taps, head, layers, stem, bn_stages, stem_bn=False):
         """forward_padded with trunk stages: `layers` is (layer1, layer2, layer3, layer4), the node starts at the lowest one given (with `stem`:
         at the stem) and needs every stage above it and the head.  `bn_stages`: () or the stages (all of the node's) that run with batch
         statistics, ("layer4",) on the vtd_resblock_bn_train_* entries, ("layer3", "layer4") on vtd_block_bn_train_*, ("layer2", "layer3",
-        "layer4") or ("layer1", "layer2", "layer3", "layer4") on vtd_trunk_bn_train_*."""
+        "layer4") or ("layer1", "layer2", "layer3", "layer4") on vtd_trunk_bn_train_*.  `stem_bn`: the stem on the vtd_stem_bn_train_* entries (with
+        the four-stage tuple only: _forward_padded_batch_stem)."""
         low = 0 if stem is not None else next(i for i, m in enumerate(layers) if m is not None)
         above = _STAGES[0 if stem is not None else low + 1:]
         if head is None or any(m is None for m in layers[4 - len(above):]):
@@ -472,7 +506,7 @@ class FeaturePyramidNetwork(nn.Module):
             x = taps[-1]
         else:
             sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], taps[0])
-            splan = (sgeom, seps, tuple(sstats))
+            splan = (sgeom, seps, tuple(sstats)) + ((_stem_bn_plan(stem[1], sgeom),) if stem_bn else ())
             x = _meta_tap(sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2, 64)
         dev = taps[-1].device
         ops, outs = [], []      # per stage: _stage_operands' result, and its output C(k) as (n, C, h, w)
@@ -513,6 +547,9 @@ class FeaturePyramidNetwork(nn.Module):
             with torch.no_grad():
                 for b in bbns:
                     b.num_batches_tracked.add_(1)
+        if stem_bn and splan[3][0]:
+            with torch.no_grad():
+                stem[1].num_batches_tracked.add_(1)
         return out
 
 
@@ -563,41 +600,56 @@ def _stem_struct(learn, stats=None):
     return st
 
 
-def _stem_forward_raw(tap, geom, eps, learn, stats):
-    """vtd_stem_train_forward on an image tap: (the pooled padded tap [n,hp+2,wp+2,64] fp16, idx [n,hp,wp,64] uint8, workspace)."""
+def _stem_forward_raw(tap, geom, eps, learn, stats, bn=None, stats_out=None):
+    """vtd_stem_train_forward on an image tap: (the pooled padded tap [n,hp+2,wp+2,64] fp16, idx [n,hp,wp,64] uint8, workspace).  With
+    `bn` = (training, momentum): vtd_stem_bn_train_forward, which with training set normalises with the statistics of the batch and updates
+    `stats` in place; `stats_out` (a float32 CUDA tensor [2,64], optional) then receives the batch's mu and biased sigma^2."""
     n, H, W = geom
     hp, wp = (H // 2 + 1) // 2, (W // 2 + 1) // 2
-    C, _native, lib, ws = _native_workspace("vtd_stem_train_workspace_bytes", (n, H, W, 0), tap.device)
+    query = "vtd_stem_train_workspace_bytes" if bn is None else "vtd_stem_bn_train_workspace_bytes"
+    C, _native, lib, ws = _native_workspace(query, (n, H, W, 0), tap.device)
     pool = torch.empty((n, hp + 2, wp + 2, 64), dtype=torch.float16, device=tap.device)
     idx = torch.empty((n, hp, wp, 64), dtype=torch.uint8, device=tap.device)
     st = _stem_struct(learn, stats)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    _native.check(lib.vtd_stem_train_forward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx),
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_stem_train_forward")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if bn is None:
+        _native.check(lib.vtd_stem_train_forward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx), stream), "vtd_stem_train_forward")
+    else:
+        _native.check(lib.vtd_stem_bn_train_forward(ptr(tap), n, H, W, C.byref(st), int(bn[0]), bn[1], eps, ptr(ws), ptr(pool), ptr(idx),
+                                                    None if stats_out is None else ptr(stats_out), stream), "vtd_stem_bn_train_forward")
     return pool, idx, ws
 
 
-def _stem_backward_raw(tap, geom, eps, learn, stats, ws, pool, idx, dpool, dscale):
-    """vtd_stem_train_backward on dpool as NHWC fp32 [n,hp,wp,64] times dscale[0]: the gradients of [conv.weight, bn.weight, bn.bias]."""
+def _stem_backward_raw(tap, geom, eps, learn, stats, ws, pool, idx, dpool, dscale, bn=None):
+    """vtd_stem_train_backward (with `bn` = (training, momentum): vtd_stem_bn_train_backward) on dpool as NHWC fp32 [n,hp,wp,64] times
+    dscale[0]: the gradients of [conv.weight, bn.weight, bn.bias]."""
     n, H, W = geom
     grads = [torch.empty_like(p) for p in learn]
-    C, _native, lib, scratch = _native_workspace("vtd_stem_train_workspace_bytes", (n, H, W, 1), tap.device)
+    query = "vtd_stem_train_workspace_bytes" if bn is None else "vtd_stem_bn_train_workspace_bytes"
+    C, _native, lib, scratch = _native_workspace(query, (n, H, W, 1), tap.device)
     st, gst = _stem_struct(learn, stats), _stem_struct(grads)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    _native.check(lib.vtd_stem_train_backward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx), ptr(dpool), ptr(dscale), C.byref(gst),
-                                              ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vtd_stem_train_backward")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if bn is None:
+        _native.check(lib.vtd_stem_train_backward(ptr(tap), n, H, W, C.byref(st), eps, ptr(ws), ptr(pool), ptr(idx), ptr(dpool), ptr(dscale), C.byref(gst),
+                                                  ptr(scratch), stream), "vtd_stem_train_backward")
+    else:
+        _native.check(lib.vtd_stem_bn_train_backward(ptr(tap), n, H, W, C.byref(st), int(bn[0]), eps, ptr(ws), ptr(pool), ptr(idx), ptr(dpool), ptr(dscale),
+                                                     C.byref(gst), ptr(scratch), stream), "vtd_stem_bn_train_backward")
     return grads
 
 
 class _StemTrainFn(torch.autograd.Function):
     """The stem on the HIP training kernels (csrc/stem_train.hip): image tap in, the pooled map [n,64,hp,wp] fp32 out, differentiable w.r.t.
-    the convolution's weight and the BatchNorm's gamma and beta.  No gradient of the image is formed."""
+    the convolution's weight and the BatchNorm's gamma and beta.  No gradient of the image is formed.  `bn`: None (vtd_stem_train_*) or
+    (training, momentum) for the vtd_stem_bn_train_* entries."""
 
     @staticmethod
-    def forward(ctx, tap, geom, eps, stats, *learn):
-        pool, idx, ws = _stem_forward_raw(tap, geom, eps, learn, stats)
+    def forward(ctx, tap, geom, eps, stats, bn, *learn):
+        pool, idx, ws = _stem_forward_raw(tap, geom, eps, learn, stats, bn)
         ctx.save_for_backward(tap, pool, idx, *stats, *learn)
-        ctx.ws, ctx.geom, ctx.eps = ws, geom, eps
+        ctx.ws, ctx.geom, ctx.eps, ctx.bn = ws, geom, eps, bn
         return pool[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).float()
 
     @staticmethod
@@ -606,8 +658,8 @@ class _StemTrainFn(torch.autograd.Function):
         tap, pool, idx, mean, var, *learn = ctx.saved_tensors
         dpool = grad_out.to(torch.float32).permute(0, 2, 3, 1).contiguous()
         dscale = torch.ones(2, dtype=torch.float32, device=dpool.device)
-        grads = _stem_backward_raw(tap, ctx.geom, ctx.eps, learn, (mean, var), ctx.ws, pool, idx, dpool, dscale)
-        return (None, None, None, None, *grads)
+        grads = _stem_backward_raw(tap, ctx.geom, ctx.eps, learn, (mean, var), ctx.ws, pool, idx, dpool, dscale, ctx.bn)
+        return (None, None, None, None, None, *grads)
 
 
 def pack_image(x):
@@ -641,7 +693,38 @@ def stem_train(conv, bn, x):
     gradient for ``x`` is None."""
     tap = pack_image(x)
     geom, eps, learn, stats = _stem_operands(conv, bn, tap)
-    return _StemTrainFn.apply(tap, geom, eps, tuple(stats), *learn)
+    return _StemTrainFn.apply(tap, geom, eps, tuple(stats), None, *learn)
+
+
+_STEM_BN_MOMENTUM = ("the HIP batch-statistics stem kernels need a fixed momentum on the stem's BatchNorm (momentum=None, the cumulative average, "
+                     "is not built)")
+
+
+def _stem_bn_plan(bn, geom):
+    """(training, momentum) for the vtd_stem_bn_train_* entries from the stem's BatchNorm, validated before the device is looked at."""
+    if bn.momentum is None:
+        raise ValueError(_STEM_BN_MOMENTUM)
+    n, H, W = geom
+    if bn.training and n * (H // 2) * (W // 2) < 2:
+        raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a conv map of {n} x {H // 2} x {W // 2}")
+    return (bool(bn.training), float(bn.momentum))
+
+
+def stem_bn_train(conv, bn, x):
+    """``stem_train`` on the vtd_stem_bn_train_* entries (csrc/stem_train.hip) with torch's module semantics, the counterpart of
+    ``trunk_block_bn_train``: in ``bn.training`` mode the statistics of the batch normalise, ``bn.running_mean`` and ``bn.running_var`` are
+    updated in place (the unbiased variance, the BatchNorm's own fixed momentum) and ``bn.num_batches_tracked`` advances; in ``eval()`` mode
+    it gives the bits of ``stem_train(conv, bn, x)`` and writes no buffer.  Differentiable w.r.t. ``conv.weight``, ``bn.weight`` and
+    ``bn.bias`` -- the full BatchNorm backward in train mode --; the gradient for ``x`` is None."""
+    if isinstance(bn, nn.BatchNorm2d) and bn.momentum is None:      # what is built, before anything about the device
+        raise ValueError(_STEM_BN_MOMENTUM)
+    tap = pack_image(x)
+    geom, eps, learn, stats = _stem_operands(conv, bn, tap)
+    out = _StemTrainFn.apply(tap, geom, eps, tuple(stats), _stem_bn_plan(bn, geom), *learn)
+    if bn.training:
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+    return out
 
 
 def forward_stem_padded(conv, bn, image_tap):
@@ -841,7 +924,8 @@ _RESBLOCK = "vtd_resblock_train"       # the entry family of the six geometries 
 _BLOCK64 = "vtd_block64_train"         # the entry family of layer1's 64 -> 64 block
 _RESBLOCK_BN = "vtd_resblock_bn_train"   # layer4's two geometries with batch-statistics BatchNorm (csrc/resblock_bn_train.hip)
 _BLOCK_BN = "vtd_block_bn_train"         # layer3's and layer4's four with batch-statistics BatchNorm, and the strided dx (the same file)
-_TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two and layer1's one as well, seven in all: the family the stem joins (the same file)
+_TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two and layer1's one as well, seven in all (the same file); the stem's batch-statistics
+                                         # entries, vtd_stem_bn_train_*, are csrc/stem_train.hip's
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
@@ -1039,7 +1123,8 @@ class _FPNTrainFn(torch.autograd.Function):
 
 # What one run of the trunk node is, built by FeaturePyramidNetwork.forward_padded.  _TrunkPlan: `taps` the padded taps the node reads, `geom`
 # the FPN's geometry, `head` the head's (BatchNorm mode, momentum, eps, running-stat buffers), `stem` None or the stem's (geometry, eps,
-# running statistics), `blocks` a _BlockPlan for each BasicBlock from the lowest up (none: the FPN and the head alone) with `beps` their eps,
+# running statistics) with (training, momentum) as a fourth entry for the vtd_stem_bn_train_* entries, `blocks` a _BlockPlan for each
+# BasicBlock from the lowest up (none: the FPN and the head alone) with `beps` their eps,
 # `bn` None or (training, momentum) for blocks on the batch-statistics entries.  _BlockPlan: the block's geometry, its running statistics,
 # its entry family and the count of its learnable tensors (9 with a downsample, 6 without)
 _TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn")
@@ -1078,8 +1163,8 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
         training, momentum, eps, hbuffers = plan.head
         x, stem_saved = plan.taps[-1], ()
         if plan.stem is not None:
-            sgeom, seps, sstats = plan.stem
-            x, idx, ctx.sws = _stem_forward_raw(plan.taps[0], sgeom, seps, slearn, sstats)
+            sgeom, seps, sstats, *sbn = plan.stem      # sbn: nothing, or [(training, momentum)] for the batch-statistics entries
+            x, idx, ctx.sws = _stem_forward_raw(plan.taps[0], sgeom, seps, slearn, sstats, *sbn)
             stem_saved = (x, idx)
         acts, bws = [], []
         for b, learn in zip(plan.blocks, blearn):      # acts: each block's output; every second one is a C(k)
@@ -1119,8 +1204,8 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
                 d, ds = _combine_scaled(d, ds, dtaps[level], scales[level])      # the stage's share of dC(k) + the FPN's
         sgrads = ()
         if plan.stem is not None:      # layer1.0's input gradient is the stem's dpool
-            sgeom, seps, sstats = plan.stem
-            sgrads = _stem_backward_raw(plan.taps[0], sgeom, seps, slearn, sstats, ctx.sws, *stem_saved, d, ds)
+            sgeom, seps, sstats, *sbn = plan.stem
+            sgrads = _stem_backward_raw(plan.taps[0], sgeom, seps, slearn, sstats, ctx.sws, *stem_saved, d, ds, *sbn)
         return (None, *sgrads, *(g for gs in bgrads for g in gs), *fgrads, *hgrads)
 
 
@@ -1316,8 +1401,12 @@ class DBNet(_EngineOwner, nn.Module):
         the vtd_trunk_bn_train_* entries -- backbone.5 .. backbone.7's fifteen BatchNorms normalise with the statistics of the batch, and their
         30 running buffers and 15 counters move every step; a following eval() forward rebuilds the inference engine on the new statistics.
         On the fourth the trunk engine gives the pooled stem output as with "frozen", then layer1 .. layer4 run on the same entries:
-        backbone.4 .. backbone.7's nineteen BatchNorms (layer1's blocks have no downsample), 38 running buffers and 19 counters.  The stem keeps frozen statistics: "head+fpn+backbone"
-        with "trained" is refused.
+        backbone.4 .. backbone.7's nineteen BatchNorms (layer1's blocks have no downsample), 38 running buffers and 19 counters.  The stem keeps
+        frozen statistics under "trained": "head+fpn+backbone" with "trained" is refused.
+        "backbone" (resnet18 with trainable="head+fpn+backbone" only; anything else raises ValueError and leaves the network as it was): the
+        whole-backbone node with the stem on the vtd_stem_bn_train_* entries and layer1 .. layer4 on vtd_trunk_bn_train_* -- all twenty
+        BatchNorms of the trunk normalise with the statistics of the batch, as the reference's model.train() step does, and their 40 running
+        buffers and 20 counters move every step.
         A tuple names exactly the residual stages the mode trains, else ValueError: ("layer4",) goes with
         trainable="head+fpn+layer4" and is equivalent to "batch"; ("layer3", "layer4") goes with trainable="head+fpn+layer4+layer3" on resnet18:
         the trunk engine gives C2 and C3 as with "frozen", then layer3 and layer4 run on the vtd_block_bn_train_* entries -- backbone.6's and
@@ -1358,7 +1447,7 @@ class DBNet(_EngineOwner, nn.Module):
         is frozen, 90 tensors train.  A forward in train mode packs the image (nets.pack_image) and runs the stem (csrc/stem_train.hip),
         layer1 .. layer4, the FPN and the head on the HIP training kernels as one autograd node; no trunk engine is built or read.  layer1.0
         forms its input gradient, which is the stem's upstream gradient; the stem's BatchNorm, like every trunk BatchNorm, normalises with
-        its running statistics, which are never written.  No gradient of the image is formed."""
+        its running statistics, which are never written -- unless trunk_bn="backbone" (above).  No gradient of the image is formed."""
         if trainable in _STAGE_MODES or trainable == _BACKBONE_MODE:
             if self.backbone_name != "resnet18":
                 raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
@@ -1371,8 +1460,10 @@ class DBNet(_EngineOwner, nn.Module):
             fits = next((mode for stages, mode in _TRUNK_BN_STAGES.items() if stages == bn_mode), None)      # no hashing: any tuple may come
             if self.backbone_name != "resnet18" or fits is None or fits != trainable:
                 raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r} on {self.backbone_name}: " + _TRUNK_BN_BUILT)
-        elif not isinstance(bn_mode, str) or bn_mode not in ("frozen", "batch", "trained"):
-            raise ValueError(f"trunk_bn must be 'frozen' or 'batch' (or 'trained', or a tuple of stage names), got {bn_mode!r}")
+        elif not isinstance(bn_mode, str) or bn_mode not in ("frozen", "batch", "trained", "backbone"):
+            raise ValueError(f"trunk_bn must be 'frozen' or 'batch' (or 'trained', 'backbone', or a tuple of stage names), got {bn_mode!r}")
+        if bn_mode == "backbone" and (self.backbone_name != "resnet18" or trainable != _BACKBONE_MODE):
+            raise ValueError(f"trunk_bn='backbone' with trainable={trainable!r} on {self.backbone_name}: " + _BACKBONE_BN_BUILT)
         if bn_mode == "trained" and (self.backbone_name != "resnet18" or trainable not in _TRAINED_BN_MODES):
             raise ValueError(f"trunk_bn='trained' with trainable={trainable!r} on {self.backbone_name}: " + _TRAINED_BN_BUILT)
         if bn_mode == "batch" and trainable != "head+fpn+layer4":
@@ -1550,8 +1641,10 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         dev = next(self.head.parameters()).device
         image = pack_image(x if x.is_cuda else x.to(dev))   # no trunk engine: the stem runs on the training kernels too
+        # trunk_bn="backbone": the stem and the eight blocks on the batch-statistics entries; their running statistics move too (mark_dirty below)
+        batch = {"trunk_batch_stats": _NODE_BN_STAGES[3], "stem_batch_stats": True} if getattr(self, "trunk_bn", "frozen") == "backbone" else {}
         out = self.fpn.forward_padded([image], head=self.head, layer4=self.backbone[7], layer3=self.backbone[6], layer2=self.backbone[5],
-                                      layer1=self.backbone[4], stem=(self.backbone[0], self.backbone[1]))
+                                      layer1=self.backbone[4], stem=(self.backbone[0], self.backbone[1]), **batch)
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
