@@ -369,6 +369,51 @@ int vtd_block64_train_backward(const void* x_dev, int n, int h_in, int w_in, int
                                float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- ResNet Bottleneck training with frozen-statistics BatchNorm (csrc/bottleneck_train.hip), v1.5 (the stride sits on the 3x3):
+ * y = relu(bn3(conv3(a2)) + id), a2 = relu(bn2(conv2(a1))), a1 = relu(bn1(conv1(x))), id = x or ds_bn(ds(x)); conv1 is 1x1 cin -> width,
+ * conv2 3x3 width -> width at `stride`, conv3 1x1 width -> 4 width, ds 1x1 cin -> 4 width at `stride`.  Tensors, layouts, the folded weights
+ * packed on the device in every call, the running statistics that normalise and are never written, the power-of-two gradient scales and
+ * the "written, not accumulated" rule are those of vtd_basicblock_train_*: x_dev [n][h_in+2][w_in+2][cin], y_dev [n][h+2][w+2][4 width]
+ * with h = h_in / stride, padded taps.  Two geometries are built, the blocks of ResNet-50's last stage (res5, torchvision's layer4), width
+ * 512: (cin 1024, stride 2, even h_in and w_in, with downsample: ds_* set) and (cin 2048, stride 1, identity: ds_* ignored).  Every other
+ * geometry, n > 65535, an extent above 4096 and a tensor of 2^31 elements or more are refused with -3901.
+ * vtd_bottleneck_train_workspace_bytes, with a256(b) = b rounded up to a multiple of 256, W = 512, pin = n (h_in+2) (w_in+2),
+ * pout = n (h+2) (w+2), M = n h w, Min = n h_in w_in and S(r) = min(8, max(1, ceil(r / 4096))):
+ *   mode 0, the forward's workspace, which the backward keeps: a256(2 pin W) [a1, padded at the INPUT's extent] + a256(2 pout W) [a2] +
+ *     a256(2 pout 4W) [id, stride 2 only] + a256(2 W cin) + a256(2 W 9 W) + a256(2 4W W) + a256(2 4W cin) [stride 2 only] (the four folded
+ *     panels) + a256(4 (2 W + 2 4W)) [the biases];
+ *   mode 1, the backward's scratch: a256(4 M 4W) + a256(4 M W) + a256(4 Min W) [g3, g2, g1 fp32] + a256(2 M 4W) + a256(2 M W) +
+ *     a256(2 Min W) [flat fp16 operands] + a256(2 pout 4W) + 2 a256(2 pin W) [padded fp16 operands; g2's is the zero-inserted plane at stride
+ *     2] + a256(2 W 9 W) [transposed panel] + a256(4 4W) [zero bias] + a256(8 256 4W) + a256(4 256) [partials] + a256(8 4W) + 2 a256(8 W) [sums]
+ *     + a256(48) [scales] + a256(4 max(S(M) W 9 W, S(Min) W cin)) [weight-gradient slabs].
+ * vtd_bottleneck_train_backward: dy_dev is NHWC float32 [n][h][w][4 width] times dscale_dev[0] (dscale_dev = {scale, 1 / scale}, a power
+ * of two).  Gradients are written into the grads struct's twelve (stride 1: nine) learnable fields; its *_mean / *_var are ignored.  Per
+ * convolution + BatchNorm pair, with g the gradient at the BatchNorm output, G = g^T im2col(input) (MFMA, wgrad_mfma.h MODE 3, slabs
+ * summed in slab order in fp64) and s = sum g:  dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s); nothing divides by gamma.
+ * Fixed orders: the 2048-wide gradient g3 = dy (y > 0) is summed per channel by min(256, ceil(M / 32)) workgroups of ceil(M / that)
+ * consecutive rows each, every row in row order in fp64, the partials then in workgroup order; the 512-wide g2 = conv3^T(g3) (a2 > 0) and
+ * g1 = conv2^T(g2) (a1 > 0) by min(256, ceil(rows / 256)) workgroups the same way; every weight-gradient launch cuts ITS rows into
+ * S(rows) slabs -- conv3, conv2 and the downsample the M output rows, conv1 the Min rows of the input's extent, where g1 lives.
+ * conv2^T at stride 2 is the stride-1 rotated, transposed 3x3 path over g2 written into the even positions of a zeroed plane of the
+ * input's size, as vtd_resblock_train_backward's.  dx_dev (optional, with dxscale_dev = {scale, 1 / scale}) is formed for both
+ * geometries: NHWC float32 [n][h_in][w_in][cin] times dxscale_dev[0] = conv1^T(g1), plus g3 (stride 1) or ds^T(g3) at the even (row,
+ * column) positions (stride 2), each summand brought to g1's power-of-two scale before the add.
+ * No atomics, shape-only grids: bitwise repeatable.  Errors, before any launch: -3901 (a null pointer, eps <= 0, dx_dev without dxscale_dev,
+ * a missing ds_* tensor at stride 2, a mode outside {0, 1}, an unsupported geometry), -3902 (alignment: taps, dy and dx 16 bytes, workspace
+ * and scratch 256, scales 8, parameters and gradients 4). */
+typedef struct vtd_bottleneck_params {
+    float *conv1_w, *bn1_w, *bn1_b, *bn1_mean, *bn1_var;
+    float *conv2_w, *bn2_w, *bn2_b, *bn2_mean, *bn2_var;
+    float *conv3_w, *bn3_w, *bn3_b, *bn3_mean, *bn3_var;
+    float *ds_w, *ds_bn_w, *ds_bn_b, *ds_bn_mean, *ds_bn_var;
+} vtd_bottleneck_params;
+int64_t vtd_bottleneck_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_bottleneck_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                 float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_bottleneck_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                  float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
+                                  const vtd_bottleneck_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
 /* ---- ResNet BasicBlock training with batch-statistics BatchNorm (csrc/resblock_bn_train.hip): the same block as torch's train() mode
  * computes it.  Tensors, layouts, the vtd_basicblock_params struct, the power-of-two gradient scales and the "written, not accumulated" rule
  * are those of vtd_basicblock_train_*.  Two geometries are built, ResNet-18's layer4: (cin 256, width 512, stride 2, even h_in and w_in, with

@@ -1,6 +1,7 @@
-// What the two ResNet BasicBlock training files share (resblock_train.hip: frozen-statistics BatchNorm; resblock_bn_train.hip: batch
-// statistics): the padded-tap helpers, the ReLU mask, the identity add, the weight-gradient slab rules, the argument checks and the
-// convolution descriptor.
+// What the ResNet block training files share (resblock_train.hip: BasicBlocks with frozen-statistics BatchNorm; resblock_bn_train.hip: batch
+// statistics; bottleneck_train.hip: ResNet-50's Bottlenecks): the padded-tap helpers, the ReLU mask, the identity add, the weight-gradient
+// slab rules, the argument checks and the convolution descriptor; and the kernels of the frozen-statistics path that take every width from
+// their launch: the fold, the reduce's finish, the fp16 operand forming, the dgrad panel and the parameter gradients.
 #ifndef VTD_RESBLOCK_COMMON_H
 #define VTD_RESBLOCK_COMMON_H
 #include "vtd_common.h"
@@ -72,6 +73,138 @@ __global__ __launch_bounds__(RB_THREADS) void rb_add_identity_kernel(float* dx, 
 
 __global__ void rb_copy_scale_kernel(const float* sc, float* out) {
     if (threadIdx.x < 2) out[threadIdx.x] = sc[threadIdx.x];
+}
+
+// ---- kernels that take every width and extent from their launch: shared with bottleneck_train.hip -------------------------------------
+// wp [W][ksz^2 cin], k = tap * cin + ci: half(w[co][ci][tap] gamma rstd); bias[co] = beta - mean gamma rstd
+__global__ __launch_bounds__(RB_THREADS) void rb_fold_kernel(const float* w, const float* gam, const float* bet, const float* mean, const float* var,
+                                                             float eps, int W, int cin, int taps, half_t* wp, float* bias) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    const int K = taps * cin;
+    if (i < (int64_t)W * K) {
+        const int co = (int)(i / K), k = (int)(i - (int64_t)co * K), tap = k / cin, ci = k - tap * cin;
+        const float sc = gam[co] / sqrtf(var[co] + eps);
+        wp[i] = (half_t)(w[((int64_t)co * cin + ci) * taps + tap] * sc);
+    } else if (i < (int64_t)W * K + W) {
+        const int co = (int)(i - (int64_t)W * K);
+        bias[co] = bet[co] - mean[co] * (gam[co] / sqrtf(var[co] + eps));
+    }
+}
+
+// v [rows][W] fp32, W = 256 or 512: thread t owns channel t (and t + 256 of a 512-wide v) over the rows of its workgroup, in row order:
+// part[g][W] fp64, pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, int64_t rows, int64_t per, int W, double* part, float* pmax) {
+    const int t = threadIdx.x;
+    const bool two = W > 256;
+    const int64_t m0 = (int64_t)blockIdx.x * per, m1 = m0 + per < rows ? m0 + per : rows;
+    double s0 = 0.0, s1 = 0.0;
+    float mx = 0.f;
+    for (int64_t m = m0; m < m1; ++m) {
+        const float a = v[m * W + t], b = two ? v[m * W + 256 + t] : 0.f;
+        s0 += (double)a; s1 += (double)b;
+        const float fa = fabsf(a), fb = fabsf(b);
+        mx = fa > mx || fa != fa ? fa : mx;
+        mx = fb > mx || fb != fb ? fb : mx;
+    }
+    part[(int64_t)blockIdx.x * W + t] = s0;
+    if (two) part[(int64_t)blockIdx.x * W + 256 + t] = s1;
+    __shared__ float shm[RB_THREADS];
+    shm[t] = mx;
+    __syncthreads();
+    if (t == 0) {
+        float m = shm[0];
+        for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
+        pmax[blockIdx.x] = m;
+    }
+}
+
+// partials in workgroup order: sum[c] = the channel sum with the incoming scale undone (fp64); out_sc = {total scale, 1 / total,
+// this stage's multiplier, 0}, the multiplier a power of two from max |v| (1 when that is zero or not finite)
+__global__ __launch_bounds__(RB_THREADS) void rb_finish_kernel(const double* part, const float* pmax, int G, int W, const float* in_sc, double* sum,
+                                                               float* out_sc) {
+    const int t = threadIdx.x;
+    for (int c = t; c < W; c += RB_THREADS) {
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) s += part[(int64_t)g * W + c];
+        sum[c] = s * (double)in_sc[1];
+    }
+    if (t == 0) {
+        float mx = pmax[0];
+        for (int g = 1; g < G; ++g) mx = pmax[g] > mx || pmax[g] != pmax[g] ? pmax[g] : mx;
+        const double tin = (double)in_sc[0];
+        int e = 0;
+        if (mx > 0.f && isfinite(mx)) e = (int)floor(log2((double)RB_SCALE_TARGET / (double)mx));
+        const int ein = (tin > 0.0 && isfinite(tin)) ? ilogb(tin) : 0;
+        int et = ein + e;
+        et = et < -120 ? -120 : et > 120 ? 120 : et;
+        e = et - ein;
+        const double tot = tin * ldexp(1.0, e);
+        out_sc[0] = (float)tot; out_sc[1] = (float)(1.0 / tot); out_sc[2] = ldexpf(1.0f, e); out_sc[3] = 0.f;
+    }
+}
+
+// v times the multiplier as fp16: flat [rows][W] (when given) and a ring-padded plane [n][dil H + 2][dil Wd + 2][W] at pixel (dil y, dil x):
+// dil = 1 fills the interior, dil = 2 the even positions of the stride-2 dgrad's zero-inserted plane.  One thread = 8 channels.
+__global__ __launch_bounds__(RB_THREADS) void rb_form_kernel(const float* v, int64_t rows, const float* sc, int H, int Wd, int W, int dil, half_t* flat,
+                                                             half_t* padded) {
+    const int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x;
+    const int C8 = W >> 3;
+    if (i >= rows * C8) return;
+    const float mul = sc[2];
+    const floatx4 v0 = *(const floatx4*)(v + i * 8), v1 = *(const floatx4*)(v + i * 8 + 4);
+    half8 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { h[e] = (half_t)(v0[e] * mul); h[4 + e] = (half_t)(v1[e] * mul); }
+    if (flat) *(half8*)(flat + i * 8) = h;
+    const int64_t m = i / C8;
+    const int c8 = (int)(i % C8), HW = H * Wd;
+    const int img = (int)(m / HW), rem = (int)(m - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    *(half8*)(padded + (((int64_t)img * (dil * H + 2) + dil * y + 1) * (dil * Wd + 2) + dil * x + 1) * W + c8 * 8) = h;
+}
+
+// wt [cin][taps * W]: row ci, k = tap' * W + co holds half(w[co][ci][taps - 1 - tap'] gamma rstd) (the window rotated by 180 degrees, the
+// folded weights transposed, rounded as the forward packs them); a zero bias row of W entries
+__global__ __launch_bounds__(RB_THREADS) void rb_pack_dgrad_kernel(const float* w, const float* gam, const float* var, float eps, int W, int cin, int taps,
+                                                                   half_t* wt, float* zero) {
+    const int i = blockIdx.x * RB_THREADS + threadIdx.x;
+    const int K = taps * W;
+    if (i < cin * K) {
+        const int ci = i / K, k = i - ci * K, tap = k / W, co = k - tap * W;
+        wt[i] = (half_t)(w[((int64_t)co * cin + ci) * taps + (taps - 1 - tap)] * (gam[co] / sqrtf(var[co] + eps)));
+    } else if (i < cin * K + W) {
+        zero[i - cin * K] = 0.f;
+    }
+}
+
+// One workgroup per output channel c.  G[c][k] = the slabs summed in slab order (fp64) with the scale undone, k = tap * cin + ci;
+// dW[c][ci][tap] = gamma rstd G; dbeta = s; dgamma = rstd (sum_k w[c][k] G[c][k] - mean s), the sum in fp64 in a fixed tree order
+__global__ __launch_bounds__(RB_THREADS) void rb_param_kernel(const float* slab, int S, int cin, int taps, const float* sc, const double* sum, const float* w,
+                                                              const float* gam, const float* mean, const float* var, float eps, float* dw, float* dgam,
+                                                              float* dbet) {
+    const int c = blockIdx.x, t = threadIdx.x, K = taps * cin;
+    const double rstd = 1.0 / sqrt((double)var[c] + (double)eps), inv = (double)sc[1], f = (double)gam[c] * rstd;
+    const int64_t nel = (int64_t)gridDim.x * K;
+    double dot = 0.0;
+    for (int k = t; k < K; k += RB_THREADS) {
+        double G = 0.0;
+        for (int s = 0; s < S; ++s) G += (double)slab[(int64_t)s * nel + (int64_t)c * K + k];
+        G *= inv;
+        const int tap = k / cin, ci = k - tap * cin;
+        const int64_t wi = ((int64_t)c * cin + ci) * taps + tap;
+        dw[wi] = (float)(f * G);
+        dot += (double)w[wi] * G;
+    }
+    __shared__ double sh[RB_THREADS];
+    sh[t] = dot;
+    __syncthreads();
+    for (int o = RB_THREADS / 2; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        dgam[c] = (float)(rstd * (sh[0] - (double)mean[c] * sum[c]));
+        dbet[c] = (float)sum[c];
+    }
 }
 
 bool bn_ok(const float* w, const float* b, const float* m, const float* v) {

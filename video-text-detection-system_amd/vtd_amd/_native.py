@@ -57,6 +57,14 @@ class BasicBlockParams(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in BLOCK_FIELDS]
 
 
+BOTTLENECK_FIELDS = BLOCK_FIELDS[:10] + ("conv3_w", "bn3_w", "bn3_b", "bn3_mean", "bn3_var") + BLOCK_FIELDS[10:]
+
+
+class BottleneckParams(C.Structure):
+    """vtd_bottleneck_params of include/vtd.h: device pointers to one Bottleneck's fp32 tensors, PyTorch layouts"""
+    _fields_ = [(k, C.c_void_p) for k in BOTTLENECK_FIELDS]
+
+
 class StemParams(C.Structure):
     """vtd_stem_params of include/vtd.h: device pointers to the stem's fp32 tensors (conv weight, BatchNorm gamma, beta, running mean, var)"""
     _fields_ = [(k, C.c_void_p) for k in ("w", "gamma", "beta", "mean", "var")]
@@ -165,6 +173,10 @@ SIGNATURES = {
     "vtd_resblock_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.POINTER(BasicBlockParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_resblock_train_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
+    "vtd_bottleneck_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(BottleneckParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
     "vtd_block64_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

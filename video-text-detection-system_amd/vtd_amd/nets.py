@@ -173,7 +173,8 @@ def basic_block_train(block, x, batch_stats=False):
     block's learnable tensors and w.r.t. ``x`` for either stride (the stride-2 blocks through the strided dgrad).  For layer4's blocks the
     output and the parameter gradients are the bits of ``block(x)``."""
     if not isinstance(block, BasicBlock):
-        raise RuntimeError("basic_block_train is built for ResNet-18's BasicBlocks; Bottleneck training is not built")
+        raise RuntimeError("basic_block_train is built for ResNet-18's BasicBlocks; Bottleneck training is not built here "
+                           "(ResNet-50's last stage goes to bottleneck_train)")
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != block.conv1.in_channels:
         raise ValueError(f"BasicBlock input must be a [n,{block.conv1.in_channels},H,W] tensor")
     bns = _block_bn_check(block) if batch_stats else None   # what is built, before anything about the device
@@ -256,6 +257,93 @@ class Bottleneck(_Residual):
         self.stride = stride
         if stride != 1 or cin != width * 4:
             self.downsample = nn.Sequential(*_conv_bn(cin, width * 4, 1, stride, 0))
+
+
+# the Bottleneck geometries csrc/bottleneck_train.hip builds: ResNet-50's last stage (res5, torchvision's layer4), (cin, width, stride, downsample)
+_BOTTLENECK_GEOMETRIES = ((1024, 512, 2, True), (2048, 512, 1, False))
+_BOTTLENECK_BUILT = ("bottleneck_train is built for the Bottlenecks of ResNet-50's last stage, res5 (1024 -> 512 -> 2048 stride 2 with downsample and "
+                     "even extents, 2048 -> 512 -> 2048 stride 1), with frozen-statistics BatchNorm")
+_RES5_BUILT = ("res5 training is built for ResNet-50's last stage: three Bottlenecks of width 512 (1024 -> 2048 stride 2 with downsample, then "
+               "2048 -> 2048 stride 1, twice) on a C4 tap of 1024 channels and even extents, with one BatchNorm eps")
+
+
+def _bottleneck_pairs(block):
+    return ([(block.conv1, block.bn1), (block.conv2, block.bn2), (block.conv3, block.bn3)] +
+            ([(block.downsample[0], block.downsample[1])] if hasattr(block, "downsample") else []))
+
+
+def _bottleneck_check(block):
+    """((cin, width, stride), eps) of a Bottleneck that csrc/bottleneck_train.hip runs, judged without looking at any device."""
+    if not isinstance(block, Bottleneck):
+        raise RuntimeError(f"{type(block).__name__}: " + _BOTTLENECK_BUILT + " (a BasicBlock goes to basic_block_train)")
+    cin, width = block.conv1.in_channels, block.conv1.out_channels
+    if (cin, width, block.stride, hasattr(block, "downsample")) not in _BOTTLENECK_GEOMETRIES:
+        raise RuntimeError(f"Bottleneck({cin} -> {width} -> {4 * width}, stride {block.stride}): " + _BOTTLENECK_BUILT)
+    if any(bn.eps != block.bn1.eps or not bn.track_running_stats for _, bn in _bottleneck_pairs(block)):
+        raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms, with running stats tracked")
+    return (cin, width, block.stride), float(block.bn1.eps)
+
+
+def _bottleneck_operands(block, device):
+    """((cin, width, stride), eps, the 9 or 12 learnable tensors, the running statistics) as vtd_bottleneck_train_* take them, validated."""
+    geom, eps = _bottleneck_check(block)
+    learn, stats = [], []
+    for conv, bn in _bottleneck_pairs(block):
+        learn += [conv.weight, bn.weight, bn.bias]
+        stats += [bn.running_mean, bn.running_var]
+    for t in learn + stats:
+        if not t.is_cuda or t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("Bottleneck parameters and buffers must be contiguous float32 CUDA tensors on the input's device "
+                             "(call .cuda() on the model)")
+    return geom, eps, learn, stats
+
+
+def bottleneck_train(block, x):
+    """One Bottleneck of ResNet-50's last stage on the HIP training kernels (csrc/bottleneck_train.hip) as a differentiable function of a CUDA
+    NCHW tensor (fp32 or fp16): 1024 -> 512 -> 2048 at stride 2 (with downsample, even extents) or 2048 -> 512 -> 2048 at stride 1.
+    Frozen-statistics BatchNorm -- the running statistics normalise and are never written, whatever ``training`` says.  Returns
+    ``[n,2048,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9 learnable tensors and w.r.t. ``x`` at either stride.  Everything else is
+    refused before the device is looked at."""
+    (cin, width, stride), eps = _bottleneck_check(block)
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != cin:
+        raise ValueError(f"Bottleneck input must be a [n,{cin},H,W] tensor")
+    n, _, hin, win = x.shape
+    if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
+        raise RuntimeError(f"Bottleneck(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise ValueError("Bottleneck runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    _, _, learn, stats = _bottleneck_operands(block, x.device)
+    src = x if x.requires_grad and torch.is_grad_enabled() else None
+    return _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _BOTTLENECK, None, *learn)
+
+
+def _res5_operands(layer, tap, device=None):
+    """ResNet-50's last stage on a padded C4 tap: (the three blocks, their geometries, eps, their learnable tensors, their running
+    statistics).  Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
+    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
+    if len(blocks) != 3 or not all(isinstance(b, Bottleneck) for b in blocks):
+        raise RuntimeError(_RES5_BUILT)
+    checks = [_bottleneck_check(b) for b in blocks]
+    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
+    if [c[0] for c in checks] != [(1024, 512, 2), (2048, 512, 1), (2048, 512, 1)] or tap.shape[3] != 1024 or h % 2 or w % 2 or len({c[1] for c in checks}) > 1:
+        raise RuntimeError(_RES5_BUILT)
+    ops = [_bottleneck_operands(b, tap.device if device is None else device) for b in blocks]
+    geoms = [(n, h, w, 1024, 512, 2), (n, h // 2, w // 2, 2048, 512, 1), (n, h // 2, w // 2, 2048, 512, 1)]
+    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_res5_padded(layer, c4_tap):
+    """ResNet-50's last stage (res5: three Bottlenecks) on a padded C4 tap with the HIP training kernels, no gradient: padded C5
+    [n,h5+2,w5+2,2048] fp16 with a zero ring."""
+    if not torch.is_tensor(c4_tap) or c4_tap.dim() != 4:
+        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+    _, geoms, eps, learn, stats = _res5_operands(layer, c4_tap)
+    _check_padded_taps([c4_tap])
+    with torch.no_grad():
+        x = c4_tap.detach()
+        for g, lr, st in zip(geoms, learn, stats):
+            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK)[0]
+        return x
 
 
 _PLANS = {
@@ -352,8 +440,15 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False,
-                       stem_batch_stats=False):
-        """`stem_batch_stats=True` goes with `stem`, `layer1` .. `layer4`, `head`, `trunk_batch_stats=("layer1", "layer2", "layer3", "layer4")` and
+                       stem_batch_stats=False, res5=None):
+        """`res5` (ResNet-50's last stage, an nn.Sequential of three Bottlenecks of width 512) goes with a DBHead and the padded taps [C2, C3, C4]
+        of 256, 512 and 1024 channels (a fourth entry is ignored: C5 is computed here from C4): res5 -> FPN -> head as ONE autograd node on the
+        vtd_bottleneck_train_* entries (csrc/bottleneck_train.hip, frozen-statistics BatchNorm), differentiable w.r.t. the stage's thirty
+        learnable tensors, the FPN's ten and the head's twenty.  dC5 goes into the last block as the FPN leaves it; blocks 2 and 1 form their
+        input gradients, block 0 forms none.  With `layer1` .. `layer4`, `stem`, `trunk_batch_stats` or `stem_batch_stats`, or without a head,
+        it raises ValueError.
+
+        `stem_batch_stats=True` goes with `stem`, `layer1` .. `layer4`, `head`, `trunk_batch_stats=("layer1", "layer2", "layer3", "layer4")` and
         the tap [image]: the stem -> layer1 -> .. -> layer4 -> FPN -> head node with the stem on the vtd_stem_bn_train_* entries and the eight
         blocks on vtd_trunk_bn_train_*, so every BatchNorm of the trunk behaves as torch's does in the mode it is in.  The stem's BatchNorm
         must be in the mode of the eight blocks and keeps its own eps and momentum; anything else raises ValueError before the device is looked
@@ -410,6 +505,13 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
+        if res5 is not None:
+            if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
+                raise ValueError("forward_padded(taps, head=head, res5=...) is ResNet-50's res5 -> FPN -> head node with frozen-statistics BatchNorm: it "
+                                 "takes no layer1 .. layer4, stem, trunk_batch_stats or stem_batch_stats (those are ResNet-18's)")
+            if head is None:
+                raise ValueError("forward_padded(taps, res5=...) is the training node: it needs the DBHead too")
+            return self._forward_padded_res5(taps, head, res5)
         if stem_batch_stats:
             return self._forward_padded_batch_stem(taps, head, layers, stem, trunk_batch_stats, stem_batch_stats)
         bn_stages = ()
@@ -444,6 +546,22 @@ class FeaturePyramidNetwork(nn.Module):
         bns, hparams, hbuffers = head._train_operands(taps[0].device)
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, (), None, None)      # no trunk stage
         return self._run_node(head, bns, plan, *params, *hparams)
+
+    def _forward_padded_res5(self, taps, head, res5):
+        """forward_padded(taps, head=head, res5=layer): the plan of three Bottleneck blocks in one stage."""
+        if not isinstance(taps, (list, tuple)) or len(taps) < 3:
+            raise ValueError("padded taps must be the tensors [C2, C3, C4]")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:3])
+        _check_padded_taps(taps)
+        dev = taps[-1].device
+        _, geoms, beps, learn, stats = _res5_operands(res5, taps[-1], dev)
+        n, h, w = geoms[-1][:3]
+        geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 2048, h, w)])
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        blocks = tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms, learn, stats))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, 3)
+        return self._run_node(head, bns, plan, *(t for lr in learn for t in lr), *params, *hparams)
 
     def _forward_padded_batch_stem(self, taps, head, layers, stem, trunk_batch_stats, stem_batch_stats):
         """forward_padded(..., stem_batch_stats=True): the whole-backbone node with batch statistics in the stem too."""
@@ -905,11 +1023,13 @@ class _DBHeadTrainFn(torch.autograd.Function):
 
 # ---- BasicBlock training (csrc/resblock_train.hip).  geom = (n, h_in, w_in, cin, width, stride); learn = conv1.weight, bn1.weight, bn1.bias,
 # conv2.*, bn2.*, then the downsample's three; stats = the running means and variances in the same order
-def _block_struct(learn, stats=None):
+def _block_struct(learn, stats=None, bottleneck=False):
+    """vtd_basicblock_params over a BasicBlock's tensors, or with `bottleneck` vtd_bottleneck_params over a Bottleneck's (conv3 / bn3 third)."""
     import ctypes as C
     from . import _native
-    st = _native.BasicBlockParams()
-    for i, pre in enumerate(("conv1_w bn1_w bn1_b", "conv2_w bn2_w bn2_b", "ds_w ds_bn_w ds_bn_b")[:len(learn) // 3]):
+    st = _native.BottleneckParams() if bottleneck else _native.BasicBlockParams()
+    pairs = ("conv1_w bn1_w bn1_b", "conv2_w bn2_w bn2_b") + (("conv3_w bn3_w bn3_b",) if bottleneck else ()) + ("ds_w ds_bn_w ds_bn_b",)
+    for i, pre in enumerate(pairs[:len(learn) // 3]):
         for j, field in enumerate(pre.split()):
             setattr(st, field, C.c_void_p(learn[3 * i + j].data_ptr()))
         if stats is not None:
@@ -926,6 +1046,8 @@ _RESBLOCK_BN = "vtd_resblock_bn_train"   # layer4's two geometries with batch-st
 _BLOCK_BN = "vtd_block_bn_train"         # layer3's and layer4's four with batch-statistics BatchNorm, and the strided dx (the same file)
 _TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two and layer1's one as well, seven in all (the same file); the stem's batch-statistics
                                          # entries, vtd_stem_bn_train_*, are csrc/stem_train.hip's
+_BOTTLENECK = "vtd_bottleneck_train"     # ResNet-50's last stage: the two Bottleneck geometries of width 512 (csrc/bottleneck_train.hip); the
+                                         # block's output has 4 width channels and its struct a third convolution + BatchNorm pair
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
@@ -943,10 +1065,10 @@ def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None)
     entry = entry if bn is None or entry in _BN_FAMILIES else _RESBLOCK_BN
     C, _native, lib, ws = _native_workspace(entry + "_workspace_bytes", (*geom, 0), tap.device)
     n, hin, win, cin, width, stride = geom
-    y = torch.empty((n, hin // stride + 2, win // stride + 2, width), dtype=torch.float16, device=tap.device)
+    y = torch.empty((n, hin // stride + 2, win // stride + 2, 4 * width if entry == _BOTTLENECK else width), dtype=torch.float16, device=tap.device)
     mode = () if bn is None else (1 if bn[0] else 0, float(bn[1]))
     bstats = () if bn is None else (torch.full((3, 2, width), float("nan"), dtype=torch.float32, device=tap.device),)
-    st = _block_struct(learn, stats)
+    st = _block_struct(learn, stats, entry == _BOTTLENECK)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     _native.check(getattr(lib, entry + "_forward")(ptr(tap), *geom, C.byref(st), *mode, eps, ptr(ws), ptr(y), *map(ptr, bstats),
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry + "_forward")
@@ -962,7 +1084,7 @@ def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx
     grads = [torch.empty_like(p) for p in learn]
     C, _native, lib, scratch = _native_workspace(entry + "_workspace_bytes", (*geom, 1), tap.device)
     n, hin, win, cin, width, stride = geom
-    st, gst = _block_struct(learn, stats), _block_struct(grads)
+    st, gst = _block_struct(learn, stats, entry == _BOTTLENECK), _block_struct(grads, None, entry == _BOTTLENECK)
     dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
     dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
     mode = () if bn is None else (1 if bn[0] else 0,)
@@ -1126,8 +1248,9 @@ class _FPNTrainFn(torch.autograd.Function):
 # running statistics) with (training, momentum) as a fourth entry for the vtd_stem_bn_train_* entries, `blocks` a _BlockPlan for each
 # BasicBlock from the lowest up (none: the FPN and the head alone) with `beps` their eps,
 # `bn` None or (training, momentum) for blocks on the batch-statistics entries.  _BlockPlan: the block's geometry, its running statistics,
-# its entry family and the count of its learnable tensors (9 with a downsample, 6 without)
-_TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn")
+# its entry family and the count of its learnable tensors (9 with a downsample, 6 without; a Bottleneck's 12 and 9).  `per`: the blocks of
+# each stage of the plan, 2 for ResNet-18's BasicBlock stages and 3 for ResNet-50's res5, the one Bottleneck stage built
+_TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn per", defaults=(2,))
 _BlockPlan = namedtuple("_BlockPlan", "geom stats entry nlearn")
 
 
@@ -1136,11 +1259,12 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
     Inputs: the plan, then the learnable tensors: the stem's 3 if it runs, those of the blocks from the lowest up, the FPN's 10, the head's 20.
 
     Forward: the stem's launch on the image tap if there is one, then the blocks in order, each on the tap the one before wrote; the last
-    tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every second block.
+    tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every stage's last block (every
+    second block; with plan.per = 3, ResNet-50's res5 on the vtd_bottleneck_train_* entries, the third).
 
     Backward: head -> FPN -> the blocks from the top down, every gradient handed on as the kernels leave it (NHWC fp32 with its power-of-two
     scale), never through fp16 or an NCHW copy.  The FPN's backward forms dC(k) for the levels the node computes itself (the top
-    len(blocks) / 2); dC5 goes into the last block.  Every block but the lowest forms its input gradient (a stage's first block: the strided
+    len(blocks) / plan.per); dC5 goes into the last block.  Every block but the lowest forms its input gradient (a stage's first block: the strided
     dgrad); where a stage's input is an FPN level too, the first block's dx and the FPN's dC(k) of that level are added at one power-of-two
     scale (vtd_resblock_train_combine) before they go into the stage below.  The lowest block forms a dx only when the stem runs, and that dx
     is the stem's dpool.  The parameter gradients of a block do not depend on whether its dx is formed, so a node gives the bits of the node
@@ -1171,7 +1295,7 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
             x, ws = _block_forward_raw(x, b.geom, plan.beps, learn, b.stats, b.entry, plan.bn)[:2]
             acts.append(x)
             bws.append(ws)
-        ftaps = (*plan.taps, *acts[1::2])[-4:]      # C2 .. C5: the last four (an image or pooled tap in front falls out)
+        ftaps = (*plan.taps, *acts[plan.per - 1::plan.per])[-4:]      # C2 .. C5: the last four (an image or pooled tap in front falls out)
         p2p, fws = _fpn_forward_raw(ftaps, plan.geom, fpn_params)
         hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
         ctx.save_for_backward(p2p, prob, thresh, *stem_saved, *acts, *params)
@@ -1188,8 +1312,8 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
         stem_saved, acts, params = rest[:nstem], rest[nstem:nstem + nb], rest[nstem + nb:]
         slearn, blearn, fpn_params, head_params = _TrunkFPNHeadTrainFn._split(plan, params)
         hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, bool(plan.head[0]), ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        ftaps = (*plan.taps, *acts[1::2])[-4:]
-        stages = nb // 2
+        ftaps = (*plan.taps, *acts[plan.per - 1::plan.per])[-4:]
+        stages = nb // plan.per
         fout = _fpn_backward_raw(ftaps, plan.geom, fpn_params, ctx.fws, dp2, dscale, sum(8 >> j for j in range(stages)))      # dC5 down
         if not plan.blocks:
             return (None, *fout, *hgrads)
@@ -1199,8 +1323,8 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
         for i in reversed(range(nb)):
             b, want_dx = plan.blocks[i], i > 0 or plan.stem is not None
             bgrads[i], d, ds = _block_backward_raw(ins[i], b.geom, plan.beps, blearn[i], b.stats, ctx.bws[i], acts[i], d, ds, want_dx, b.entry, plan.bn)
-            level = 3 - stages + i // 2      # the FPN level of this block's stage's input: C(2 + level), none below C2
-            if want_dx and i % 2 == 0 and level >= 0:
+            level = 3 - stages + i // plan.per      # the FPN level of this block's stage's input: C(2 + level), none below C2
+            if want_dx and i % plan.per == 0 and level >= 0:
                 d, ds = _combine_scaled(d, ds, dtaps[level], scales[level])      # the stage's share of dC(k) + the FPN's
         sgrads = ()
         if plan.stem is not None:      # layer1.0's input gradient is the stem's dpool
@@ -1365,6 +1489,8 @@ class _EngineOwner:
 _STAGE_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+layer3+layer2", "head+fpn+layer4+layer3+layer2+layer1")
 # the whole detector: the four stages and the stem (ResNet-18 only); nothing is frozen and the train-mode forward needs no trunk engine
 _BACKBONE_MODE = "head+fpn+backbone"
+# ResNet-50's last stage, res5 (backbone.7: three Bottlenecks), with the FPN and the head; frozen-statistics BatchNorm (ResNet-50 only)
+_RES5_MODE = "head+fpn+res5"
 
 
 class DBNet(_EngineOwner, nn.Module):
@@ -1418,6 +1544,12 @@ class DBNet(_EngineOwner, nn.Module):
         every step; a following eval() forward rebuilds the inference engine on the new statistics.  The state dict is the same in
         either mode.
 
+        "head+fpn+res5" (ResNet-50 only; on resnet18 it raises ValueError that names "head+fpn+layer4"): fine-tune ResNet-50's last stage with the
+        FPN and the head -- backbone.0 .. backbone.6 stop requiring grad; backbone.7 (three Bottlenecks, 30 tensors), fpn and head train.  A
+        forward in train mode takes C2..C4 from the trunk engine (keyed on the frozen backbone tensors only; its own C5 is ignored), then runs
+        res5 (csrc/bottleneck_train.hip), the FPN and the head on the HIP training kernels as one autograd node.  res5's BatchNorms normalise
+        with their running statistics, which are never written: trunk_bn must be "frozen".
+
         None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
         FPN -- their parameters stop requiring grad, and a forward in train mode runs trunk + FPN on a separate features engine (built
         with fuse_fpn_head=0, rebuilt only when trunk / FPN weights change) and the head on the HIP training kernels, differentiable
@@ -1451,10 +1583,17 @@ class DBNet(_EngineOwner, nn.Module):
         if trainable in _STAGE_MODES or trainable == _BACKBONE_MODE:
             if self.backbone_name != "resnet18":
                 raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
-                                 "Bottleneck training is not built")
+                                 "Bottleneck training is not built under this name (resnet50's last stage trains with trainable='head+fpn+res5')")
+        elif trainable == _RES5_MODE:
+            if self.backbone_name != "resnet50":
+                raise ValueError(f"trainable={trainable!r} names ResNet-50's last stage (three Bottlenecks); on {self.backbone_name} the last stage "
+                                 "trains with trainable='head+fpn+layer4'")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
+        if trainable == _RES5_MODE and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
+            raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: res5 trains with frozen-statistics BatchNorm only (trunk_bn='frozen'); "
+                             "batch-statistics BatchNorm is not built for Bottleneck blocks")
         if isinstance(bn_mode, (tuple, list)):
             bn_mode = tuple(bn_mode)
             fits = next((mode for stages, mode in _TRUNK_BN_STAGES.items() if stages == bn_mode), None)      # no hashing: any tuple may come
@@ -1477,7 +1616,7 @@ class DBNet(_EngineOwner, nn.Module):
         elif trainable == "head+fpn":
             for p in self.backbone.parameters():
                 p.requires_grad_(False)
-        elif trainable in _STAGE_MODES:
+        elif trainable in _STAGE_MODES or trainable == _RES5_MODE:
             first = self._first_trained()
             for i in range(8):
                 for p in self.backbone[i].parameters():
@@ -1493,12 +1632,14 @@ class DBNet(_EngineOwner, nn.Module):
     def _first_trained(self):
         """The first backbone module a stage mode trains: the mode at position k - 1 of _STAGE_MODES trains the top k residual stages,
         backbone.(8 - k) .. backbone.7, over the frozen backbone.0 .. backbone.(7 - k)."""
-        return 8 - (_STAGE_MODES.index(self.trainable) + 1)
+        return 7 if self.trainable == _RES5_MODE else 8 - (_STAGE_MODES.index(self.trainable) + 1)
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable == _BACKBONE_MODE:
+        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable in (_BACKBONE_MODE, _RES5_MODE):
             tensors += list(self.fpn.parameters())
+        if self.trainable == _RES5_MODE:      # backbone.7's 30 parameters and 30 buffers
+            tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
         if self.trainable == _BACKBONE_MODE:      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
             for i in (7, 6, 5, 4, 0, 1):
                 tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
@@ -1513,7 +1654,7 @@ class DBNet(_EngineOwner, nn.Module):
         with self._engine_lock:
             # keyed on the backbone tensors' versions only (load_state_dict bumps them): FPN and head updates never rebuild it
             frozen = self.backbone.state_dict()
-            if self.trainable in _STAGE_MODES:
+            if self.trainable in _STAGE_MODES or self.trainable == _RES5_MODE:
                 # the frozen tensors only: what the engine computes from the trained stages (stale weights) is never read -- its C5 in the
                 # layer4 mode, C4 and C5 in the layer3 mode, all but C2 in the layer2 mode, all but the pooled stem output in the layer1 mode
                 trained = tuple(f"{i}." for i in range(self._first_trained(), 8))
@@ -1560,10 +1701,12 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE) + _STAGE_MODES:
+        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE, _RES5_MODE) + _STAGE_MODES:
             if self.training:
                 if self.trainable == _BACKBONE_MODE:
                     return self._forward_train_backbone(x)
+                if self.trainable == _RES5_MODE:
+                    return self._forward_train_res5(x)
                 if self.trainable in _STAGE_MODES:
                     return self._forward_train_trunk(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
@@ -1626,6 +1769,21 @@ class DBNet(_EngineOwner, nn.Module):
         if bn_mode == "trained":      # every stage the mode trains (set_trainable: layer1 at the lowest), on the node of that many stages
             bn_mode = tuple(stages)
         out = self.fpn.forward_padded(taps, head=self.head, trunk_batch_stats=bn_mode if isinstance(bn_mode, tuple) else bn_mode == "batch", **stages)
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+    def _forward_train_res5(self, x):
+        """The train-mode forward of "head+fpn+res5": C2 .. C4 from the frozen trunk engine (its own C5 comes from the res5 weights it was built
+        with and is ignored), then res5, the FPN and the head as one autograd node."""
+        frozen = [n for i in range(7) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res5 is not implemented; only "
+                               "res5 (backbone.7), the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. backbone.6)")
+        for m in (self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = self.trunk_engine().forward_trunk(x)[:3]   # new tensors per call: autograd may keep them
+        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
