@@ -31,6 +31,9 @@ struct HaloParams {
     int in_hp, in_wp, in_ring, out_hp, out_wp, out_ring, res_hp, res_wp, res_ring;
     int tiles_x, tiles_y, tiles_n, relu;
     unsigned long long* stamps;  // debug (VTD_HALO_STAMPS=1): 4 s_memtime stamps per workgroup
+    const half_t* in2 = nullptr;  // conv_halo_small_kernel only: second K segment, [n][in2_hp][in2_wp][in2_c] read at (2 oy, 2 ox) + in2_ring, 64 channels
+    int in2_hp = 0, in2_wp = 0, in2_c = 0, in2_ring = 0;
+    int K = 0;                   // conv_halo_small_kernel only: weight row length, 9*cin (+ 64 with a second segment)
     int dbg;                     // instrumented build only (-DVTD_CONV_EXPERIMENT, VTD_C64_DEBUG): 1 = every pixel block of a workgroup reads and
                                  // writes ONE block's addresses (operands out of L2, results wrong): the layer-1 kernel without its HBM traffic
 };
@@ -403,6 +406,208 @@ int halo64_launch(const HaloParams& p, hipStream_t stream) {
     }
     hipLaunchKernelGGL((conv_halo64_kernel<TW>), dim3(p.n * p.tiles_y * p.tiles_x * p.tiles_n), dim3(256), lds, stream, p);
     return -(int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Small-footprint variant: the tap reuse of the kernels above in a workgroup small enough that THREE share a CU and cover one
+// another's exposed halo fetches, prologues and epilogues, the way the 128 x 128 implicit-GEMM tiles do.  A tile is an 8 x 16
+// pixel block (128 GEMM rows; the 10 x 18 halo of head_entry_halo.hip: 180 rows = 23 one-KB pieces) by 64 output channels.
+// Per 64-channel input chunk the halo is staged once, then nine K-steps each stage only 64 weight rows (8 pieces): per tile
+// and chunk 23 + 72 KB for 4.7 MMAC, ~50 MAC per staged byte against the 32 of the 128 x 128 im2col tile.
+//   * LDS, one array: 24 KB halo + 3 x 8 KB weight ring = 48 KB;
+//   * four waves, 2 x 2, of 64 pixels x 32 channels each (two waves of 64 x 64 read a third fewer fragments per MFMA but leave
+//     each SIMD with too few waves to cover the LDS latency: 84 / 87 us against 63 / 67 us on layer 2);
+//   * ONE halo buffer: the next chunk's halo is issued behind a barrier after the chunk's last tap, and the weights of the
+//     step after next are issued BEHIND it, so the wait at the top of every step is the same counted one (the newest weight
+//     stage stays in flight; the halo, older, has landed) and vmcnt(0) is only ever asked for when nothing newer exists;
+//   * the 16-byte chunks of a halo row are XOR-swizzled by the row's halo COLUMN (as head_entry_halo256_kernel): a lane's four
+//     pixels share the column, so a tap's fragment reads are one of six precomputed addresses plus immediates;
+//   * the weight rows are permuted on their way into LDS (row g*32 + ii*16 + q*4 + e holds channel g*32 + q*8 + ii*4 + e), so
+//     a lane's two fragments of a pixel are 8 consecutive channels: bias, residual, ReLU and one 16-byte NHWC store per pixel
+//     straight from the accumulators, no staging tile and no barrier in the epilogue.
+//   * a second K segment (conv_igemm.hip DUAL: the 1x1 / stride-2 downsample of a BasicBlock folded into its conv2) is one more
+//     "chunk" after the regular ones: the block's 128 pixels of the second tensor at (2 oy, 2 ox), 16 gathered pieces in the
+//     halo buffer, and one K-step on the last 64 columns of the weight rows.
+// Accumulation is chunk-major (all nine taps of channels 0-63, then of 64-127, ...), as in the kernels above: results are
+// not bit-identical to conv_igemm.hip's tap-major order.
+constexpr int HS_HW = 18, HS_ROWS = 180, HS_PIECES = 23, HS_HALO_BYTES = 24 * 1024, HS_BSTAGE = 64 * 128;
+constexpr int HS_LDS = HS_HALO_BYTES + 3 * HS_BSTAGE;
+
+// counted wait for the LDS-DMA plus a full wait for this wave's own fragment reads: once the barrier behind it is passed, the
+// ring stage (or halo) those reads came from may be refilled by any wave
+template <int N>
+__device__ __forceinline__ void hs_wait_staged() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+
+__global__ __launch_bounds__(256, 3) void conv_halo_small_kernel(const HaloParams p) {
+    constexpr int NW = 4, FN = 2, BPW = 2, HPW = 6;
+    __shared__ __attribute__((aligned(16))) char smem[HS_LDS];
+    char* const hb = smem;
+    char* const bring = smem + HS_HALO_BYTES;
+
+    const int nblk = gridDim.x, b = blockIdx.x;
+    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = b & 7;
+    int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
+    const int tn = tile % p.tiles_n;
+    tile /= p.tiles_n;
+    const int tx = tile % p.tiles_x;
+    tile /= p.tiles_x;
+    const int ty = tile % p.tiles_y;
+    const int img = tile / p.tiles_y;
+    const int y0 = ty * 8, x0 = tx * 16, n0 = tn * 64;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lrow = lane >> 3, fr = lane & 15, fq = lane >> 4;
+    const int K = p.K, nchunks = p.cin >> 6;
+    const bool dual = p.in2 != nullptr;
+
+    // ---- halo loader: wave w takes pieces w, w + NW, ...; this lane's source element offset of each (chunk 0)
+    int hoff[HPW];
+#pragma unroll
+    for (int k = 0; k < HPW; ++k) {
+        int row = (w + k * NW) * 8 + lrow;
+        row = row < HS_ROWS ? row : HS_ROWS - 1;
+        const int hy = row / HS_HW, hx = row - hy * HS_HW;
+        int gy = y0 - 1 + hy + p.in_ring, gx = x0 - 1 + hx + p.in_ring;
+        gy = gy < p.in_hp ? gy : p.in_hp - 1;  // partial blocks: stay inside the allocation (those outputs are masked)
+        gx = gx < p.in_wp ? gx : p.in_wp - 1;
+        hoff[k] = ((img * p.in_hp + gy) * p.in_wp + gx) * p.cin + ((lane & 7) ^ (hx & 6)) * 8;
+    }
+    auto issue_halo = [&](int chunk) {
+#pragma unroll
+        for (int k = 0; k < HPW; ++k)
+            if (w + k * NW < HS_PIECES)
+                __builtin_amdgcn_global_load_lds((const VTD_AS1 void*)(p.in + hoff[k] + chunk * 64), (VTD_AS3 void*)(hb + (w + k * NW) * 1024), 16, 0, 0);
+    };
+    // second segment: LDS row r*16 + c = pixel (2(y0 + r), 2(x0 + c)) of in2, 16 pieces, chunks swizzled by the column c
+    auto issue_dual = [&]() {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int row = (w + k * NW) * 8 + lrow, r = row >> 4, c = row & 15;
+            const int off = ((img * p.in2_hp + 2 * (y0 + r) + p.in2_ring) * p.in2_wp + 2 * (x0 + c) + p.in2_ring) * p.in2_c + ((lane & 7) ^ (c & 6)) * 8;
+            __builtin_amdgcn_global_load_lds((const VTD_AS1 void*)(p.in2 + off), (VTD_AS3 void*)(hb + (w + k * NW) * 1024), 16, 0, 0);
+        }
+    };
+    // ---- weight loader: LDS row R = (i*NW + w)*8 + lrow takes output channel n0 + perm(R), 128 bytes per K-step
+    const half_t* bsrc[BPW];
+#pragma unroll
+    for (int i = 0; i < BPW; ++i) {
+        const int row = (i * NW + w) * 8 + lrow;
+        const int chan = (row & 32) + ((row >> 2) & 3) * 8 + ((row >> 4) & 1) * 4 + (row & 3);
+        bsrc[i] = p.wgt + (int64_t)(n0 + chan) * K + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
+    }
+    auto issue_b = [&](int koff, int stage) {
+#pragma unroll
+        for (int i = 0; i < BPW; ++i)
+            __builtin_amdgcn_global_load_lds((const VTD_AS1 void*)(bsrc[i] + koff), (VTD_AS3 void*)(bring + stage * HS_BSTAGE + (i * NW + w) * 1024), 16, 0, 0);
+    };
+
+    // ---- compute state: wave (wm, wn) owns tile rows wm*4 .. wm*4+3 (pixel column fr) x channels wn*32 ..
+    const int wm = w >> 1, wn = w & 1;
+    const char* a_addr[3][2];  // [tap column dx][half kk]: halo row (wm*4)*18 + fr + dx, chunk (fq + 4*kk) under the column swizzle
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) a_addr[dx][kk] = hb + (wm * 4 * HS_HW + fr + dx) * 128 + (((fq + 4 * kk) ^ ((fr + dx) & 6)) << 4);
+    const char* b_addr[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) b_addr[kk] = bring + (wn * FN * 16 + fr) * 128 + (((fq + 4 * kk) ^ ((fr >> 1) & 7)) << 4);
+    floatx4 acc[FN][4];
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+    issue_halo(0);
+    issue_b(0, 0);
+    issue_b(p.cin, 1);
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+        const bool more = chunk + 1 < nchunks;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            // Outstanding here, oldest first: weights of this step, [the halo, at tap 0], weights of the next step (none at the
+            // very last step).  The count leaves only those newest weights in flight.
+            if (tap < 8 || more || dual) hs_wait_staged<BPW>(); else hs_wait_staged<0>();
+            __builtin_amdgcn_s_barrier();  // landed for every wave; everyone left the previous step (its ring stage may be refilled)
+            const int tap2 = (tap + 2) % 9;
+            const int koff2 = (tap == 7 && !more) ? 9 * p.cin : tap2 * p.cin + (chunk + (tap + 2 >= 9 ? 1 : 0)) * 64;  // behind the last chunk: the second segment
+            if (tap < 7 || (tap == 7 && (more || dual))) issue_b(koff2, (tap + 2) % 3);
+            const int row_off = ((tap / 3) * HS_HW) * 128, stage_off = (tap % 3) * HS_BSTAGE;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                half8 af[4], bf[FN];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) af[j] = *(const half8*)(a_addr[tap % 3][kk] + row_off + j * (HS_HW * 128));
+#pragma unroll
+                for (int i = 0; i < FN; ++i) bf[i] = *(const half8*)(b_addr[kk] + stage_off + i * 2048);
+#pragma unroll
+                for (int i = 0; i < FN; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[i], af[j], acc[i][j], 0, 0, 0);
+            }
+            if (tap == 8 && more) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();  // every wave is done with this chunk's halo before the next one replaces it
+                issue_halo(chunk + 1);
+                issue_b(koff2, (tap + 2) % 3);  // behind the halo: see the wait above
+            } else if (tap == 8 && dual) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                issue_dual();
+            }
+        }
+    }
+    if (dual) {  // its weights (ring stage 9 % 3 = 0) were issued at the last chunk's tap 7, its pixels just now: nothing newer exists
+        hs_wait_staged<0>();
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            half8 af[4], bf[FN];
+            const char* a2 = hb + (wm * 64 + fr) * 128 + (((fq + 4 * kk) ^ (fr & 6)) << 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) af[j] = *(const half8*)(a2 + j * 2048);
+#pragma unroll
+            for (int i = 0; i < FN; ++i) bf[i] = *(const half8*)(b_addr[kk] + i * 2048);
+#pragma unroll
+            for (int i = 0; i < FN; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[i], af[j], acc[i][j], 0, 0, 0);
+        }
+    }
+
+    // ---- epilogue from the accumulators: lane (fr, fq) holds channels n0 + wn*32 + fq*8 .. +7 of pixels (wm*4 + j, fr)
+    const int ch = n0 + wn * 32 + fq * 8;
+    const floatx4 bias0 = *(const floatx4*)(p.bias + ch), bias1 = *(const floatx4*)(p.bias + ch + 4);
+    const int x = x0 + fr;
+    half8 rv[4];
+    if (p.res) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int y = y0 + wm * 4 + j;
+            y = y < p.h ? y : p.h - 1;
+            const int xc = x < p.w ? x : p.w - 1;
+            rv[j] = *(const half8*)(p.res + (((int64_t)img * p.res_hp + y + p.res_ring) * p.res_wp + xc + p.res_ring) * p.cout + ch);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = y0 + wm * 4 + j;
+        if (y >= p.h || x >= p.w) continue;
+        floatx4 v0 = acc[0][j] + bias0, v1 = acc[1][j] + bias1;
+        if (p.res) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v0[e] += (float)rv[j][e]; v1[e] += (float)rv[j][4 + e]; }
+        }
+        half8 hv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            hv[e] = (half_t)((p.relu && v0[e] < 0.f) ? 0.f : v0[e]);
+            hv[4 + e] = (half_t)((p.relu && v1[e] < 0.f) ? 0.f : v1[e]);
+        }
+        *(half8*)(p.out + (((int64_t)img * p.out_hp + y + p.out_ring) * p.out_wp + x + p.out_ring) * p.cout + ch) = hv;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -878,14 +1083,20 @@ int halo_launch(const HaloParams& p, hipStream_t stream) {
 
 }  // namespace
 
-// Shape test: can (and should) this convolution run on the halo kernel?  *tw_out = 16 or 32 picks the pixel-block shape.
-bool vtd_conv_halo_supported(const ConvParams& c, int* bn_out, int* tw_out) {
-    if (c.plist || c.in2 || c.pool_pw || c.stride != 1 || c.kw != 3 || c.K != 9 * c.in_c || (c.in_c & 63)) return false;  // 3x3, stride 1, whole chunks
+// What every kernel of this file asks of a convolution: plain 3x3 / stride 1 / pad 1 on whole 64-channel chunks, no pixel
+// list, second K segment or fused pool, and an epilogue of bias, optional unshifted residual and optional ReLU.
+static bool halo_common_rules(const ConvParams& c, bool second_segment = false) {
+    if (c.plist || (c.in2 && !second_segment) || c.pool_pw || c.stride != 1 || c.kw != 3 || c.K != 9 * c.in_c + (c.in2 ? 64 : 0) || (c.in_c & 63)) return false;  // 3x3, stride 1, whole chunks
     if (c.cin_steps * 64 != c.in_c || c.s_step != c.in_c || c.r_step != c.in_wp * c.in_c || c.k_hi_step != 32) return false;
     if ((c.cout & 63) || c.cout != c.cout_pad || c.out_c != c.cout) return false;
     if (c.flags & ~(EPI_RELU | EPI_RESIDUAL)) return false;
     if ((c.flags & EPI_RESIDUAL) && (c.res_shift || !c.res)) return false;
-    if (c.in_y0 < 0 || c.in_x0 != c.in_y0 || c.ho <= 0 || c.wo <= 0 || c.M % (c.ho * c.wo)) return false;
+    return !(c.in_y0 < 0 || c.in_x0 != c.in_y0 || c.ho <= 0 || c.wo <= 0 || c.M % (c.ho * c.wo));
+}
+
+// Shape test: can (and should) this convolution run on the halo kernel?  *tw_out = 16 or 32 picks the pixel-block shape.
+bool vtd_conv_halo_supported(const ConvParams& c, int* bn_out, int* tw_out) {
+    if (!halo_common_rules(c)) return false;
     // pixel-block shape: 16x16, or 8x32 for short wide maps; at least 85 % of the block grid must be real pixels
     const int h = c.ho, w = c.wo;
     auto eff = [&](int th, int tw) { return (double)h * w / ((double)((h + th - 1) / th * th) * ((w + tw - 1) / tw * tw)); };
@@ -932,4 +1143,42 @@ int vtd_launch_conv_halo(const ConvParams& c, int bn, int tw, hipStream_t stream
     if (bn == 128 && tw == 16) return halo_launch<128, 16>(p, stream);
     if (bn == 128 && tw == 32) return halo_launch<128, 32>(p, stream);
     return -2201;
+}
+
+// The small-footprint variant (conv_halo_small_kernel): the same rules, on maps of whole 8 x 16 pixel blocks.
+bool vtd_conv_halo_small_supported(const ConvParams& c) {
+    if (!halo_common_rules(c, true) || c.ho % 8 || c.wo % 16) return false;
+    // a second K segment: one 64-channel step of a 1x1 window at (2 oy, 2 ox), every pixel of it inside its allocation
+    if (c.in2 && (c.in2_mul != 2 || c.in2_shr != 0 || c.cin_steps2 != 1 || c.kw2 != 1 || c.seg1_steps * 64 != 9 * c.in_c || c.in2_c < 64 || (c.in2_c & 7) ||
+                  c.in2_ring < 0 || 2 * (c.ho - 1) + c.in2_ring >= c.in2_hp || 2 * (c.wo - 1) + c.in2_ring >= c.in2_wp))
+        return false;
+    return c.in_hp >= c.ho + c.in_y0 + 2 && c.in_wp >= c.wo + c.in_y0 + 2;  // the halo's last row and column exist (a zero ring on every side)
+}
+
+int vtd_launch_conv_halo_small(const ConvParams& c, hipStream_t stream) {
+    if (c.ho <= 0 || c.wo <= 0) return -2201;
+    HaloParams p;
+    p.in = c.in; p.wgt = c.wgt; p.bias = c.bias; p.res = (c.flags & EPI_RESIDUAL) ? c.res : nullptr; p.out = (half_t*)c.out;
+    p.h = c.ho; p.w = c.wo; p.n = c.M / (c.ho * c.wo); p.cin = c.in_c; p.cout = c.cout;
+    p.in_hp = c.in_hp; p.in_wp = c.in_wp; p.in_ring = c.in_y0 + 1;  // in_y0 = ring - pad
+    p.out_hp = c.out_hp; p.out_wp = c.out_wp; p.out_ring = c.out_ring;
+    p.res_hp = c.res_hp; p.res_wp = c.res_wp; p.res_ring = c.res_ring;
+    p.relu = (c.flags & EPI_RELU) ? 1 : 0;
+    p.stamps = nullptr;
+    p.dbg = 0;
+    p.K = c.K;
+    if (c.in2) { p.in2 = c.in2; p.in2_hp = c.in2_hp; p.in2_wp = c.in2_wp; p.in2_c = c.in2_c; p.in2_ring = c.in2_ring; }
+    if (c.in_y0 != c.in_x0 || c.in_y0 < 0 || c.K != 9 * c.in_c + (c.in2 ? 64 : 0) || c.out_c != c.cout || p.n <= 0 || (c.in_c & 63) || (c.cout & 63) ||
+        c.stride != 1 || c.M != p.n * c.ho * c.wo || (c.ho & 7) || (c.wo & 15) || ((c.flags & EPI_RESIDUAL) && !c.res) || c.plist)
+        return -2201;  // shapes are validated here: a mismatch must never reach a kernel
+    if (c.in2 && (c.in2_mul != 2 || c.in2_shr != 0 || c.in2_c < 64 || (c.in2_c & 7) || c.in2_ring < 0 || 2 * (c.ho - 1) + c.in2_ring >= c.in2_hp ||
+                  2 * (c.wo - 1) + c.in2_ring >= c.in2_wp || (int64_t)p.n * c.in2_hp * c.in2_wp * c.in2_c >= (1ll << 31)))
+        return -2201;
+    if (c.in_hp < c.ho + p.in_ring + 1 || c.in_wp < c.wo + p.in_ring + 1 || c.out_ring < 0 || c.out_hp < c.ho + c.out_ring || c.out_wp < c.wo + c.out_ring ||
+        (p.res && (c.res_ring < 0 || c.res_hp < c.ho + c.res_ring || c.res_wp < c.wo + c.res_ring)))
+        return -2201;  // the halo's last row and column, every output and every residual pixel lie inside their allocations
+    if ((int64_t)p.n * c.in_hp * c.in_wp * c.in_c >= (1ll << 31)) return -2202;  // 32-bit element offsets in the loader
+    p.tiles_x = p.w / 16; p.tiles_y = p.h / 8; p.tiles_n = p.cout / 64;
+    hipLaunchKernelGGL(conv_halo_small_kernel, dim3(p.n * p.tiles_y * p.tiles_x * p.tiles_n), dim3(256), 0, stream, p);
+    return -(int)hipGetLastError();
 }

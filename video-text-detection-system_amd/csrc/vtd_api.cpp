@@ -38,6 +38,8 @@ int vtd_launch_head_entry_pair(const ConvParams& c, const int* half_steps_dev, c
 bool vtd_conv_halo_supported(const ConvParams& c, int* bn_out, int* tw_out);
 bool vtd_conv_halo_c64_supported(const ConvParams& c, int tw);
 int vtd_launch_conv_halo(const ConvParams& c, int bn, int tw, hipStream_t stream);
+bool vtd_conv_halo_small_supported(const ConvParams& c);
+int vtd_launch_conv_halo_small(const ConvParams& c, hipStream_t stream);
 bool vtd_pointwise128_supported(const ConvParams& c);
 int vtd_launch_pointwise128(const ConvParams& c, hipStream_t stream);
 void vtd_head_tail_pack_w1(const half_t* w1_gemm, half_t* packed);
@@ -266,6 +268,7 @@ static void fill_conv_params(const ConvOp& c, int n, ConvParams& p) {
 static const int kHaloCfg = 100;
 static const int kHaloC64Cfg = 101;  // persistent resident-weight variant for 64 -> 64 channels
 static const int kHalo64Cfg = 104;  // second-generation halo kernel: 64 output channels per workgroup, hand-pipelined
+static const int kHaloSmallCfg = 108;  // small-footprint halo kernel: 8x16 pixel blocks x 64 output channels, three workgroups per CU
 static const int kHeadEntryHalo256Cfg = 103;  // same, 16x16 pixel blocks with 64x64 register tiles (hand-pipelined)
 static const int kHeadEntryPairCfg = 105;  // two 16x16 blocks per workgroup on one weight ring, 32-channel halos prefetched two groups ahead
 static const int kPointwiseCfg = 106;  // streaming 1x1 convolution 128 -> 256 with the top-down add (pointwise.hip): the C3 lateral
@@ -341,6 +344,7 @@ static int launch_conv_op(const ConvOp& c, int n, hipStream_t s, int cfg = -1, f
         if (!vtd_conv_halo_supported(p, &bn, &tw)) return ERR_GEOMETRY;
         return vtd_launch_conv_halo(p, cfg == kHaloC64Cfg ? 1 : cfg == kHalo64Cfg ? 2 : bn, tw, s);
     }
+    if (cfg == kHaloSmallCfg) return vtd_conv_halo_small_supported(p) ? vtd_launch_conv_halo_small(p, s) : ERR_GEOMETRY;
     if (cfg == kPointwiseCfg) return vtd_launch_pointwise128(p, s);
     if (!c.plist && (cfg == 0 || cfg == 12 || cfg == 13 || cfg == 14 || cfg == 15)) cfg = pick_tile_height(p, cfg);
     return vtd_launch_conv(p, cfg, s);
@@ -429,10 +433,10 @@ static int autotune_conv(const ConvOp& c, int n, hipStream_t s, int* best_cfg) {
         }
     }
     int hbn = 0, htw = 0;
+    const char* force = std::getenv("VTD_FORCE_HALO");  // tests: 1 = take the halo kernel wherever it applies,
+    bool pinned = false;  // the variant VTD_FORCE_HALO=2 / 3 names was taken: no later variant may win on time
     if (!rc && halo_enabled() && vtd_conv_halo_supported(p, &hbn, &htw)) {
-        const char* force = std::getenv("VTD_FORCE_HALO");  // tests: 1 = take the halo kernel wherever it applies,
         if (force && (force[0] == '1' || force[0] == '2' || force[0] == '3')) best = 1e30f;  // 2 = and its persistent 64->64 variant, 3 = the hand-pipelined 64-channel kernel
-        bool pinned = false;  // the variant VTD_FORCE_HALO=2 / 3 names was taken: no later variant may win on time
         for (int variant = 0; variant < 3 && !rc; ++variant) {
             if (variant == 1 && !vtd_conv_halo_c64_supported(p, htw)) continue;
             const int bn = variant == 1 ? 1 : variant == 2 ? 2 : hbn;
@@ -446,6 +450,18 @@ static int autotune_conv(const ConvOp& c, int n, hipStream_t s, int* best_cfg) {
             const int vid = variant == 1 ? kHaloC64Cfg : variant == 2 ? kHalo64Cfg : kHaloCfg;
             const bool pin = (variant == 1 && force && force[0] == '2') || (variant == 2 && force && force[0] == '3');
             if (!rc && !pinned && (ms < best || pin)) { best = ms; best_id = vid; pinned = pin; }
+        }
+    }
+    if (!rc && halo_enabled() && vtd_conv_halo_small_supported(p)) {  // 4 = the small-footprint kernel wherever it applies
+        if (!(rc = vtd_launch_conv_halo_small(p, s))) {
+            (void)hipEventRecord(e0, s);
+            for (int rep = 0; rep < 3 && !rc; ++rep) rc = vtd_launch_conv_halo_small(p, s);
+            (void)hipEventRecord(e1, s);
+            if (hipEventSynchronize(e1) != hipSuccess) rc = ERR_ARG;
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            const bool pin = force && force[0] == '4';
+            if (!rc && (pin || (!pinned && ms < best))) { best = ms; best_id = kHaloSmallCfg; }
         }
     }
     (void)hipEventDestroy(e0);
@@ -555,6 +571,7 @@ static bool config_valid_for(const ConvOp& c, int n, int cfg) {
         if (!vtd_conv_halo_supported(p, &bn, &tw)) return false;
         return cfg != kHaloC64Cfg || vtd_conv_halo_c64_supported(p, tw);
     }
+    if (cfg == kHaloSmallCfg) return vtd_conv_halo_small_supported(p);
     if (cfg == kPointwiseCfg) return vtd_pointwise128_supported(p);
     return cfg >= 0 && cfg < vtd_conv_num_configs() && vtd_conv_config_valid(p, cfg);
 }
@@ -2010,6 +2027,8 @@ int vtd_detector_get_profile(vtd_detector* d, int op_index, char* name, int name
                           "next slot)", c.ho * c.wo, c.cout, c.K);
         else if (cfg == kPointwiseCfg)
             std::snprintf(name, name_cap, "pointwise128 1x1%s streaming M/img=%d N=%d K=%d", c.has_res ? "+top-down add" : "", c.ho * c.wo, c.cout, c.K);
+        else if (cfg == kHaloSmallCfg)
+            std::snprintf(name, name_cap, "conv_halo_small 3x3 M/img=%d N=%d K=%d", c.ho * c.wo, c.cout, c.K);
         else if (cfg == kHaloCfg || cfg == kHaloC64Cfg || cfg == kHalo64Cfg)
             std::snprintf(name, name_cap, "conv_halo%s 3x3 M/img=%d N=%d K=%d", cfg == kHaloC64Cfg ? "_c64_persistent" : cfg == kHalo64Cfg ? "64" : "",
                           c.ho * c.wo, c.cout, c.K);
