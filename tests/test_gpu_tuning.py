@@ -89,6 +89,55 @@ def test_table_entries_steer_the_launch_and_invalid_ones_are_ignored(hip, monkey
         eng.close()
 
 
+def test_profile_labels_and_border_slot_follow_the_candidate_table(hip):
+    """One ResNet-18 forward on the shipped table: every launch slot the table gives to a kernel candidate (id >= 100) is
+    labelled with the name the candidate table (csrc/conv_select.cpp) holds for that id, and the BORDER slot runs if and only if
+    the head-entry slot before it took a row that leaves the border classes to it.  A label carries M/img, N and K of its slot,
+    a table key ho x wo, cout and K: slots are matched to entries on these three."""
+    import ctypes
+    import re
+    from test_conv_candidates import candidate_rows
+    from vtd_amd import _native
+    from vtd_amd.engine import DetectorEngine, detector_profile
+    rows = candidate_rows(ctypes.CDLL(_native.LIB_PATH))
+    name_of = {r[0]: r[3] for r in rows}
+    id_of = {r[3]: r[0] for r in rows}
+    border_ids = {r[0] for r in rows if r[1]}
+    eng = DetectorEngine("resnet18", mynets.seeded_state_dict(lambda: mynets.DBNet("resnet18"), seed=5), max_batch=1)
+    try:
+        assert eng.lib.vtd_detector_set_profiling(eng.handle, 1) == 0
+        eng.forward(torch.randn(1, 3, 640, 640, generator=torch.Generator().manual_seed(0)))
+        table_ids = {}   # (M/img, N, K) -> ids of the table's entries for bucket 1
+        for key, cfg in eng.tuning().items():
+            m = re.fullmatch(r"conv\|in\d+x\d+x\d+\|out(\d+)x(\d+)\|co(\d+)\|K(\d+)\|.*\|n1", key)
+            if m:
+                ho, wo, co, K = map(int, m.groups())
+                table_ids.setdefault((ho * wo, co, K), set()).add(cfg)
+        profile = detector_profile(eng)
+        seen, expected, head_entry_id, border_calls = set(), set(), None, None
+        for i, (label, _, calls, _) in enumerate(profile):
+            if "border classes of the composed head entry" in label:
+                border_calls = calls
+                prev = profile[i - 1][0].split(" ")[0]
+                assert "composed" in profile[i - 1][0]
+                head_entry_id = id_of.get(prev)   # None: an implicit-GEMM tile did every class
+                continue
+            m = re.search(r" M/img=(\d+) N=(\d+) K=(\d+)", label)
+            if not m or calls == 0:
+                continue
+            shape = tuple(map(int, m.groups()))
+            expected |= {(shape, name_of.get(cfg, cfg)) for cfg in table_ids.get(shape, ()) if cfg >= 100}
+            stem = label.split(" ")[0]
+            if stem in id_of:
+                seen.add((shape, stem))
+        # a slot carries a candidate's name exactly where the table gives that shape to that candidate, and the graph has such slots
+        assert seen and seen == expected, (seen, expected)
+        assert border_calls is not None
+        assert (border_calls > 0) == (head_entry_id in border_ids), (border_calls, head_entry_id)
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("backbone,batches,reps", [("resnet18", (32, 5, 16, 1), 16), ("resnet50", (8,), 12)])
 def test_asynchronous_kernels_are_bitwise_repeatable_under_load(hip, backbone, batches, reps):
     """Every hot kernel keeps loads in flight across barriers behind counted `s_waitcnt vmcnt(N)` (LDS-DMA rings in stem_pool,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # CRNN recogniser alone (272 crops and CROPS2): per-launch table with every conv on one forced tile configuration (VTD_FORCE_CONV_CFG),
-# to calibrate the row-count-aware tile choice (vtd_api.cpp: pick_tile_height)
+# to calibrate the row-count-aware tile choice (conv_select.cpp: pick_tile_height)
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/rec_cfgs
 mkdir -p $out

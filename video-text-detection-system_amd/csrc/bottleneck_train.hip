@@ -33,7 +33,7 @@
 // No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
 #include "resblock_common.h"
 
-int vtd_launch_conv(const ConvParams& p, int cfg, hipStream_t stream);
+#include "conv_kernels.h"
 
 namespace {
 

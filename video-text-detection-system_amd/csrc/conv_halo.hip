@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "vtd_common.h"
+#include "conv_kernels.h"
 
 namespace {
 

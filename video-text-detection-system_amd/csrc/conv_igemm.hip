@@ -22,6 +22,7 @@
 //                  contiguous run of tiles (neighbouring tiles share halo rows and the weight panel in that L2)
 #include <cstdlib>
 #include "vtd_common.h"
+#include "conv_kernels.h"
 
 namespace {
 
@@ -705,7 +706,7 @@ int launch_plain(const ConvParams& p, hipStream_t stream) {
 }  // namespace
 
 // ---- tile configurations.  Which one wins depends on the layer (M, N, K, how memory-bound it is), so the network
-// graphs time the valid candidates once per batch size (vtd_api.cpp: autotune) instead of guessing.
+// graphs time the valid candidates once per batch size (conv_select.cpp: autotune_conv) instead of guessing.
 //   id  tile      waves stages  LDS      blocks/CU
 //   0   256x128   8     3       144 KB   1      K-heavy, N >= 128: least L2->LDS traffic per FLOP
 //   1   128x128   4     2        68 KB   2
@@ -728,7 +729,11 @@ int launch_plain(const ConvParams& p, hipStream_t stream) {
 //   15  256x256   8 (2x4) 2     128 KB   1      64 LDS-DMA pieces per K-step for twice the MFMAs of the 256 x 128 tile (32 per 256 x 128
 //                                               equivalent instead of 48): for launches with enough 256 x 256 tiles.  Register epilogue only
 //   16  128x64    4     6       144 KB   1      six LDS stages: five K-steps of loads in flight, for launches of a few workgroups with a long K
-int vtd_conv_num_configs() { return 17; }
+// the same list as the profile prints it (vtd_detector_get_profile): "<rows>,<columns>,s<stages>[,...]" by id
+static const char* const kConfigNames[] = {"256,128,s3", "128,128,s2", "128,128,s3", "256,64,s2", "256,64,s3", "128,64,s2", "128,64,s3",
+                                           "64,256,s2", "128,64,s2,classed", "128,64,s3,classed", "256,64,s2,classed", "256,64,s3,classed", "208,128,s3", "272,128,s3", "256,128,s3,16w", "256,256,s2", "128,64,s6"};
+int vtd_conv_num_configs() { return (int)(sizeof kConfigNames / sizeof *kConfigNames); }
+const char* vtd_conv_config_name(int cfg) { return cfg >= 0 && cfg < vtd_conv_num_configs() ? kConfigNames[cfg] : "default"; }
 
 // plain NHWC fp16 output with bias / residual / ReLU only: what the register epilogue (and so configurations 12 / 13) can finish
 static bool epi_direct_eligible(const ConvParams& p) {

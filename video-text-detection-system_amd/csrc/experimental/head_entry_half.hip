@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <vector>
 #include "vtd_common.h"
+#include "conv_kernels.h"
 
 namespace {
 

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "vtd_common.h"
+#include "conv_kernels.h"
 
 namespace {
 

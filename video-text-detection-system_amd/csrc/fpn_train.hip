@@ -26,7 +26,7 @@
 
 #include <cstring>
 
-int vtd_launch_conv(const ConvParams& p, int cfg, hipStream_t stream);
+#include "conv_kernels.h"
 
 namespace {
 

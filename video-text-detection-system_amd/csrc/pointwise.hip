@@ -15,6 +15,7 @@
 // Arithmetic order is that of conv_igemm.hip (K ascending in steps of 32 into a zero accumulator; then + bias; then + residual; one
 // fp16 rounding), so the two kernels give bit-identical maps and kernel choice cannot change results.
 #include "vtd_common.h"
+#include "conv_kernels.h"
 
 namespace {
 

@@ -50,7 +50,7 @@
 // Nothing divides by gamma or sigma.  No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
 #include "resblock_common.h"
 
-int vtd_launch_conv(const ConvParams& p, int cfg, hipStream_t stream);
+#include "conv_kernels.h"
 int64_t vtd_basicblock_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
 int vtd_launch_basicblock_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_basicblock_params* P, float eps,
                                   void* ws, void* y, hipStream_t s);

@@ -1,5 +1,5 @@
 // Transformer recogniser (TrOCR) handle: checkpoint ingest, graph, workspace and the vtd_trocr_* entry points of include/vtd.h.
-// Textually included at the end of vtd_api.cpp (it shares that file's ModelBase / build_linear / kernel-selection helpers).
+// Textually included at the end of vtd_api.cpp (it shares that file's ModelBase / build_linear and its conv_select.h kernel selection).
 // Reference: app/ml/models/text_recognizer.py:39-69 -> transformers 4.36 ViTModel + TrOCRForCausalLM + greedy generate
 // (algorithm restated in oracle/trocr.py; kernels in trocr.hip).
 

@@ -13,11 +13,9 @@
 
 #include "../../include/vtd.h"
 #include "vtd_common.h"
+#include "conv_select.h"  // ConvOp, kernel choice per launch slot; with conv_kernels.h, the convolution launchers it chooses among
 
-// kernel launchers (defined in the .hip files)
-int vtd_launch_conv(const ConvParams& p, int cfg, hipStream_t stream);
-int vtd_conv_num_configs();
-bool vtd_conv_config_valid(const ConvParams& p, int cfg);
+// the other kernel launchers (defined in the .hip files)
 int vtd_launch_preprocess(const uint8_t* frames, int n, int H, int W, half_t* out, const int* xb, const int* xk, int ksx,
                           const int* yb, const int* yk, int ksy, int max_rows, hipStream_t stream);
 int vtd_launch_nchw_to_input(const float* x, half_t* out, int n, hipStream_t stream);
@@ -25,23 +23,6 @@ int vtd_launch_maxpool(const TensorDesc& in, const TensorDesc& out, int n, int k
                        hipStream_t stream);
 void vtd_stem_pool_pack_weights(const float* w_folded, half_t* packed);
 int vtd_launch_stem_pool(const TensorDesc& in, const TensorDesc& out, const half_t* w_packed, const float* bias, int n, hipStream_t stream);
-extern "C" int vtd_head_entry_halo_steps(int py, int px, int nch1, int* out);
-int vtd_launch_head_entry_halo(const ConvParams& c, const int* steps_dev, int nsteps, int big_tiles, hipStream_t stream);
-#ifdef VTD_EXPERIMENTAL_CANDIDATES
-// csrc/experimental/: measured, parity-green, LOSING candidates of the composed head entry.  They are not part of the
-// product library: only an instrumented build (VTD_LIB_VARIANT=<tag> VTD_EXTRA_HIPCC_FLAGS=-DVTD_EXPERIMENTAL_CANDIDATES) carries them.
-extern "C" int vtd_head_entry_half_schedule(const int* steps, int nsteps, int* out);
-int vtd_launch_head_entry_half(const ConvParams& c, const int* sched_dev, int nsteps, hipStream_t stream);
-int vtd_head_entry_pair_tables(int py, int px, int c2ch, int* half_steps, int* plan);
-int vtd_launch_head_entry_pair(const ConvParams& c, const int* half_steps_dev, const int* plan_dev, int nh, hipStream_t stream);
-#endif
-bool vtd_conv_halo_supported(const ConvParams& c, int* bn_out, int* tw_out);
-bool vtd_conv_halo_c64_supported(const ConvParams& c, int tw);
-int vtd_launch_conv_halo(const ConvParams& c, int bn, int tw, hipStream_t stream);
-bool vtd_conv_halo_small_supported(const ConvParams& c);
-int vtd_launch_conv_halo_small(const ConvParams& c, hipStream_t stream);
-bool vtd_pointwise128_supported(const ConvParams& c);
-int vtd_launch_pointwise128(const ConvParams& c, hipStream_t stream);
 void vtd_head_tail_pack_w1(const half_t* w1_gemm, half_t* packed);
 void vtd_head_tail_pack_w2(const float* w2, half_t* packed);
 int vtd_launch_head_tail(const TensorDesc& in, const half_t* w1, const float* bias1, const half_t* w2, float b2, float* out, int n,
@@ -136,17 +117,6 @@ int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd
 
 namespace vtd {
 
-enum : int {
-    ERR_ARG = -1100,
-    ERR_UNKNOWN_KEY = -1101,
-    ERR_SHAPE = -1102,
-    ERR_MISSING_KEY = -1103,
-    ERR_NOT_FINALIZED = -1104,
-    ERR_BATCH = -1105,
-    ERR_GEOMETRY = -1106,
-    ERR_CAPACITY = -1107,
-};
-
 using StateDict = std::map<std::string, std::vector<float>>;
 
 struct DeviceArena {
@@ -180,46 +150,6 @@ static TensorDesc make_desc(int n, int h, int w, int c, int ring, int ring_br) {
     return t;
 }
 
-struct ConvOp {
-    TensorDesc in, out, res;
-    bool has_res = false;
-    half_t* w = nullptr;
-    half_t* w_panel = nullptr;   // the same weights K-panel-major, [K / 32][cout_pad][32] (dense_gemm.hip; dense layers of the Transformer encoder only)
-    float* bias = nullptr;
-    int k_hi_step = 32, cin_steps = 1, kw = 1, s_step = 0, r_step = 0;  // scalar K walk (ConvParams)
-    int K = 0, cout = 0, cout_pad = 0, stride = 1, in_y0 = 0, in_x0 = 0, flags = 0, ps_cout = 0, res_shift = 0;
-    int ho = 0, wo = 0;           // GEMM row decomposition (input-pixel grid for transposed conv)
-    int64_t macs_per_image = 0;
-    void* out_f32 = nullptr;      // EPI_OUT_F32 destination
-    int ldc = 0;
-    int seg_cols = 0;             // EPI_OUT_F16 in column segments (ConvParams::seg_cols)
-    void* seg_out[3] = {nullptr, nullptr, nullptr};
-    int seg_ldc[3] = {0, 0, 0};
-    const float* head_w = nullptr;  // EPI_HEAD_FINAL
-    float head_b = 0.f;
-    // classed dual-source mode (fused FPN top + head entry)
-    const uint32_t* plist = nullptr;
-    const int* tile_combo = nullptr;
-    const uint32_t* plist_b = nullptr;  // 256-row cut of the pixel lists
-    const int* tile_combo_border = nullptr;  // the 12 border classes only (interior classes run on head_entry_halo.hip)
-    int tiles_border = 0;
-    const int* he_steps = nullptr;  // step tables of the four interior classes
-    int he_nsteps = 0;
-    const int* hh_sched = nullptr;  // head_entry_half.hip: half-step schedules of the four interior classes
-    const int* hp_half_steps = nullptr;  // head_entry_pair.hip: half-step tables and halo prefetch plans of the four interior classes
-    const int* hp_plan = nullptr;
-    int hp_nh = 0;
-    const int* tile_combo_b = nullptr;
-    int tiles_per_img_b = 0;
-    int tiles_per_img = 0, seg1_steps = 0, cin_steps2 = 0, kw2 = 0, s_step2 = 0, r_step2 = 0, img_h = 0, img_w = 0;
-    TensorDesc in2;
-    const float* bias_tab = nullptr;
-    // second K segment of a plain conv (conv_igemm.hip DUAL): a 1x1 window of `in2` at (oy * in2_mul >> in2_shr, ox * in2_mul >> in2_shr)
-    bool dual = false;
-    int in2_mul = 1, in2_shr = 0;
-    int pool_pw = 0;   // 2 x pool_pw max-pool behind the ReLU fused into the epilogue (`out` = the pooled tensor); 0 = none
-};
-
 struct Op {
     enum Kind { CONV, POOL, FINAL, STEMPOOL, HEADTAIL, BORDER } kind;  // BORDER: border-class tiles of the composed head entry in the slot before it, run iff that slot took the halo-plane kernel
     ConvOp conv;
@@ -233,250 +163,6 @@ struct Op {
     const half_t* htw1 = nullptr;  // HEADTAIL: fragment-ordered ConvT1 / ConvT2 weights
     const half_t* htw2 = nullptr;
 };
-
-static void fill_conv_params(const ConvOp& c, int n, ConvParams& p) {
-    std::memset(&p, 0, sizeof(p));
-    p.in = c.in.ptr; p.wgt = c.w; p.k_hi_step = c.k_hi_step; p.cin_steps = c.cin_steps; p.kw = c.kw; p.s_step = c.s_step; p.r_step = c.r_step; p.bias = c.bias;
-    p.res = c.has_res ? c.res.ptr : nullptr;
-    p.out = (c.flags & (EPI_OUT_F32 | EPI_OUT_F16)) ? c.out_f32 : (void*)c.out.ptr;
-    p.M = n * c.ho * c.wo; p.K = c.K; p.cout = c.cout; p.cout_pad = c.cout_pad;
-    p.ho = c.ho; p.wo = c.wo;
-    p.in_hp = c.in.hp; p.in_wp = c.in.wp; p.in_c = c.in.c; p.in_y0 = c.in_y0; p.in_x0 = c.in_x0; p.stride = c.stride;
-    p.out_hp = c.out.hp; p.out_wp = c.out.wp; p.out_c = c.out.c; p.out_ring = c.out.ring;
-    p.res_hp = c.res.hp; p.res_wp = c.res.wp; p.res_ring = c.res.ring; p.res_shift = c.res_shift;
-    p.ps_cout = c.ps_cout; p.flags = c.flags; p.ldc = c.ldc;
-    p.seg_cols = c.seg_cols;
-    for (int i = 0; i < 3; ++i) { p.seg_out[i] = c.seg_out[i]; p.seg_ldc[i] = c.seg_ldc[i]; }
-    p.head_w = c.head_w; p.head_b = c.head_b; p.prob_out = (float*)c.out_f32;
-    if (c.plist) {
-        p.plist = c.plist; p.tile_combo = c.tile_combo; p.tiles_per_img = c.tiles_per_img;
-        p.plist_b = c.plist_b; p.tile_combo_b = c.tile_combo_b; p.tiles_per_img_b = c.tiles_per_img_b;
-        p.in2 = c.in2.ptr; p.in2_hp = c.in2.hp; p.in2_wp = c.in2.wp; p.in2_c = c.in2.c; p.in2_ring = c.in2.ring;
-        p.seg1_steps = c.seg1_steps; p.cin_steps2 = c.cin_steps2; p.kw2 = c.kw2; p.s_step2 = c.s_step2; p.r_step2 = c.r_step2;
-        p.bias_tab = c.bias_tab; p.img_h = c.img_h; p.img_w = c.img_w;
-        p.M = n * c.tiles_per_img * 128;
-    }
-    p.pool_pw = c.pool_pw;
-    if (c.dual) {
-        p.in2 = c.in2.ptr; p.in2_hp = c.in2.hp; p.in2_wp = c.in2.wp; p.in2_c = c.in2.c; p.in2_ring = c.in2.ring;
-        p.in2_mul = c.in2_mul; p.in2_shr = c.in2_shr;
-        p.seg1_steps = c.seg1_steps; p.cin_steps2 = c.cin_steps2; p.kw2 = 1; p.s_step2 = 0; p.r_step2 = 0;
-    }
-}
-
-// Tile "configuration" kHaloCfg selects the halo-tile kernel (conv_halo.hip) instead of an implicit-GEMM tile shape.
-static const int kHaloCfg = 100;
-static const int kHaloC64Cfg = 101;  // persistent resident-weight variant for 64 -> 64 channels
-static const int kHalo64Cfg = 104;  // second-generation halo kernel: 64 output channels per workgroup, hand-pipelined
-static const int kHaloSmallCfg = 108;  // small-footprint halo kernel: 8x16 pixel blocks x 64 output channels, three workgroups per CU
-static const int kHeadEntryHalo256Cfg = 103;  // same, 16x16 pixel blocks with 64x64 register tiles (hand-pipelined)
-static const int kHeadEntryPairCfg = 105;  // two 16x16 blocks per workgroup on one weight ring, 32-channel halos prefetched two groups ahead
-static const int kPointwiseCfg = 106;  // streaming 1x1 convolution 128 -> 256 with the top-down add (pointwise.hip): the C3 lateral
-static const int kHeadEntryHalfCfg = 107;  // 16x16 blocks on 32-channel half halos fetched two K-steps ahead (head_entry_half.hip): no exposed halo switch
-static const int kHeadEntryHaloCfg = 102;  // composed head entry: interior classes on head_entry_halo.hip, border classes on cfg 8
-static bool halo_enabled() {
-    const char* e = std::getenv("VTD_HALO_CONV");
-    return !(e && e[0] == '0');
-}
-
-// Configurations 0 / 12 / 13 / 14 / 15 are one kernel family (128 or 256 channels wide, 3- or 2-stage ring) at tile heights 256 / 208 /
-// 272 rows, on 8 or 16 waves.  Which is cheapest depends on how the launch's tile count falls on the 256 CUs (one workgroup each), i.e.
-// on the ACTUAL row count, which a per-bucket table cannot know (272 crops and 512 crops share a bucket; the table's entry was timed at
-// 512): rounds x time per tile.  Time per tile = rows x columns / relative efficiency of the shape, measured on layer 2-4 and on the
-// CRNN at 272 and 301 crops with every convolution forced onto each shape in turn (tools/gpu_rec_cfgs.sh, round 4): 4 x 2 waves of
-// 64 x 64 (cfg 0) 1.0, the same tile on 16 waves (14) 1.04, 2 x 4 waves of 9+8 fragments x 32 (13: 272 rows) 0.92, 7+6 x 32 (12: 208 rows)
-// 0.80, the 256 x 256 tile (15) 1.07.  What that buys at 272 crops: conv5 (34 816 rows x 512 channels; the table's 256 x 256 tile makes
-// 272 tiles = two rounds for 1.06) 130 -> 85 us on 272-row tiles (512 tiles = two full rounds), conv3 / conv4 / conv6 58 / 99 / 177 ->
-// 52 / 87 / 152 us; at 301 crops the 16-wave 256-row tile wins instead and conv5 takes 99 us.  The table's entry is tried first and
-// keeps the slot unless another shape is cheaper by more than 6 % (short-K launches have per-tile overheads the model does not see).
-// A pure function of the shape, and the tile shape never changes a bit of the result
-// (tests/test_gpu_detector.py: test_implicit_gemm_tile_heights_bit_identical).
-static int pick_tile_height(const ConvParams& p, int table_cfg) {
-    if (const char* e = std::getenv("VTD_TILE_HEIGHT_MODEL"); e && e[0] == '0') return table_cfg;
-    if (std::getenv("VTD_FORCE_CONV_CFG")) return table_cfg;  // tests pin one configuration
-    static const struct { int cfg, bm, bn; double eff; } family[5] = {{0, 256, 128, 1.0}, {14, 256, 128, 1.04}, {13, 272, 128, 0.92}, {12, 208, 128, 0.80},
-                                                                      {15, 256, 256, 1.07}};
-    auto cost_of = [&](int cfg) -> double {
-        for (const auto& k : family)
-            if (k.cfg == cfg) {
-                if (!vtd_conv_config_valid(p, k.cfg)) return 0.0;
-                const int64_t tiles = (int64_t)((p.M + k.bm - 1) / k.bm) * (p.cout_pad / k.bn);
-                return (double)((tiles + 255) / 256) * k.bm * k.bn / k.eff;
-            }
-        return 0.0;
-    };
-    int best = table_cfg;
-    double best_cost = cost_of(table_cfg);
-    if (best_cost == 0.0) return table_cfg;
-    const double keep = best_cost * 0.94;   // another shape must beat the table's by more than 6 %
-    double other_cost = keep;
-    for (const auto& k : family) {
-        if (k.cfg == table_cfg) continue;
-        const double c = cost_of(k.cfg);
-        if (c > 0.0 && c < other_cost) { other_cost = c; best = k.cfg; }
-    }
-    (void)best_cost;
-    return best;
-}
-
-static int launch_conv_op(const ConvOp& c, int n, hipStream_t s, int cfg = -1, float* prob_out = nullptr) {
-    ConvParams p;
-    fill_conv_params(c, n, p);
-    if (prob_out) p.prob_out = prob_out;
-#ifdef VTD_EXPERIMENTAL_CANDIDATES
-    if (cfg == kHeadEntryPairCfg) {
-        if (!c.hp_half_steps || !c.tile_combo_border) return ERR_GEOMETRY;
-        return vtd_launch_head_entry_pair(p, c.hp_half_steps, c.hp_plan, c.hp_nh, s);
-    }
-    if (cfg == kHeadEntryHalfCfg) {
-        if (!c.hh_sched || !c.tile_combo_border) return ERR_GEOMETRY;
-        return vtd_launch_head_entry_half(p, c.hh_sched, c.he_nsteps, s);
-    }
-#else
-    if (cfg == kHeadEntryPairCfg || cfg == kHeadEntryHalfCfg) return ERR_GEOMETRY;  // candidates of the instrumented build only
-#endif
-    if (cfg == kHeadEntryHaloCfg || cfg == kHeadEntryHalo256Cfg) {  // interior classes only; border tiles = the next graph slot
-        if (!c.he_steps || !c.tile_combo_border) return ERR_GEOMETRY;
-        return vtd_launch_head_entry_halo(p, c.he_steps, c.he_nsteps, cfg == kHeadEntryHalo256Cfg ? 1 : 0, s);
-    }
-    if (cfg == kHaloCfg || cfg == kHaloC64Cfg || cfg == kHalo64Cfg) {
-        int bn = 0, tw = 0;
-        if (!vtd_conv_halo_supported(p, &bn, &tw)) return ERR_GEOMETRY;
-        return vtd_launch_conv_halo(p, cfg == kHaloC64Cfg ? 1 : cfg == kHalo64Cfg ? 2 : bn, tw, s);
-    }
-    if (cfg == kHaloSmallCfg) return vtd_conv_halo_small_supported(p) ? vtd_launch_conv_halo_small(p, s) : ERR_GEOMETRY;
-    if (cfg == kPointwiseCfg) return vtd_launch_pointwise128(p, s);
-    if (!c.plist && (cfg == 0 || cfg == 12 || cfg == 13 || cfg == 14 || cfg == 15)) cfg = pick_tile_height(p, cfg);
-    return vtd_launch_conv(p, cfg, s);
-}
-
-// Border pixels of the composed head entry: the same op restricted to the border classes' 128-row tiles.
-static int launch_border_tiles(const ConvOp& c, int n, hipStream_t s) {
-    if (!c.tile_combo_border || c.tiles_border <= 0) return ERR_GEOMETRY;
-    ConvParams pb;
-    fill_conv_params(c, n, pb);
-    pb.tile_combo = c.tile_combo_border; pb.tiles_per_img = c.tiles_border; pb.M = n * c.tiles_border * 128;
-    pb.plist_b = nullptr; pb.tile_combo_b = nullptr; pb.tiles_per_img_b = 0;
-    // 384 tiles on 256 CUs: one latency-bound round, so the 3-stage ring (two K-steps of loads in flight) beats the 2-stage one
-    // that wins when several workgroups share a CU (41 vs 53 us)
-    return vtd_launch_conv(pb, 9, s);
-}
-
-// Times every valid tile configuration of one convolution at batch n and returns the fastest (HIP events on `s`).
-// The launch writes the op's real output buffer; the graph recomputes it on the next forward anyway.
-static int autotune_conv(const ConvOp& c, int n, hipStream_t s, int* best_cfg) {
-    ConvParams p;
-    fill_conv_params(c, n, p);
-    hipEvent_t e0, e1;
-    VTD_HIP_CHECK(hipEventCreate(&e0));
-    VTD_HIP_CHECK(hipEventCreate(&e1));
-    float best = 1e30f;
-    int best_id = -1, rc = 0;
-    if (p.plist) {  // tests: pin the composed conv to one tile configuration (8..11)
-        const char* fc = std::getenv("VTD_FORCE_CLASSED_CFG");
-        if (fc && (vtd_conv_config_valid(p, std::atoi(fc)) || ((std::atoi(fc) == kHeadEntryHaloCfg || std::atoi(fc) == kHeadEntryHalo256Cfg) && c.he_steps) ||
-                   (std::atoi(fc) == kHeadEntryHalfCfg && c.hh_sched) ||
-                   (std::atoi(fc) == kHeadEntryPairCfg && c.hp_half_steps))) {
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            *best_cfg = std::atoi(fc);
-            return 0;
-        }
-    }
-    for (int cfg = 0; cfg < vtd_conv_num_configs() && !rc; ++cfg) {
-        if (!vtd_conv_config_valid(p, cfg)) continue;
-        if ((rc = vtd_launch_conv(p, cfg, s))) break;  // warm-up (also sets the LDS attribute)
-        (void)hipEventRecord(e0, s);
-        for (int rep = 0; rep < 3 && !rc; ++rep) rc = vtd_launch_conv(p, cfg, s);
-        (void)hipEventRecord(e1, s);
-        if (hipEventSynchronize(e1) != hipSuccess) { rc = ERR_ARG; break; }
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        if (ms < best) { best = ms; best_id = cfg; }
-    }
-    if (!rc && p.plist && c.he_steps && halo_enabled()) {  // composed head entry: halo-plane kernels + border tiles
-        const float best_gathered = best;
-        for (int variant = 0; variant < 4 && !rc; ++variant) {
-            if (variant == 2 && !c.hp_half_steps) continue;
-            if (variant == 3 && !c.hh_sched) continue;
-            const int vcfg = variant == 3 ? kHeadEntryHalfCfg : variant == 2 ? kHeadEntryPairCfg : variant ? kHeadEntryHalo256Cfg : kHeadEntryHaloCfg;
-            auto both = [&]() { int r = launch_conv_op(c, n, s, vcfg); return r ? r : launch_border_tiles(c, n, s); };
-            if ((rc = both())) break;
-            float ms = 1e30f;
-            for (int round = 0; round < 2 && !rc; ++round) {  // the two variants are within ~5 %: best of two rounds of four
-                (void)hipEventRecord(e0, s);
-                for (int rep = 0; rep < 4 && !rc; ++rep) rc = both();
-                (void)hipEventRecord(e1, s);
-                if (hipEventSynchronize(e1) != hipSuccess) rc = ERR_ARG;
-                float t = 0.f;
-                (void)hipEventElapsedTime(&t, e0, e1);
-                ms = t * 0.75f < ms ? t * 0.75f : ms;  // scaled to the 3 launches the other candidates are timed on
-            }
-            if (const char* v = std::getenv("VTD_AUTOTUNE_VERBOSE"); v && v[0] == '1')
-                std::fprintf(stderr, "[autotune] head entry variant %d: %.1f us per launch incl. border tiles (best so far %.1f, cfg %d)\n", vcfg,
-                             ms / 3.f * 1e3f, best / 3.f * 1e3f, best_id);
-            // Plain timing, no hand-set handicaps: this back-to-back contest only serves shapes the shipped table
-            // (vtd_amd/tuning/gfx950.txt, chosen by in-situ measurement of the whole pipeline: tools/tune_table.py) lacks.
-            (void)best_gathered;
-            if (!rc && ms < best) { best = ms; best_id = vcfg; }
-        }
-    }
-    if (!rc && vtd_pointwise128_supported(p)) {
-        if (!(rc = vtd_launch_pointwise128(p, s))) {
-            (void)hipEventRecord(e0, s);
-            for (int rep = 0; rep < 3 && !rc; ++rep) rc = vtd_launch_pointwise128(p, s);
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) rc = ERR_ARG;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            if (!rc && ms < best) { best = ms; best_id = kPointwiseCfg; }
-        }
-    }
-    int hbn = 0, htw = 0;
-    const char* force = std::getenv("VTD_FORCE_HALO");  // tests: 1 = take the halo kernel wherever it applies,
-    bool pinned = false;  // the variant VTD_FORCE_HALO=2 / 3 names was taken: no later variant may win on time
-    if (!rc && halo_enabled() && vtd_conv_halo_supported(p, &hbn, &htw)) {
-        if (force && (force[0] == '1' || force[0] == '2' || force[0] == '3')) best = 1e30f;  // 2 = and its persistent 64->64 variant, 3 = the hand-pipelined 64-channel kernel
-        for (int variant = 0; variant < 3 && !rc; ++variant) {
-            if (variant == 1 && !vtd_conv_halo_c64_supported(p, htw)) continue;
-            const int bn = variant == 1 ? 1 : variant == 2 ? 2 : hbn;
-            if ((rc = vtd_launch_conv_halo(p, bn, htw, s))) break;
-            (void)hipEventRecord(e0, s);
-            for (int rep = 0; rep < 3 && !rc; ++rep) rc = vtd_launch_conv_halo(p, bn, htw, s);
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) rc = ERR_ARG;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            const int vid = variant == 1 ? kHaloC64Cfg : variant == 2 ? kHalo64Cfg : kHaloCfg;
-            const bool pin = (variant == 1 && force && force[0] == '2') || (variant == 2 && force && force[0] == '3');
-            if (!rc && !pinned && (ms < best || pin)) { best = ms; best_id = vid; pinned = pin; }
-        }
-    }
-    if (!rc && halo_enabled() && vtd_conv_halo_small_supported(p)) {  // 4 = the small-footprint kernel wherever it applies
-        if (!(rc = vtd_launch_conv_halo_small(p, s))) {
-            (void)hipEventRecord(e0, s);
-            for (int rep = 0; rep < 3 && !rc; ++rep) rc = vtd_launch_conv_halo_small(p, s);
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) rc = ERR_ARG;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            const bool pin = force && force[0] == '4';
-            if (!rc && (pin || (!pinned && ms < best))) { best = ms; best_id = kHaloSmallCfg; }
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *best_cfg = best_id;
-    if (const char* v = std::getenv("VTD_AUTOTUNE_VERBOSE"); v && v[0] == '1')
-        std::fprintf(stderr, "[autotune] M=%d N=%d K=%d%s -> cfg %d (%.1f us per launch)\n", p.M, p.cout, p.K, p.plist ? " classed" : "", best_id,
-                     best / 3.f * 1e3f);
-    return rc;
-}
-
-static bool autotune_enabled() {
-    const char* e = std::getenv("VTD_AUTOTUNE");
-    return !(e && e[0] == '0');
-}
 
 // ---- Pillow resample coefficient tables (8-bit path, bilinear filter with antialias support scaling)
 struct ResampleAxis {
@@ -522,21 +208,10 @@ struct PreTables {
     int ksx = 0, ksy = 0, max_rows = 0;
 };
 
-}  // namespace vtd
-
-using namespace vtd;
-
-namespace vtd {
-// what both model handles share: the ingested state dict and the device arena
-struct ModelBase {
+// what both model handles share: the ingested state dict, the device arena and the kernel-selection table (conv_select.h)
+struct ModelBase : TuningTable {
     StateDict sd;
     DeviceArena arena;
-    // Kernel-selection table: "<op signature>|n<batch bucket>" -> configuration id.  Filled from vtd_*_set_tuning (a table
-    // shipped with the package / broadcast by rank 0) and by the timing contest for shapes the table does not hold;
-    // vtd_*_get_tuning serialises it.  With a complete table kernel choice -- hence fp32 summation order -- is the same in
-    // every process and on every rank.
-    std::map<std::string, int> tuning;
-    bool tuning_measured = false;  // at least one entry came from this process's own timing contest
     int alloc_tensor(TensorDesc& t) {
         void* p = nullptr;
         int rc = arena.alloc(&p, (size_t)tensor_elems(t) * sizeof(half_t), true);
@@ -550,100 +225,9 @@ struct ModelBase {
     }
 };
 
-// Signature of one convolution launch slot: everything kernel choice may depend on except the batch.
-static std::string conv_signature(const ConvOp& c) {
-    char buf[192];
-    int len = std::snprintf(buf, sizeof buf, "conv|in%dx%dx%d|out%dx%d|co%d|K%d|s%d|f%x|r%d|c%d", c.in.h, c.in.w, c.in.c, c.ho, c.wo, c.cout, c.K,
-                            c.stride, (unsigned)c.flags, c.has_res ? 1 + c.res_shift : 0, c.plist ? 1 : 0);
-    if (c.dual) len += std::snprintf(buf + len, sizeof buf - len, "|x%dm%ds%d", c.in2.c, c.in2_mul, c.in2_shr);  // second K segment (entries of plain convs keep their keys)
-    if (c.pool_pw) std::snprintf(buf + len, sizeof buf - len, "|p2x%d", c.pool_pw);  // max-pool fused into the epilogue
-    return buf;
-}
-
-static bool config_valid_for(const ConvOp& c, int n, int cfg) {
-    ConvParams p;
-    fill_conv_params(c, n, p);
-    if (cfg == kHeadEntryPairCfg) return p.plist && c.hp_half_steps && c.tile_combo_border;
-    if (cfg == kHeadEntryHalfCfg) return p.plist && c.hh_sched && c.tile_combo_border;
-    if (cfg == kHeadEntryHaloCfg || cfg == kHeadEntryHalo256Cfg) return p.plist && c.he_steps && c.tile_combo_border;
-    if (cfg == kHaloCfg || cfg == kHaloC64Cfg || cfg == kHalo64Cfg) {
-        int bn = 0, tw = 0;
-        if (!vtd_conv_halo_supported(p, &bn, &tw)) return false;
-        return cfg != kHaloC64Cfg || vtd_conv_halo_c64_supported(p, tw);
-    }
-    if (cfg == kHaloSmallCfg) return vtd_conv_halo_small_supported(p);
-    if (cfg == kPointwiseCfg) return vtd_pointwise128_supported(p);
-    return cfg >= 0 && cfg < vtd_conv_num_configs() && vtd_conv_config_valid(p, cfg);
-}
-
-// Configuration of one launch slot at batch bucket n: the table's entry when it has a valid one, else the timing contest
-// (whose result joins the table), else -1 (built-in heuristic).
-static int choose_config(ModelBase* m, const ConvOp& c, int n, hipStream_t s, int* cfg) {
-    const std::string key = conv_signature(c) + "|n" + std::to_string(n);
-    auto it = m->tuning.find(key);
-    // test switches that pin a kernel variant (VTD_FORCE_CLASSED_CFG, VTD_FORCE_HALO) are honoured by the contest: they outrank the table
-    const bool forced = std::getenv("VTD_FORCE_CLASSED_CFG") || std::getenv("VTD_FORCE_HALO");
-    if (const char* fc = std::getenv("VTD_FORCE_CONV_CFG"); fc && !c.plist && config_valid_for(c, n, std::atoi(fc))) {
-        *cfg = std::atoi(fc);  // tests: one implicit-GEMM tile configuration wherever it is valid, every other slot as usual
-        return 0;
-    }
-    if (const char* fp = std::getenv("VTD_FORCE_POINTWISE"); fp && fp[0] == '1' && config_valid_for(c, n, kPointwiseCfg)) {
-        *cfg = kPointwiseCfg;  // tests: the streaming 1x1 kernel wherever it applies, every other slot as usual
-        return 0;
-    }
-    if (!forced && it != m->tuning.end() && config_valid_for(c, n, it->second)) {
-        *cfg = it->second;
-        return 0;
-    }
-    *cfg = -1;
-    if (!autotune_enabled()) return 0;
-    int rc = autotune_conv(c, n, s, cfg);
-    if (!rc && *cfg >= 0) {
-        m->tuning[key] = *cfg;
-        m->tuning_measured = true;
-    }
-    return rc;
-}
-
-static int set_tuning_text(ModelBase* m, const char* text) {
-    if (!m || !text) return ERR_ARG;
-    const char* p = text;
-    while (*p) {
-        const char* eol = std::strchr(p, '\n');
-        std::string line = eol ? std::string(p, eol) : std::string(p);
-        p = eol ? eol + 1 : p + line.size();
-        if (line.empty() || line[0] == '#') continue;
-        const size_t sp = line.find_last_of(" \t");
-        if (sp == std::string::npos || sp + 1 >= line.size()) return ERR_ARG;
-        char* end = nullptr;
-        const long v = std::strtol(line.c_str() + sp + 1, &end, 10);
-        if (!end || *end != 0) return ERR_ARG;
-        size_t ke = sp;
-        while (ke > 0 && (line[ke - 1] == ' ' || line[ke - 1] == '\t')) --ke;
-        m->tuning[line.substr(0, ke)] = (int)v;
-    }
-    return 0;
-}
-
-static int64_t get_tuning_text(const ModelBase* m, char* buf, int64_t cap) {
-    if (!m) return ERR_ARG;
-    std::string out;
-    for (const auto& kv : m->tuning) out += kv.first + " " + std::to_string(kv.second) + "\n";
-    if (buf && cap > 0) {
-        const size_t ncopy = std::min((size_t)cap - 1, out.size());
-        std::memcpy(buf, out.data(), ncopy);
-        buf[ncopy] = 0;
-    }
-    return (int64_t)out.size() + 1;
-}
-
-static int batch_bucket(int n, int cap) {
-    int b = 1;
-    while (b < n) b <<= 1;
-    return std::min(b, cap);
-}
-
 }  // namespace vtd
+
+using namespace vtd;
 
 struct vtd_detector : vtd::ModelBase {
     std::string backbone;
@@ -1872,8 +1456,10 @@ static int run_detector_ops(vtd_detector* d, int n, float* prob_dev, float* thre
         const Op& o = d->ops[oi];
         int rc = 0;
         if (o.final_slot == 1 && !thresh_dev) continue;
-        if (o.kind == Op::BORDER && (oi == 0 || (cfgs[oi - 1] != kHeadEntryHaloCfg && cfgs[oi - 1] != kHeadEntryHalo256Cfg && cfgs[oi - 1] != kHeadEntryPairCfg && cfgs[oi - 1] != kHeadEntryHalfCfg)))
-            continue;  // the gathered kernel did every class
+        if (o.kind == Op::BORDER) {
+            const ConvCandidate* row = oi ? find_conv_candidate(cfgs[oi - 1]) : nullptr;
+            if (!(row && row->needs_border)) continue;  // the gathered kernel did every class
+        }
         hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool prof = d->profiling && (d->prof_only < 0 || d->prof_only == (int)oi);
         if (prof) {
@@ -2009,32 +1595,19 @@ int vtd_detector_get_profile(vtd_detector* d, int op_index, char* name, int name
     const Op& o = d->ops[op_index];
     if (o.kind == Op::CONV) {
         const ConvOp& c = o.conv;
-        static const char* kTile[] = {"256,128,s3", "128,128,s2", "128,128,s3", "256,64,s2", "256,64,s3", "128,64,s2", "128,64,s3",
-                                      "64,256,s2", "128,64,s2,classed", "128,64,s3,classed", "256,64,s2,classed", "256,64,s3,classed", "208,128,s3", "272,128,s3", "256,128,s3,16w", "256,256,s2", "128,64,s6"};
         int cfg = -1;
         if (!d->tuned.empty()) cfg = d->tuned.rbegin()->second[op_index];
-        if (cfg == kHeadEntryPairCfg)
-            std::snprintf(name, name_cap, "head_entry_pair M/img=%d N=%d K=%d (lateral+smooth+head conv composed; border classes in the "
-                          "next slot)", c.ho * c.wo, c.cout, c.K);
-        else if (cfg == kHeadEntryHalfCfg)
-            std::snprintf(name, name_cap, "head_entry_half M/img=%d N=%d K=%d (lateral+smooth+head conv composed, half halos two steps ahead; border classes in the "
-                          "next slot)", c.ho * c.wo, c.cout, c.K);
-        else if (cfg == kHeadEntryHalo256Cfg)
-            std::snprintf(name, name_cap, "head_entry_halo256 M/img=%d N=%d K=%d (lateral+smooth+head conv composed; border classes in the "
-                          "next slot)", c.ho * c.wo, c.cout, c.K);
-        else if (cfg == kHeadEntryHaloCfg)
-            std::snprintf(name, name_cap, "head_entry_halo M/img=%d N=%d K=%d (lateral+smooth+head conv composed; border classes in the "
-                          "next slot)", c.ho * c.wo, c.cout, c.K);
-        else if (cfg == kPointwiseCfg)
-            std::snprintf(name, name_cap, "pointwise128 1x1%s streaming M/img=%d N=%d K=%d", c.has_res ? "+top-down add" : "", c.ho * c.wo, c.cout, c.K);
-        else if (cfg == kHaloSmallCfg)
-            std::snprintf(name, name_cap, "conv_halo_small 3x3 M/img=%d N=%d K=%d", c.ho * c.wo, c.cout, c.K);
-        else if (cfg == kHaloCfg || cfg == kHaloC64Cfg || cfg == kHalo64Cfg)
-            std::snprintf(name, name_cap, "conv_halo%s 3x3 M/img=%d N=%d K=%d", cfg == kHaloC64Cfg ? "_c64_persistent" : cfg == kHalo64Cfg ? "64" : "",
-                          c.ho * c.wo, c.cout, c.K);
+        const ConvCandidate* row = find_conv_candidate(cfg);
+        if (row && row->needs_border)
+            std::snprintf(name, name_cap, "%s M/img=%d N=%d K=%d (lateral+smooth+head conv composed%s; border classes in the next slot)", row->name,
+                          c.ho * c.wo, c.cout, c.K, cfg == kHeadEntryHalfCfg ? ", half halos two steps ahead" : "");
+        else if (row && cfg == kPointwiseCfg)
+            std::snprintf(name, name_cap, "%s 1x1%s streaming M/img=%d N=%d K=%d", row->name, c.has_res ? "+top-down add" : "", c.ho * c.wo, c.cout, c.K);
+        else if (row)  // the conv_halo family
+            std::snprintf(name, name_cap, "%s 3x3 M/img=%d N=%d K=%d", row->name, c.ho * c.wo, c.cout, c.K);
         else
-            std::snprintf(name, name_cap, "conv_igemm<%s> M/img=%d N=%d K=%d%s", (cfg >= 0 && cfg < 17) ? kTile[cfg] : "default",
-                          c.ho * c.wo, c.cout, c.K, c.plist ? " (lateral+smooth+head conv composed)" : "");
+            std::snprintf(name, name_cap, "conv_igemm<%s> M/img=%d N=%d K=%d%s", vtd_conv_config_name(cfg), c.ho * c.wo, c.cout, c.K,
+                          c.plist ? " (lateral+smooth+head conv composed)" : "");
     } else if (o.kind == Op::POOL) {
         std::snprintf(name, name_cap, "maxpool %dx%d/s%d", o.pk[0], o.pk[1], o.pk[2]);
     } else if (o.kind == Op::BORDER) {
