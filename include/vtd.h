@@ -607,8 +607,11 @@ int vtd_recognizer_crop_resize(vtd_recognizer* r, const uint8_t* frames_dev, int
 int vtd_recognizer_set_input_nchw(vtd_recognizer* r, const float* x_dev, int ncrops, vtd_stream stream);
 /* CRNN.forward (text_recognizer.py:29-37) on the current input: logits_dev receives [ncrops,31,vocab] float32. */
 int vtd_recognizer_forward(vtd_recognizer* r, int ncrops, float* logits_dev, vtd_stream stream);
-/* Test taps as dense NCHW float32 on the host: "resized" ([n,32,128,3] uint8 values), "cnn" ([n,512,1,31]),
- * "h0", "h1" ([n,512,1,31] LSTM layer outputs).  Synchronises the stream. */
+/* Test taps as dense NCHW float32 on the host: "resized" ([n,32,128,3] uint8 values); the convolution stages, each behind
+ * its BN + ReLU and (where the layer has one) its max-pool, in both fuse_pools modes: "conv1" ([n,64,16,64]), "conv2"
+ * ([n,128,8,32]), "conv3" ([n,256,8,32]), "conv4" ([n,256,4,32]), "conv5" ([n,512,4,32]), "conv6" ([n,512,2,32]), "cnn"
+ * (conv7, [n,512,1,31]); "h0", "h1" ([n,512,1,31]: LSTM layer outputs [n,31,512] seen as NCHW, forward units 0-255, reverse
+ * units 256-511).  The hoisted input projections and the cell state have no tap.  Synchronises the stream. */
 int vtd_recognizer_read_tap(vtd_recognizer* r, const char* name, int ncrops, float* host_out, int64_t capacity, vtd_stream stream);
 int64_t vtd_recognizer_macs_per_crop(const vtd_recognizer* r);
 /* Kernel-selection table of the recogniser (see vtd_detector_set_tuning); buckets are powers of two of the crop count. */

@@ -252,3 +252,59 @@ def test_pools_fused_into_the_conv_epilogues_are_bit_identical(hip, monkeypatch,
         logits, cnn = run(1, cfg)
         assert np.array_equal(cnn, want_cnn), (ncrops, cfg)
         assert np.array_equal(logits, want_logits), (ncrops, cfg)
+
+
+def _decode_rows(T, V, seed):
+    """[6, T, V] float32 logits, one launch: two free rows of different lengths, a row of exact ties across the lane stride (classes c
+    and c + 64 are read by the same lane in successive iterations; 5 and 69 at t = 0; where V <= 69 the partner is c + 16, another lane),
+    a row of exact ties between two lanes (resolved by the wave reduction), an all-blank row and a row of one repeated class.  Outside
+    the ties the top-2 logit gap is at least 1 (>= 1e-3 asked)."""
+    rng = np.random.default_rng(seed)
+    lg = (3.0 * rng.standard_normal((6, T, V))).astype(np.float32)
+    top = lg.argmax(2)
+    for r in range(6):
+        lg[r, np.arange(T), top[r]] += np.float32(1.0)
+    lg[0, T // 2:, 0] = 30.0                                   # row 0 ends half way: blanks behind
+    lg[5, (2 * T) // 3:, 0] = 30.0
+    far = 64 if V > 69 else 16
+    for t in range(T):
+        a = 5 + t % 3
+        lg[1, t, a] = lg[1, t, a + far] = np.float32(20.0)     # lowest index wins, as np.argmax does
+        b = 7 + t % 4
+        lg[2, t, b] = lg[2, t, b + 13] = np.float32(20.0)
+    lg[3, :, 0] = 30.0
+    lg[4, :, 11] = 30.0
+    srt = np.sort(lg.astype(np.float64), axis=2)
+    gap = srt[..., -1] - srt[..., -2]
+    assert (gap[[0, 3, 4, 5]] >= 1e-3).all() and (gap[[1, 2]] == 0).all()
+    assert (srt[[1, 2], :, -2] - srt[[1, 2], :, -3] >= 1e-3).all()
+    return lg
+
+
+@pytest.mark.parametrize("T,V", [(1, 97), (31, 37), (31, 97), (128, 128)])
+def test_ctc_decode_batched_rows_vs_oracle(hip, T, V):
+    """vtd_ctc_greedy_decode on n = 6 rows of different lengths and content in one launch, softmax fused, against
+    oracle.pipeline.decode_prediction on the fp64 softmax of the same logits with the vocabulary cut to V."""
+    from vtd_amd.engine import ctc_greedy_decode
+    lg = _decode_rows(T, V, 100 * T + V)
+    vocab = {k: v for k, v in opipe.build_vocab().items() if v < V}
+    got = ctc_greedy_decode(torch.from_numpy(lg), id_to_char_table(build_vocab())[:V])
+    z = lg.astype(np.float64)
+    e = np.exp(z - z.max(2, keepdims=True))
+    probs = e / e.sum(2, keepdims=True)
+    want = [opipe.decode_prediction(p, vocab) for p in probs]
+    print(T, V, [t for t, _ in got])
+    assert [t for t, _ in got] == [t for t, _ in want]
+    assert max(abs(c - w) for (_, c), (_, w) in zip(got, want)) <= 1e-5
+    assert got[3] == ("", 0.0)
+    assert len(got[4][0]) == 1
+    assert (lg[1].argmax(1) == 5 + np.arange(T) % 3).all() and (lg[2].argmax(1) == 7 + np.arange(T) % 4).all()
+    if T > 1:
+        assert len({len(t) for t, _ in want}) >= 4, "rows of different lengths"
+
+
+def test_ctc_decode_rejects_more_than_128_steps(hip):
+    from vtd_amd._native import NativeError
+    from vtd_amd.engine import ctc_greedy_decode
+    with pytest.raises(NativeError, match="-1040"):
+        ctc_greedy_decode(torch.zeros(2, 129, 97), id_to_char_table(build_vocab()))

@@ -1673,6 +1673,7 @@ static int build_recognizer_graph(vtd_recognizer* r) {
         if ((rc = upload(r->arena, wp.data(), wp.size() * sizeof(half_t), (void**)&r->w1))) return rc;
         if ((rc = upload(r->arena, bp.data(), bp.size() * 4, (void**)&r->b1))) return rc;
         if ((rc = new_tensor(16, 64, 64, 1, r->t1))) return rc;
+        r->taps["conv1"] = r->t1;
         r->macs += (int64_t)32 * 128 * 64 * 27;
     }
     struct Spec { int conv, bn, cin, cout, k, pad, ph, pw; };
@@ -1714,6 +1715,8 @@ static int build_recognizer_graph(vtd_recognizer* r) {
             r->ops.push_back(po);
             x = z;
         }
+        // stage taps conv2..conv6: the layer's output behind its pool, whichever launch took the pool (conv7 is the `cnn` tap)
+        if (&sp != &specs[5]) r->taps["conv" + std::to_string((int)(&sp - specs) + 2)] = x;
     }
     if (x.h != 1 || x.w != 31 || x.c != 512) return ERR_GEOMETRY;
     r->t7 = x;

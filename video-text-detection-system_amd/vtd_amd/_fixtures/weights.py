@@ -14,8 +14,9 @@
     layer1  block0: t = relu(255*x0 - 127.5)   block1: B = 2*relu(t) - 2*relu(t - 0.5)  in {0, ~1}
     FPN     only the C2 lateral feeds channel 0; smooth / head conv / ConvT pass it with unit centre taps
     ConvT6  logit = 16*B - 8
-* ``stress_detector_state_dict`` / ``stress_trocr_state_dict``  calibrated stress weights for the stage-isolated parity tests
-  (oracle/stage_bounds.py, oracle/trocr_bounds.py): activations O(1), biases of activation size, decisions that mean something.
+* ``stress_detector_state_dict`` / ``stress_trocr_state_dict`` / ``stress_crnn_state_dict``  calibrated stress weights for the
+  stage-isolated parity tests (oracle/stage_bounds.py, oracle/trocr_bounds.py, oracle/crnn_bounds.py): activations O(1), biases of
+  activation size, decisions that mean something.
 """
 from collections import OrderedDict
 
@@ -274,6 +275,29 @@ def calibrated_crnn_state_dict(seed=0, vocab_size=97, ih_gain=2.0, cls_gain=8.0)
     sd["classifier.weight"] = sd["classifier.weight"] * cls_gain
     with torch.no_grad():
         return _crnn_calibrate(sd, _calibration_batch(seed))
+
+
+def stress_crnn_state_dict(seed=0, vocab_size=97, bn_shift=(-0.45, 0.5), ih_gain=(1.5, 2.5), hh_gain=(8.0, 8.0), forget_bias=(0.5, 2.5)):
+    """Calibrated stress weights for the CRNN's stage-isolated parity tests (oracle/crnn_bounds.py): the calibrated fixture with
+    BatchNorm shifts of activation size spread per channel (mean + std x N(0,1), statistics re-calibrated behind them), gains on
+    rnn.weight_ih* (per layer, on top of the calibrated fixture's) and rnn.weight_hh* (per layer) and a positive forget-gate bias
+    spread over [lo, hi], so that W_hh h is a large part of every gate pre-activation and the cell state carries over many steps.
+    tests/test_crnn_bounds.py asserts what this must achieve, on the CPU."""
+    sd = calibrated_crnn_state_dict(seed, vocab_size)
+    g = torch.Generator().manual_seed(70001 + seed)
+    for _, bi, _, _ in _CRNN_CONV:
+        c = sd[f"cnn.{bi}.bias"].shape[0]
+        sd[f"cnn.{bi}.bias"] = bn_shift[0] + bn_shift[1] * torch.randn(c, generator=g)
+    with torch.no_grad():
+        _crnn_calibrate(sd, _calibration_batch(seed))
+    for layer in range(2):
+        for suf in (f"_l{layer}", f"_l{layer}_reverse"):
+            sd["rnn.weight_ih" + suf] = sd["rnn.weight_ih" + suf] * ih_gain[layer]
+            sd["rnn.weight_hh" + suf] = sd["rnn.weight_hh" + suf] * hh_gain[layer]
+            b = sd["rnn.bias_ih" + suf].clone()
+            b[256:512] += torch.empty(256).uniform_(forget_bias[0], forget_bias[1], generator=g)
+            sd["rnn.bias_ih" + suf] = b
+    return sd
 
 
 def margin_crnn_live_classes(seed=0, vocab_size=97):

@@ -461,8 +461,11 @@ class RecognizerEngine(_Tunable):
         PINNED.release(ticket["keep"][0], ticket["event"])
         return out
 
+    TAP_SHAPES = {"resized": (32, 128, 3), "conv1": (64, 16, 64), "conv2": (128, 8, 32), "conv3": (256, 8, 32), "conv4": (256, 4, 32),
+                  "conv5": (512, 4, 32), "conv6": (512, 2, 32), "cnn": (512, 1, 31), "h0": (512, 1, 31), "h1": (512, 1, 31)}
+
     def read_tap(self, name, n):
-        shape = (n, 32, 128, 3) if name == "resized" else (n, 512, 1, 31)
+        shape = (n,) + self.TAP_SHAPES.get(name, (512, 1, 31))   # an unknown name is the library's error to raise
         out = np.empty(shape, np.float32)
         with self.lock:
             _native.check(self.lib.vtd_recognizer_read_tap(self.handle, name.encode(), n, out.ctypes.data, out.size, _stream_ptr()),
