@@ -414,6 +414,36 @@ int vtd_bottleneck_train_backward(const void* x_dev, int n, int h_in, int w_in, 
                                   float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                   const vtd_bottleneck_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- The 256-wide Bottlenecks of ResNet-50's res4 (torchvision's layer3), the same file, host path and kernels at W = 256.  Signatures,
+ * the vtd_bottleneck_params struct, tensors, layouts, scales and the "written, not accumulated" rule are those of vtd_bottleneck_train_*:
+ * x_dev [n][h_in+2][w_in+2][cin], y_dev [n][h+2][w+2][1024], dy_dev NHWC float32 [n][h][w][1024].  Exactly two geometries are accepted,
+ * width 256: (cin 512, stride 2, even h_in and w_in, with downsample: ds_* set) and (cin 1024, stride 1, identity: ds_* ignored).  Every
+ * other geometry (width 512 included: that is vtd_bottleneck_train_*'s), n > 65535, an extent above 4096 and a tensor of 2^31 elements or
+ * more are refused with -3903.
+ * vtd_bottleneck256_train_workspace_bytes, with a256(b) = b rounded up to a multiple of 256, W = 256 (4W = 1024), pin = n (h_in+2) (w_in+2),
+ * pout = n (h+2) (w+2), M = n h w, Min = n h_in w_in and S(r) = min(8, max(1, ceil(r / 4096))):
+ *   mode 0, the forward's workspace, which the backward keeps: a256(2 pin W) [a1, padded at the INPUT's extent] + a256(2 pout W) [a2] +
+ *     a256(2 pout 4W) [id, stride 2 only] + a256(2 W cin) + a256(2 W 9 W) + a256(2 4W W) + a256(2 4W cin) [stride 2 only] (the four folded
+ *     panels) + a256(4 (2 W + 2 4W)) [the biases];
+ *   mode 1, the backward's scratch: a256(4 M 4W) + a256(4 M W) + a256(4 Min W) [g3, g2, g1 fp32] + a256(2 M 4W) + a256(2 M W) +
+ *     a256(2 Min W) [flat fp16 operands] + a256(2 pout 4W) + 2 a256(2 pin W) [padded fp16 operands; g2's is the zero-inserted plane at stride
+ *     2] + a256(2 W 9 W) [transposed panel] + a256(4 4W) [zero bias] + a256(8 256 4W) + a256(4 256) [partials] + a256(8 4W) + 2 a256(8 W) [sums]
+ *     + a256(48) [scales] + a256(4 max(S(M) W 9 W, S(Min) W cin)) [weight-gradient slabs].
+ * Fixed orders: the 1024-wide gradient g3 = dy (y > 0) is summed per channel by min(256, ceil(M / 32)) workgroups of ceil(M / that)
+ * consecutive rows each (one 16-byte load per thread and row), every row in row order in fp64, the partials then in workgroup order; the
+ * 256-wide g2 and g1 by min(256, ceil(rows / 256)) workgroups the same way; every weight-gradient launch (wgrad_mfma.h MODE 3) cuts ITS rows
+ * into S(rows) slabs, summed in slab order in fp64 -- conv3, conv2 and the downsample the M output rows, conv1 the Min rows of the input's
+ * extent.  dx_dev (optional) as vtd_bottleneck_train_backward's.  No atomics, shape-only grids: bitwise repeatable.  Errors, before any
+ * launch: -3903 (a null pointer, eps <= 0, dx_dev without dxscale_dev, a missing ds_* tensor at stride 2, a mode outside {0, 1}, an
+ * unsupported geometry), -3904 (alignment: taps, dy and dx 16 bytes, workspace and scratch 256, scales 8, parameters and gradients 4). */
+int64_t vtd_bottleneck256_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_bottleneck256_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                    float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_bottleneck256_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride,
+                                     const vtd_bottleneck_params* params, float eps, const void* workspace_dev, const void* y_dev,
+                                     const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
+                                     float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
 /* ---- ResNet BasicBlock training with batch-statistics BatchNorm (csrc/resblock_bn_train.hip): the same block as torch's train() mode
  * computes it.  Tensors, layouts, the vtd_basicblock_params struct, the power-of-two gradient scales and the "written, not accumulated" rule
  * are those of vtd_basicblock_train_*.  Two geometries are built, ResNet-18's layer4: (cin 256, width 512, stride 2, even h_in and w_in, with

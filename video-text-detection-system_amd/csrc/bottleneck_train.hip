@@ -1,34 +1,38 @@
 // ResNet Bottleneck (v1.5: the stride sits on the 3x3) training with frozen-statistics BatchNorm (the running statistics normalise and are
-// never written; gamma and beta learn), forward and backward, for the blocks of ResNet-50's last stage (res5, torchvision's layer4), W = 512:
-// (1024 -> 512 -> 2048, stride 2, downsample) and (2048 -> 512 -> 2048, stride 1, identity).
+// never written; gamma and beta learn), forward and backward, for the blocks of ResNet-50's upper two stages.  One host path and one set of
+// kernels serve both widths W; each stage has its own C entries and error codes:
+//   res5 (torchvision's layer4), W = 512: (1024 -> 512 -> 2048, stride 2, downsample) and (2048 -> 512 -> 2048, stride 1, identity)
+//   res4 (torchvision's layer3), W = 256: (512 -> 256 -> 1024, stride 2, downsample) and (1024 -> 256 -> 1024, stride 1, identity)
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn3(conv3(a2)) + id), a2 = relu(bn2(conv2(a1))), a1 = relu(bn1(conv1(x))),
-// id = x or ds_bn(ds(x)); conv1 1x1 cin -> W, conv2 3x3 at stride s, conv3 1x1 W -> 4 W, ds 1x1 cin -> 4 W at stride s.
+// id = x or ds_bn(ds(x)); conv1 1x1 cin -> W, conv2 3x3 at stride s, conv3 1x1 W -> 4 W, ds 1x1 cin = 2 W -> 4 W at stride s.
 //
 // Forward:
 //   fold             per convolution (rb_fold_kernel): w gamma rstd -> fp16 GEMM panel [cout][ksz^2 cin] (k = tap * cin + ci), bias = beta -
 //                    mean gamma rstd; on the device, every call
 //   conv x 3 or 4    conv_igemm.hip: conv1 (ReLU) -> padded a1 at the INPUT's extent; conv2 (stride s, ReLU) -> padded a2; downsample
 //                    (stride 2) -> padded id; conv3 (EPI_RESIDUAL from id or x, ReLU) -> padded y.  a1, a2 and id stay in the workspace
-// Backward from dy (NHWC fp32 [n h w][2048] times a power of two):
-//   mask + reduce    bk_mask_reduce_kernel, one pass over the 2048-wide gradient: g3 = dy (y > 0) in fp32 (the gradient at bn3's output, of
-//                    the downsample's BatchNorm output, and of an identity input) with its per-channel fp64 partial sums and max |.|.
-//                    G = min(256, ceil(rows / 32)) workgroups of ceil(rows / G) consecutive rows each, in row order; thread t owns channels
-//                    4 t .. 4 t + 3 and 1024 + 4 t .. 1024 + 4 t + 3, so every wave load is 1 KiB of one row and a workgroup's two loads
-//                    are the row's 8 KB.  rb_finish_kernel adds the partials in workgroup order and gives the power-of-two scale
+// Backward from dy (NHWC fp32 [n h w][4 W] times a power of two):
+//   mask + reduce    bk_mask_reduce_kernel<4 W / 1024>, one pass over the 4 W-wide gradient: g3 = dy (y > 0) in fp32 (the gradient at bn3's
+//                    output, of the downsample's BatchNorm output, and of an identity input) with its per-channel fp64 partial sums and
+//                    max |.|.  G = min(256, ceil(rows / 32)) workgroups of ceil(rows / G) consecutive rows each, in row order; thread t
+//                    owns channels 1024 j + 4 t .. 1024 j + 4 t + 3 (j < 2 at W = 512, j = 0 at W = 256), so every wave load is 1 KiB of
+//                    one row and a workgroup's loads are the whole row.  rb_finish_kernel adds the partials in workgroup order and gives
+//                    the power-of-two scale
 //   form             rb_form_kernel: the fp16 operands, flat [rows][C] for the weight gradients and ring-padded for the transposed convolutions
-//   g2, g1           the 512-wide stages as resblock_train.hip's: rb_mask_kernel, rb_reduce_kernel (min(256, ceil(rows / 256)) workgroups),
-//                    finish, form.  g1 lives at the input's extent (conv1 is 1x1 at stride 1 in front of the strided 3x3)
-//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h as it stands: conv3 (lda 2048: 16 column tiles, xc 512, 1x1), conv2
-//                    (lda 512, xc 512, 3x3 at stride s over a1), conv1 (lda 512, xc = cin, 1x1, rows = n h_in w_in) and the downsample
-//                    (lda 2048, xc 1024, 1x1 at stride 2).  Slabs: min(8, ceil(rows / 4096)) of the LAUNCH's rows -- conv1's are the
+//   g2, g1           the W-wide stages as resblock_train.hip's: rb_mask_kernel, rb_reduce_kernel (min(256, ceil(rows / 256)) workgroups; one
+//                    channel per thread at W = 256, two at 512), finish, form.  g1 lives at the input's extent (conv1 is 1x1 at stride 1
+//                    in front of the strided 3x3)
+//   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h as it stands: conv3 (lda 4 W: 4 W / 128 column tiles, xc W, 1x1), conv2
+//                    (lda W, xc W, 3x3 at stride s over a1), conv1 (lda W, xc = cin, 1x1, rows = n h_in w_in) and the downsample
+//                    (lda 4 W, xc 2 W, 1x1 at stride 2).  Slabs: min(8, ceil(rows / 4096)) of the LAUNCH's rows -- conv1's are the
 //                    input's, the others' the output's
 //   param            rb_param_kernel: slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s)
-//   da2              conv3^T(g3): a 1x1 GEMM 2048 -> 512 on the transposed folded weights (conv_igemm.hip, fp32 output); g2 = da2 (a2 > 0)
+//   da2              conv3^T(g3): a 1x1 GEMM 4 W -> W on the transposed folded weights (conv_igemm.hip, fp32 output); g2 = da2 (a2 > 0)
 //   da1              conv2^T(g2): the folded weights rotated by 180 degrees and transposed, 3x3 at stride 1.  Stride 2: g2 is written to
 //                    the even positions of a zeroed ring-padded plane of the input's extent first (Z[2o][2p] = g2[o][p]), then the same
 //                    path -- the form resblock_train.hip documents.  g1 = da1 (a1 > 0)
-//   dx (optional)    conv1^T(g1), a 1x1 GEMM 512 -> cin at g1's total scale; plus, stride 1, g3 times the product of the three stages'
-//                    power-of-two multipliers; or, stride 2, ds^T(g3) (a 1x1 GEMM 2048 -> 1024 at g3's scale) times the product of the
+//   dx (optional)    conv1^T(g1), a 1x1 GEMM W -> cin at g1's total scale; plus, stride 1, g3 times the product of the three stages'
+//                    power-of-two multipliers; or, stride 2, ds^T(g3) (a 1x1 GEMM 4 W -> 2 W at g3's scale) times the product of the
 //                    two lower stages' multipliers at the even (row, column) positions
 // No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
 #include "resblock_common.h"
@@ -37,25 +41,30 @@
 
 namespace {
 
-constexpr int BK_W = 512, BK_OUT = 4 * BK_W;
 constexpr int BK_MAX_RED = 256;
-constexpr int BK_ERR_ARG = -3901, BK_ERR_ALIGN = -3902;
+
+// an entry family: the Bottleneck width it accepts and its error-code pair
+struct Fam { int width, err_arg, err_align; };
+constexpr Fam BK_RES5 = {512, -3901, -3902}, BK_RES4 = {256, -3903, -3904};
 
 struct Geo {
     int n, hin, win, cin, stride, h, w;
+    int W, OUT;                  // the Bottleneck width and 4 W
     int64_t m, min, pin, pout;   // output rows, input rows, padded pixels of the input's and the output's extent
     bool ds;
 };
 
-bool make_geo(int n, int hin, int win, int cin, int width, int stride, Geo& g) {
-    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096 || width != BK_W) return false;
-    if (!((cin == 2 * BK_W && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == BK_OUT && stride == 1))) return false;
+bool make_geo(const Fam& fam, int n, int hin, int win, int cin, int width, int stride, Geo& g) {
+    const int W = fam.width, OUT = 4 * W;
+    if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096 || width != W) return false;
+    if (!((cin == 2 * W && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == OUT && stride == 1))) return false;
+    g.W = W; g.OUT = OUT;
     g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w; g.min = (int64_t)n * hin * win;
     g.pin = (int64_t)n * (hin + 2) * (win + 2); g.pout = (int64_t)n * (g.h + 2) * (g.w + 2);
     g.ds = stride == 2;
     // every tensor the convolutions index: x, a1 and the planes of the input's extent, y and id
-    return g.pin * (cin > BK_W ? cin : BK_W) < (1ll << 31) && g.pout * BK_OUT < (1ll << 31);
+    return g.pin * (cin > W ? cin : W) < (1ll << 31) && g.pout * OUT < (1ll << 31);
 }
 
 struct FwdLayout { int64_t a1, a2, id, w1, w2, w3, wd, bias, total; };
@@ -63,55 +72,62 @@ struct BwdLayout { int64_t g3, g2, g1, g3h, g2h, g1h, g3p, g2p, g1p, wt, zero, p
 
 FwdLayout fwd_layout(const Geo& g) {
     FwdLayout L;
+    const int W = g.W, OUT = g.OUT;
     int64_t o = 0;
     auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
-    L.a1 = take(g.pin * BK_W * 2); L.a2 = take(g.pout * BK_W * 2); L.id = take(g.ds ? g.pout * BK_OUT * 2 : 0);
-    L.w1 = take((int64_t)BK_W * g.cin * 2); L.w2 = take((int64_t)BK_W * 9 * BK_W * 2); L.w3 = take((int64_t)BK_OUT * BK_W * 2);
-    L.wd = take(g.ds ? (int64_t)BK_OUT * g.cin * 2 : 0);
-    L.bias = take((2 * BK_W + 2 * BK_OUT) * 4);
+    L.a1 = take(g.pin * W * 2); L.a2 = take(g.pout * W * 2); L.id = take(g.ds ? g.pout * OUT * 2 : 0);
+    L.w1 = take((int64_t)W * g.cin * 2); L.w2 = take((int64_t)W * 9 * W * 2); L.w3 = take((int64_t)OUT * W * 2);
+    L.wd = take(g.ds ? (int64_t)OUT * g.cin * 2 : 0);
+    L.bias = take((2 * W + 2 * OUT) * 4);
     L.total = o;
     return L;
 }
 
 BwdLayout bwd_layout(const Geo& g) {
     BwdLayout L;
+    const int W = g.W, OUT = g.OUT;
     int64_t o = 0;
     auto take = [&](int64_t b) { const int64_t r = o; o += a256(b); return r; };
-    L.g3 = take(g.m * BK_OUT * 4); L.g2 = take(g.m * BK_W * 4); L.g1 = take(g.min * BK_W * 4);
-    L.g3h = take(g.m * BK_OUT * 2); L.g2h = take(g.m * BK_W * 2); L.g1h = take(g.min * BK_W * 2);
-    L.g3p = take(g.pout * BK_OUT * 2);
-    L.g2p = take(g.pin * BK_W * 2);   // stride 1: g2 ring-padded; stride 2: the zero-inserted plane.  Both of the input's extent
-    L.g1p = take(g.pin * BK_W * 2);
-    L.wt = take((int64_t)BK_W * 9 * BK_W * 2);   // the largest transposed panel: conv2's (the downsample's is 1024 x 2048)
-    L.zero = take(BK_OUT * 4);
-    L.part = take((int64_t)BK_MAX_RED * BK_OUT * 8); L.pmax = take(BK_MAX_RED * 4);
-    L.sum3 = take(BK_OUT * 8); L.sum2 = take(BK_W * 8); L.sum1 = take(BK_W * 8);
+    L.g3 = take(g.m * OUT * 4); L.g2 = take(g.m * W * 4); L.g1 = take(g.min * W * 4);
+    L.g3h = take(g.m * OUT * 2); L.g2h = take(g.m * W * 2); L.g1h = take(g.min * W * 2);
+    L.g3p = take(g.pout * OUT * 2);
+    L.g2p = take(g.pin * W * 2);   // stride 1: g2 ring-padded; stride 2: the zero-inserted plane.  Both of the input's extent
+    L.g1p = take(g.pin * W * 2);
+    L.wt = take((int64_t)W * 9 * W * 2);   // the largest transposed panel: conv2's 9 W^2 (the downsample's is 2 W x 4 W)
+    L.zero = take(OUT * 4);
+    L.part = take((int64_t)BK_MAX_RED * OUT * 8); L.pmax = take(BK_MAX_RED * 4);
+    L.sum3 = take(OUT * 8); L.sum2 = take(W * 8); L.sum1 = take(W * 8);
     L.sc = take(3 * 4 * 4);
-    // conv2's slab [512][4608] is the largest of the launches over the output's rows (conv3 [2048][512], the downsample [2048][1024]);
-    // conv1's [512][cin] goes with the input's rows
-    const int64_t so = (int64_t)wg_slabs(g.m) * BK_W * 9 * BK_W, si = (int64_t)wg_slabs(g.min) * BK_W * g.cin;
+    // conv2's slab [W][9 W] is the largest of the launches over the output's rows (conv3 [4 W][W], the downsample [4 W][2 W]);
+    // conv1's [W][cin] goes with the input's rows
+    const int64_t so = (int64_t)wg_slabs(g.m) * W * 9 * W, si = (int64_t)wg_slabs(g.min) * W * g.cin;
     L.slab = take((so > si ? so : si) * 4);
     L.total = o;
     return L;
 }
 
-// v [rows][2048] fp32, act the ring-padded fp16 activation [n][H + 2][Wd + 2][2048]: out = v where act > 0, else 0 (in place when out == v),
-// and over the workgroup's rows m0 .. m1 - 1 in row order the per-channel fp64 sums of out: part[g][2048], pmax[g] = max |out| (NaN kept).
-// Thread t owns channels 4 t .. 4 t + 3 and 1024 + 4 t .. 1024 + 4 t + 3: a wave's 16-byte loads cover 1 KiB of the row.
+// v [rows][OUT] fp32, OUT = 1024 NJ (NJ = 2: res5's 2048-wide gradient, NJ = 1: res4's 1024-wide one), act the ring-padded fp16 activation
+// [n][H + 2][Wd + 2][OUT]: out = v where act > 0, else 0 (in place when out == v), and over the workgroup's rows m0 .. m1 - 1 in row order
+// the per-channel fp64 sums of out: part[g][OUT], pmax[g] = max |out| (NaN kept).
+// Thread t owns channels 1024 j + 4 t .. 1024 j + 4 t + 3 for j < NJ: a wave's 16-byte loads cover 1 KiB of the row.
+template <int NJ>
 __global__ __launch_bounds__(RB_THREADS) void bk_mask_reduce_kernel(const float* v, const half_t* act, int64_t rows, int64_t per, int H, int Wd, float* out,
                                                                     double* part, float* pmax) {
     const int t = threadIdx.x;
     const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
-    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    constexpr int OUT = 1024 * NJ;
+    double s[4 * NJ];
+#pragma unroll
+    for (int k = 0; k < 4 * NJ; ++k) s[k] = 0.0;
     float mx = 0.f;
     const int HW = H * Wd;
     int img = (int)(m0 / HW), rem = (int)(m0 - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
     for (int64_t m = m0; m < m1; ++m) {
-        const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * BK_OUT;
+        const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * OUT;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             const int c = j * 1024 + 4 * t;
-            const floatx4 f = *(const floatx4*)(v + m * BK_OUT + c);
+            const floatx4 f = *(const floatx4*)(v + m * OUT + c);
             const half4 hh = *(const half4*)(a + c);
             floatx4 o;
 #pragma unroll
@@ -121,14 +137,14 @@ __global__ __launch_bounds__(RB_THREADS) void bk_mask_reduce_kernel(const float*
                 const float fa = fabsf(o[e]);
                 mx = fa > mx || fa != fa ? fa : mx;
             }
-            *(floatx4*)(out + m * BK_OUT + c) = o;
+            *(floatx4*)(out + m * OUT + c) = o;
         }
         if (++x == Wd) { x = 0; if (++y == H) { y = 0; ++img; } }
     }
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) part[(int64_t)blockIdx.x * BK_OUT + j * 1024 + 4 * t + e] = s[4 * j + e];
+        for (int e = 0; e < 4; ++e) part[(int64_t)blockIdx.x * OUT + j * 1024 + 4 * t + e] = s[4 * j + e];
     __shared__ float shm[RB_THREADS];
     shm[t] = mx;
     __syncthreads();
@@ -172,17 +188,18 @@ __global__ __launch_bounds__(RB_THREADS) void bk_add_downsample_kernel(float* dx
 }
 
 // the tensors of one struct the block reads: params (five per pair) or grads (the three learnable fields per pair)
-int struct_check(const vtd_bottleneck_params* p, bool ds, bool stats) {
-    if (!p) return BK_ERR_ARG;
+int struct_check(const Fam& fam, const vtd_bottleneck_params* p, bool ds, bool stats) {
+    const int err_arg = fam.err_arg, err_align = fam.err_align;
+    if (!p) return err_arg;
     const float* const f[4][5] = {{p->conv1_w, p->bn1_w, p->bn1_b, p->bn1_mean, p->bn1_var}, {p->conv2_w, p->bn2_w, p->bn2_b, p->bn2_mean, p->bn2_var},
                                   {p->conv3_w, p->bn3_w, p->bn3_b, p->bn3_mean, p->bn3_var}, {p->ds_w, p->ds_bn_w, p->ds_bn_b, p->ds_bn_mean, p->ds_bn_var}};
     uintptr_t bits = 0;
     for (int i = 0; i < (ds ? 4 : 3); ++i)
         for (int j = 0; j < (stats ? 5 : 3); ++j) {
-            if (!f[i][j]) return BK_ERR_ARG;
+            if (!f[i][j]) return err_arg;
             bits |= (uintptr_t)f[i][j];
         }
-    return (bits & 3) ? BK_ERR_ALIGN : 0;
+    return (bits & 3) ? err_align : 0;
 }
 
 void padded_out(ConvParams& c, int h, int w, int ch, half_t* out) {
@@ -191,70 +208,73 @@ void padded_out(ConvParams& c, int h, int w, int ch, half_t* out) {
 
 unsigned ring_blocks(int n, int h, int w, int ch) { return nblk((int64_t)n * (2 * (w + 2) + 2 * h) * (ch / 8)); }
 
-}  // namespace
-
-int64_t vtd_bottleneck_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+int64_t ws_bytes(const Fam& fam, int n, int hin, int win, int cin, int width, int stride, int mode) {
     Geo g;
-    if (!make_geo(n, hin, win, cin, width, stride, g) || mode < 0 || mode > 1) return BK_ERR_ARG;
+    if (!make_geo(fam, n, hin, win, cin, width, stride, g) || mode < 0 || mode > 1) return fam.err_arg;
     return mode ? bwd_layout(g).total : fwd_layout(g).total;
 }
 
-int vtd_launch_bottleneck_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps, void* ws,
-                                  void* y, hipStream_t s) {
+int launch_forward(const Fam& fam, const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps, void* ws,
+                   void* y, hipStream_t s) {
+    const int err_arg = fam.err_arg, err_align = fam.err_align;
     Geo g;
-    if (!x || !ws || !y || !make_geo(n, hin, win, cin, width, stride, g) || !(eps > 0.f)) return BK_ERR_ARG;
-    const int pc = struct_check(P, g.ds, true);
-    if (pc == BK_ERR_ARG) return pc;
-    if (pc || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255)) return BK_ERR_ALIGN;
+    if (!x || !ws || !y || !make_geo(fam, n, hin, win, cin, width, stride, g) || !(eps > 0.f)) return err_arg;
+    const int W = g.W, OUT = g.OUT;
+    const int pc = struct_check(fam, P, g.ds, true);
+    if (pc == err_arg) return pc;
+    if (pc || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255)) return err_align;
     const FwdLayout L = fwd_layout(g);
     char* w = (char*)ws;
     half_t *a1 = (half_t*)(w + L.a1), *a2 = (half_t*)(w + L.a2), *id = (half_t*)(w + L.id), *w1 = (half_t*)(w + L.w1), *w2 = (half_t*)(w + L.w2),
            *w3 = (half_t*)(w + L.w3), *wd = (half_t*)(w + L.wd);
-    float *b1 = (float*)(w + L.bias), *b2 = b1 + BK_W, *b3 = b2 + BK_W, *bd = b3 + BK_OUT;
+    float *b1 = (float*)(w + L.bias), *b2 = b1 + W, *b3 = b2 + W, *bd = b3 + OUT;
     auto fold = [&](const float* cw, const float* gam, const float* bet, const float* mean, const float* var, int cout, int ci, int taps, half_t* wp,
                     float* bias) {
         hipLaunchKernelGGL(rb_fold_kernel, dim3(nblk((int64_t)cout * taps * ci + cout)), dim3(RB_THREADS), 0, s, cw, gam, bet, mean, var, eps, cout, ci, taps,
                            wp, bias);
     };
-    fold(P->conv1_w, P->bn1_w, P->bn1_b, P->bn1_mean, P->bn1_var, BK_W, cin, 1, w1, b1);
-    fold(P->conv2_w, P->bn2_w, P->bn2_b, P->bn2_mean, P->bn2_var, BK_W, BK_W, 9, w2, b2);
-    fold(P->conv3_w, P->bn3_w, P->bn3_b, P->bn3_mean, P->bn3_var, BK_OUT, BK_W, 1, w3, b3);
-    if (g.ds) fold(P->ds_w, P->ds_bn_w, P->ds_bn_b, P->ds_bn_mean, P->ds_bn_var, BK_OUT, cin, 1, wd, bd);
-    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, hin, win, BK_W)), dim3(RB_THREADS), 0, s, a1, n, hin, win, BK_W);
-    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, BK_W)), dim3(RB_THREADS), 0, s, a2, n, g.h, g.w, BK_W);
-    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, BK_OUT)), dim3(RB_THREADS), 0, s, (half_t*)y, n, g.h, g.w, BK_OUT);
+    fold(P->conv1_w, P->bn1_w, P->bn1_b, P->bn1_mean, P->bn1_var, W, cin, 1, w1, b1);
+    fold(P->conv2_w, P->bn2_w, P->bn2_b, P->bn2_mean, P->bn2_var, W, W, 9, w2, b2);
+    fold(P->conv3_w, P->bn3_w, P->bn3_b, P->bn3_mean, P->bn3_var, OUT, W, 1, w3, b3);
+    if (g.ds) fold(P->ds_w, P->ds_bn_w, P->ds_bn_b, P->ds_bn_mean, P->ds_bn_var, OUT, cin, 1, wd, bd);
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, hin, win, W)), dim3(RB_THREADS), 0, s, a1, n, hin, win, W);
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, W)), dim3(RB_THREADS), 0, s, a2, n, g.h, g.w, W);
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, OUT)), dim3(RB_THREADS), 0, s, (half_t*)y, n, g.h, g.w, OUT);
     VTD_HIP_CHECK(hipGetLastError());
     int rc;
-    ConvParams c1 = conv_of(n, hin, win, BK_W, (const half_t*)x, cin, hin, win, 1, 1, w1, b1);
+    ConvParams c1 = conv_of(n, hin, win, W, (const half_t*)x, cin, hin, win, 1, 1, w1, b1);
     c1.flags = EPI_RELU;
-    padded_out(c1, hin, win, BK_W, a1);
+    padded_out(c1, hin, win, W, a1);
     if ((rc = vtd_launch_conv(c1, -1, s))) return rc;
-    ConvParams c2 = conv_of(n, g.h, g.w, BK_W, a1, BK_W, hin, win, 3, stride, w2, b2);
+    ConvParams c2 = conv_of(n, g.h, g.w, W, a1, W, hin, win, 3, stride, w2, b2);
     c2.flags = EPI_RELU;
-    padded_out(c2, g.h, g.w, BK_W, a2);
+    padded_out(c2, g.h, g.w, W, a2);
     if ((rc = vtd_launch_conv(c2, -1, s))) return rc;
     if (g.ds) {
-        ConvParams d = conv_of(n, g.h, g.w, BK_OUT, (const half_t*)x, cin, hin, win, 1, 2, wd, bd);
-        padded_out(d, g.h, g.w, BK_OUT, id);
+        ConvParams d = conv_of(n, g.h, g.w, OUT, (const half_t*)x, cin, hin, win, 1, 2, wd, bd);
+        padded_out(d, g.h, g.w, OUT, id);
         if ((rc = vtd_launch_conv(d, -1, s))) return rc;
     }
-    ConvParams c3 = conv_of(n, g.h, g.w, BK_OUT, a2, BK_W, g.h, g.w, 1, 1, w3, b3);
+    ConvParams c3 = conv_of(n, g.h, g.w, OUT, a2, W, g.h, g.w, 1, 1, w3, b3);
     c3.flags = EPI_RELU | EPI_RESIDUAL;
     c3.res = g.ds ? id : (const half_t*)x; c3.res_hp = g.h + 2; c3.res_wp = g.w + 2; c3.res_ring = 1; c3.res_shift = 0;
-    padded_out(c3, g.h, g.w, BK_OUT, (half_t*)y);
+    padded_out(c3, g.h, g.w, OUT, (half_t*)y);
     return vtd_launch_conv(c3, -1, s);
 }
 
-int vtd_launch_bottleneck_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
-                                   const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
-                                   float* dx, float* dxscale, hipStream_t s) {
+int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch, float* dx,
+                    float* dxscale, hipStream_t s) {
+    const int err_arg = fam.err_arg, err_align = fam.err_align;
     Geo g;
-    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(n, hin, win, cin, width, stride, g) || !(eps > 0.f) || (dx && !dxscale)) return BK_ERR_ARG;
-    const int pc = struct_check(P, g.ds, true), gc = struct_check(Gp, g.ds, false);
-    if (pc == BK_ERR_ARG || gc == BK_ERR_ARG) return BK_ERR_ARG;
+    if (!x || !ws || !y || !dy || !dscale || !scratch || !make_geo(fam, n, hin, win, cin, width, stride, g) || !(eps > 0.f) || (dx && !dxscale))
+        return err_arg;
+    const int W = g.W, OUT = g.OUT;
+    const int pc = struct_check(fam, P, g.ds, true), gc = struct_check(fam, Gp, g.ds, false);
+    if (pc == err_arg || gc == err_arg) return err_arg;
     if (pc || gc || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)ws & 255) || ((uintptr_t)scratch & 255) || ((uintptr_t)dy & 15) || ((uintptr_t)dscale & 7) ||
         ((uintptr_t)dx & 15) || ((uintptr_t)dxscale & 7))
-        return BK_ERR_ALIGN;
+        return err_align;
     const FwdLayout L = fwd_layout(g);
     const BwdLayout B = bwd_layout(g);
     char* q = (char*)scratch;
@@ -280,14 +300,14 @@ int vtd_launch_bottleneck_backward(const void* x, int n, int hin, int win, int c
         hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(RB_THREADS), 0, s, (const double*)part, (const float*)pmax, G, C, in_sc, sum, out_sc);
         hipLaunchKernelGGL(rb_form_kernel, dim3(nblk(rows * (C / 8))), dim3(RB_THREADS), 0, s, gout, rows, (const float*)out_sc, h, w, C, dil, flat, padded);
     };
-    // a 512-wide stage: v masked by the padded activation `act` of h x w pixels (in place when gout == v), reduced, formed
-    auto stage512 = [&](const float* v, const half_t* act, float* gout, int64_t rows, int h, int w, const float* in_sc, double* sum, float* out_sc,
+    // a W-wide stage: v masked by the padded activation `act` of h x w pixels (in place when gout == v), reduced, formed
+    auto stageW = [&](const float* v, const half_t* act, float* gout, int64_t rows, int h, int w, const float* in_sc, double* sum, float* out_sc,
                         half_t* flat, half_t* padded, int dil) {
         int64_t per;
         const int G = red_grid(rows, 256, per);
-        hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(rows * (BK_W / 4))), dim3(RB_THREADS), 0, s, v, act, rows, h, w, BK_W, gout);
-        hipLaunchKernelGGL(rb_reduce_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, BK_W, part, pmax);
-        finish_form(gout, rows, h, w, BK_W, G, in_sc, sum, out_sc, flat, padded, dil);
+        hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(rows * (W / 4))), dim3(RB_THREADS), 0, s, v, act, rows, h, w, W, gout);
+        hipLaunchKernelGGL(rb_reduce_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, W, part, pmax);
+        finish_form(gout, rows, h, w, W, G, in_sc, sum, out_sc, flat, padded, dil);
     };
     // a: [rows][lda] gradients of a convolution of ksz x ksz at stride st over the padded input xin (xc channels, hi x wi pixels) whose output
     // has ho x wo pixels
@@ -311,50 +331,86 @@ int vtd_launch_bottleneck_backward(const void* x, int n, int hin, int win, int c
         return vtd_launch_conv(c, -1, s);
     };
 
-    // the zero bias row of the transposed convolutions: up to 2048 outputs (conv1^T of the identity block)
-    VTD_HIP_CHECK(hipMemsetAsync(zero, 0, BK_OUT * 4, s));
-    {   // g3 = dy (y > 0), 2048 wide
+    // the zero bias row of the transposed convolutions: up to 4 W outputs (conv1^T of the identity block)
+    VTD_HIP_CHECK(hipMemsetAsync(zero, 0, OUT * 4, s));
+    {   // g3 = dy (y > 0), 4 W wide
         int64_t per;
         const int G = red_grid(M, 32, per);
-        hipLaunchKernelGGL(bk_mask_reduce_kernel, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
-        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, BK_OUT)), dim3(RB_THREADS), 0, s, g3p, n, g.h, g.w, BK_OUT);
-        finish_form(g3, M, g.h, g.w, BK_OUT, G, dscale, sum3, sc3, g3h, g3p, 1);
+        if (OUT == 2048)
+            hipLaunchKernelGGL(bk_mask_reduce_kernel<2>, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
+        else
+            hipLaunchKernelGGL(bk_mask_reduce_kernel<1>, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
+        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, OUT)), dim3(RB_THREADS), 0, s, g3p, n, g.h, g.w, OUT);
+        finish_form(g3, M, g.h, g.w, OUT, G, dscale, sum3, sc3, g3h, g3p, 1);
     }
     VTD_HIP_CHECK(hipGetLastError());
-    wgrad(g3h, BK_OUT, M, g.h, g.w, a2, BK_W, g.h, g.w, 1, 1, sc3, sum3, P->conv3_w, P->bn3_w, P->bn3_mean, P->bn3_var, Gp->conv3_w, Gp->bn3_w, Gp->bn3_b);
+    wgrad(g3h, OUT, M, g.h, g.w, a2, W, g.h, g.w, 1, 1, sc3, sum3, P->conv3_w, P->bn3_w, P->bn3_mean, P->bn3_var, Gp->conv3_w, Gp->bn3_w, Gp->bn3_b);
     if (g.ds)
-        wgrad(g3h, BK_OUT, M, g.h, g.w, (const half_t*)x, cin, hin, win, 1, 2, sc3, sum3, P->ds_w, P->ds_bn_w, P->ds_bn_mean, P->ds_bn_var, Gp->ds_w,
+        wgrad(g3h, OUT, M, g.h, g.w, (const half_t*)x, cin, hin, win, 1, 2, sc3, sum3, P->ds_w, P->ds_bn_w, P->ds_bn_mean, P->ds_bn_var, Gp->ds_w,
               Gp->ds_bn_w, Gp->ds_bn_b);
     VTD_HIP_CHECK(hipGetLastError());
     // da2 = conv3^T(g3) into the g2 buffer, masked in place by a2 > 0.  Its padded operand is of the input's extent: the interior for the
     // stride-1 block, the even positions of a zeroed plane for the stride-2 block
-    if ((rc = dgrad(g3p, g.h, g.w, BK_OUT, P->conv3_w, P->bn3_w, P->bn3_var, BK_W, 1, g2))) return rc;
+    if ((rc = dgrad(g3p, g.h, g.w, OUT, P->conv3_w, P->bn3_w, P->bn3_var, W, 1, g2))) return rc;
     if (g.ds)
-        VTD_HIP_CHECK(hipMemsetAsync(g2p, 0, (size_t)g.pin * BK_W * 2, s));
+        VTD_HIP_CHECK(hipMemsetAsync(g2p, 0, (size_t)g.pin * W * 2, s));
     else
-        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, BK_W)), dim3(RB_THREADS), 0, s, g2p, n, g.h, g.w, BK_W);
-    stage512(g2, a2, g2, M, g.h, g.w, sc3, sum2, sc2, g2h, g2p, stride);
-    wgrad(g2h, BK_W, M, g.h, g.w, a1, BK_W, hin, win, 3, stride, sc2, sum2, P->conv2_w, P->bn2_w, P->bn2_mean, P->bn2_var, Gp->conv2_w, Gp->bn2_w, Gp->bn2_b);
+        hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, W)), dim3(RB_THREADS), 0, s, g2p, n, g.h, g.w, W);
+    stageW(g2, a2, g2, M, g.h, g.w, sc3, sum2, sc2, g2h, g2p, stride);
+    wgrad(g2h, W, M, g.h, g.w, a1, W, hin, win, 3, stride, sc2, sum2, P->conv2_w, P->bn2_w, P->bn2_mean, P->bn2_var, Gp->conv2_w, Gp->bn2_w, Gp->bn2_b);
     VTD_HIP_CHECK(hipGetLastError());
     // da1 = conv2^T(g2) at the input's extent into the g1 buffer, masked in place by a1 > 0
-    if ((rc = dgrad(g2p, hin, win, BK_W, P->conv2_w, P->bn2_w, P->bn2_var, BK_W, 3, g1))) return rc;
-    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, hin, win, BK_W)), dim3(RB_THREADS), 0, s, g1p, n, hin, win, BK_W);
-    stage512(g1, a1, g1, Min, hin, win, sc2, sum1, sc1, g1h, g1p, 1);
-    wgrad(g1h, BK_W, Min, hin, win, (const half_t*)x, cin, hin, win, 1, 1, sc1, sum1, P->conv1_w, P->bn1_w, P->bn1_mean, P->bn1_var, Gp->conv1_w, Gp->bn1_w,
+    if ((rc = dgrad(g2p, hin, win, W, P->conv2_w, P->bn2_w, P->bn2_var, W, 3, g1))) return rc;
+    hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, hin, win, W)), dim3(RB_THREADS), 0, s, g1p, n, hin, win, W);
+    stageW(g1, a1, g1, Min, hin, win, sc2, sum1, sc1, g1h, g1p, 1);
+    wgrad(g1h, W, Min, hin, win, (const half_t*)x, cin, hin, win, 1, 1, sc1, sum1, P->conv1_w, P->bn1_w, P->bn1_mean, P->bn1_var, Gp->conv1_w, Gp->bn1_w,
           Gp->bn1_b);
     VTD_HIP_CHECK(hipGetLastError());
     if (dx) {
-        if ((rc = dgrad(g1p, hin, win, BK_W, P->conv1_w, P->bn1_w, P->bn1_var, cin, 1, dx))) return rc;
+        if ((rc = dgrad(g1p, hin, win, W, P->conv1_w, P->bn1_w, P->bn1_var, cin, 1, dx))) return rc;
         if (!g.ds) {
-            hipLaunchKernelGGL(bk_add_identity_kernel, dim3(nblk(M * (BK_OUT / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M * (BK_OUT / 4),
+            hipLaunchKernelGGL(bk_add_identity_kernel, dim3(nblk(M * (OUT / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M * (OUT / 4),
                                (const float*)sc3, (const float*)sc2, (const float*)sc1);
         } else {
             // ds^T(g3) at g3's scale into the g3 buffer (its fp32 values are in the operands by now), then onto the even positions
-            if ((rc = dgrad(g3p, g.h, g.w, BK_OUT, P->ds_w, P->ds_bn_w, P->ds_bn_var, cin, 1, g3))) return rc;
+            if ((rc = dgrad(g3p, g.h, g.w, OUT, P->ds_w, P->ds_bn_w, P->ds_bn_var, cin, 1, g3))) return rc;
             hipLaunchKernelGGL(bk_add_downsample_kernel, dim3(nblk(M * (cin / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M, g.h, g.w, cin,
                                (const float*)sc2, (const float*)sc1);
         }
         hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
     }
     return -(int)hipGetLastError();
+}
+
+}  // namespace
+
+int64_t vtd_bottleneck_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(BK_RES5, n, hin, win, cin, width, stride, mode);
+}
+
+int vtd_launch_bottleneck_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps, void* ws,
+                                  void* y, hipStream_t s) {
+    return launch_forward(BK_RES5, x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+}
+
+int vtd_launch_bottleneck_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                   const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
+                                   float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(BK_RES5, x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+}
+
+// res4 (torchvision's layer3), W = 256: (512 -> 256 -> 1024, stride 2, downsample) and (1024 -> 256 -> 1024, stride 1, identity)
+int64_t vtd_bottleneck256_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(BK_RES4, n, hin, win, cin, width, stride, mode);
+}
+
+int vtd_launch_bottleneck256_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                     void* ws, void* y, hipStream_t s) {
+    return launch_forward(BK_RES4, x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+}
+
+int vtd_launch_bottleneck256_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                      const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
+                                      float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(BK_RES4, x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
 }

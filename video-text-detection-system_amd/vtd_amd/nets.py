@@ -267,26 +267,36 @@ _RES5_BUILT = ("res5 training is built for ResNet-50's last stage: three Bottlen
                "2048 -> 2048 stride 1, twice) on a C4 tap of 1024 channels and even extents, with one BatchNorm eps")
 
 
+# ResNet-50's res4 (torchvision's layer3): the 256-wide Bottlenecks, behind the vtd_bottleneck256_train_* entries of the same file
+_BOTTLENECK256_GEOMETRIES = ((512, 256, 2, True), (1024, 256, 1, False))
+_BOTTLENECK256_BUILT = ("bottleneck256_train is built for the Bottlenecks of ResNet-50's res4 (512 -> 256 -> 1024 stride 2 with downsample and "
+                        "even extents, 1024 -> 256 -> 1024 stride 1), with frozen-statistics BatchNorm")
+_RES4_BUILT = ("res4 training is built for ResNet-50's res4: six Bottlenecks of width 256 (512 -> 1024 stride 2 with downsample, then "
+               "1024 -> 1024 stride 1, five times) on a C3 tap of 512 channels and even extents, with one BatchNorm eps")
+
+
 def _bottleneck_pairs(block):
     return ([(block.conv1, block.bn1), (block.conv2, block.bn2), (block.conv3, block.bn3)] +
             ([(block.downsample[0], block.downsample[1])] if hasattr(block, "downsample") else []))
 
 
-def _bottleneck_check(block):
-    """((cin, width, stride), eps) of a Bottleneck that csrc/bottleneck_train.hip runs, judged without looking at any device."""
+def _bottleneck_check(block, geometries=_BOTTLENECK_GEOMETRIES, built=_BOTTLENECK_BUILT):
+    """((cin, width, stride), eps) of a Bottleneck that csrc/bottleneck_train.hip runs under one entry family (`geometries`: res5's by default,
+    res4's with _BOTTLENECK256_GEOMETRIES), judged without looking at any device."""
     if not isinstance(block, Bottleneck):
-        raise RuntimeError(f"{type(block).__name__}: " + _BOTTLENECK_BUILT + " (a BasicBlock goes to basic_block_train)")
+        raise RuntimeError(f"{type(block).__name__}: " + built + " (a BasicBlock goes to basic_block_train)")
     cin, width = block.conv1.in_channels, block.conv1.out_channels
-    if (cin, width, block.stride, hasattr(block, "downsample")) not in _BOTTLENECK_GEOMETRIES:
-        raise RuntimeError(f"Bottleneck({cin} -> {width} -> {4 * width}, stride {block.stride}): " + _BOTTLENECK_BUILT)
+    if (cin, width, block.stride, hasattr(block, "downsample")) not in geometries:
+        raise RuntimeError(f"Bottleneck({cin} -> {width} -> {4 * width}, stride {block.stride}): " + built)
     if any(bn.eps != block.bn1.eps or not bn.track_running_stats for _, bn in _bottleneck_pairs(block)):
         raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms, with running stats tracked")
     return (cin, width, block.stride), float(block.bn1.eps)
 
 
-def _bottleneck_operands(block, device):
-    """((cin, width, stride), eps, the 9 or 12 learnable tensors, the running statistics) as vtd_bottleneck_train_* take them, validated."""
-    geom, eps = _bottleneck_check(block)
+def _bottleneck_operands(block, device, geometries=_BOTTLENECK_GEOMETRIES, built=_BOTTLENECK_BUILT):
+    """((cin, width, stride), eps, the 9 or 12 learnable tensors, the running statistics) as vtd_bottleneck_train_* (or, with res4's
+    geometries, vtd_bottleneck256_train_*) take them, validated."""
+    geom, eps = _bottleneck_check(block, geometries, built)
     learn, stats = [], []
     for conv, bn in _bottleneck_pairs(block):
         learn += [conv.weight, bn.weight, bn.bias]
@@ -304,7 +314,18 @@ def bottleneck_train(block, x):
     Frozen-statistics BatchNorm -- the running statistics normalise and are never written, whatever ``training`` says.  Returns
     ``[n,2048,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9 learnable tensors and w.r.t. ``x`` at either stride.  Everything else is
     refused before the device is looked at."""
-    (cin, width, stride), eps = _bottleneck_check(block)
+    return _bottleneck_train(block, x, _BOTTLENECK_GEOMETRIES, _BOTTLENECK_BUILT, _BOTTLENECK)
+
+
+def bottleneck256_train(block, x):
+    """bottleneck_train's counterpart for ResNet-50's res4 (the vtd_bottleneck256_train_* entries): 512 -> 256 -> 1024 at stride 2 (with
+    downsample, even extents) or 1024 -> 256 -> 1024 at stride 1.  Returns ``[n,1024,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9
+    learnable tensors and w.r.t. ``x`` at either stride; frozen statistics, never written; the same refusals before the device is looked at."""
+    return _bottleneck_train(block, x, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT, _BOTTLENECK256)
+
+
+def _bottleneck_train(block, x, geometries, built, entry):
+    (cin, width, stride), eps = _bottleneck_check(block, geometries, built)
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != cin:
         raise ValueError(f"Bottleneck input must be a [n,{cin},H,W] tensor")
     n, _, hin, win = x.shape
@@ -312,9 +333,9 @@ def bottleneck_train(block, x):
         raise RuntimeError(f"Bottleneck(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
     if not x.is_cuda:
         raise ValueError("Bottleneck runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
-    _, _, learn, stats = _bottleneck_operands(block, x.device)
+    _, _, learn, stats = _bottleneck_operands(block, x.device, geometries, built)
     src = x if x.requires_grad and torch.is_grad_enabled() else None
-    return _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _BOTTLENECK, None, *learn)
+    return _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), entry, None, *learn)
 
 
 def _res5_operands(layer, tap, device=None):
@@ -343,6 +364,38 @@ def forward_res5_padded(layer, c4_tap):
         x = c4_tap.detach()
         for g, lr, st in zip(geoms, learn, stats):
             x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK)[0]
+        return x
+
+
+def _res4_operands(layer, tap, device=None):
+    """ResNet-50's res4 on a padded C3 tap, as _res5_operands: (the six blocks, their geometries, eps, their learnable tensors, their running
+    statistics), judged on shapes alone."""
+    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
+    if len(blocks) != 6 or not all(isinstance(b, Bottleneck) for b in blocks):
+        raise RuntimeError(_RES4_BUILT)
+    checks = [_bottleneck_check(b, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT) for b in blocks]
+    if not torch.is_tensor(tap) or tap.dim() != 4:
+        raise RuntimeError(_RES4_BUILT)
+    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
+    if ([c[0] for c in checks] != [(512, 256, 2)] + [(1024, 256, 1)] * 5 or tap.shape[3] != 512 or h < 2 or w < 2 or h % 2 or w % 2 or
+            len({c[1] for c in checks}) > 1):
+        raise RuntimeError(_RES4_BUILT)
+    ops = [_bottleneck_operands(b, tap.device if device is None else device, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT) for b in blocks]
+    geoms = [(n, h, w, 512, 256, 2)] + [(n, h // 2, w // 2, 1024, 256, 1)] * 5
+    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_res4_padded(layer, c3_tap):
+    """ResNet-50's res4 (six Bottlenecks of width 256) on a padded C3 tap with the HIP training kernels, no gradient: padded C4
+    [n,h4+2,w4+2,1024] fp16 with a zero ring."""
+    if not torch.is_tensor(c3_tap) or c3_tap.dim() != 4:
+        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+    _, geoms, eps, learn, stats = _res4_operands(layer, c3_tap)
+    _check_padded_taps([c3_tap])
+    with torch.no_grad():
+        x = c3_tap.detach()
+        for g, lr, st in zip(geoms, learn, stats):
+            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK256)[0]
         return x
 
 
@@ -440,8 +493,16 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False,
-                       stem_batch_stats=False, res5=None):
-        """`res5` (ResNet-50's last stage, an nn.Sequential of three Bottlenecks of width 512) goes with a DBHead and the padded taps [C2, C3, C4]
+                       stem_batch_stats=False, res5=None, res4=None):
+        """`res4` (ResNet-50's res4, an nn.Sequential of six Bottlenecks of width 256) goes with `res5`, a DBHead and the padded taps [C2, C3] of
+        256 and 512 channels (further entries are ignored: C4 and C5 are computed here): res4 -> res5 -> FPN -> head as ONE autograd node, res4
+        on the vtd_bottleneck256_train_* entries and res5 on vtd_bottleneck_train_* (csrc/bottleneck_train.hip, frozen-statistics BatchNorm),
+        differentiable w.r.t. res4's fifty-seven learnable tensors, res5's thirty, the FPN's ten and the head's twenty.  C4 is the sixth
+        block's output and C5 the ninth's; the FPN forms dC5 and dC4; res5's first block forms its strided input gradient, which is added to
+        the FPN's dC4 at one power-of-two scale; res4's blocks 5 .. 1 form their input gradients, block 0 forms none (no dC3).  Without
+        `res5`, without a head, or with a ResNet-18 stage argument or batch-statistics flag it raises ValueError.
+
+        `res5` (ResNet-50's last stage, an nn.Sequential of three Bottlenecks of width 512) goes with a DBHead and the padded taps [C2, C3, C4]
         of 256, 512 and 1024 channels (a fourth entry is ignored: C5 is computed here from C4): res5 -> FPN -> head as ONE autograd node on the
         vtd_bottleneck_train_* entries (csrc/bottleneck_train.hip, frozen-statistics BatchNorm), differentiable w.r.t. the stage's thirty
         learnable tensors, the FPN's ten and the head's twenty.  dC5 goes into the last block as the FPN leaves it; blocks 2 and 1 form their
@@ -505,6 +566,16 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
+        if res4 is not None:
+            if res5 is None:
+                raise ValueError("forward_padded(taps, head=head, res4=...) is ResNet-50's res4 -> res5 -> FPN -> head node: it needs res5 too")
+            if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
+                raise ValueError("forward_padded(taps, head=head, res5=..., res4=...) is ResNet-50's res4 -> res5 -> FPN -> head node with "
+                                 "frozen-statistics BatchNorm: it takes no layer1 .. layer4, stem, trunk_batch_stats or stem_batch_stats (those are "
+                                 "ResNet-18's)")
+            if head is None:
+                raise ValueError("forward_padded(taps, res5=..., res4=...) is the training node: it needs the DBHead too")
+            return self._forward_padded_res4(taps, head, res5, res4)
         if res5 is not None:
             if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
                 raise ValueError("forward_padded(taps, head=head, res5=...) is ResNet-50's res5 -> FPN -> head node with frozen-statistics BatchNorm: it "
@@ -562,6 +633,28 @@ class FeaturePyramidNetwork(nn.Module):
         blocks = tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms, learn, stats))
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, 3)
         return self._run_node(head, bns, plan, *(t for lr in learn for t in lr), *params, *hparams)
+
+    def _forward_padded_res4(self, taps, head, res5, res4):
+        """forward_padded(taps, head=head, res5=layer5, res4=layer4): the plan of nine Bottleneck blocks in two stages, (6, 3)."""
+        if not isinstance(taps, (list, tuple)) or len(taps) < 2:
+            raise ValueError("padded taps must be the tensors [C2, C3]")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:2])
+        _check_padded_taps(taps)
+        dev = taps[-1].device
+        _, geoms4, beps, learn4, stats4 = _res4_operands(res4, taps[-1], dev)
+        n, h3, w3 = geoms4[0][:3]
+        c4 = _meta_tap(n, h3 // 2, w3 // 2, 1024)      # res5 is judged on C4's shape (even extents): the tensor itself is computed in the node
+        _, geoms5, beps5, learn5, stats5 = _res5_operands(res5, c4, dev)
+        if beps5 != beps:
+            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of res4 and res5")
+        h, w = geoms5[-1][1:3]
+        geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 1024, h3 // 2, w3 // 2), (n, 2048, h, w)])
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, (6, 3))
+        return self._run_node(head, bns, plan, *(t for lr in learn4 + learn5 for t in lr), *params, *hparams)
 
     def _forward_padded_batch_stem(self, taps, head, layers, stem, trunk_batch_stats, stem_batch_stats):
         """forward_padded(..., stem_batch_stats=True): the whole-backbone node with batch statistics in the stem too."""
@@ -1048,6 +1141,8 @@ _TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two and layer1's one as well
                                          # entries, vtd_stem_bn_train_*, are csrc/stem_train.hip's
 _BOTTLENECK = "vtd_bottleneck_train"     # ResNet-50's last stage: the two Bottleneck geometries of width 512 (csrc/bottleneck_train.hip); the
                                          # block's output has 4 width channels and its struct a third convolution + BatchNorm pair
+_BOTTLENECK256 = "vtd_bottleneck256_train"   # ResNet-50's res4: the two Bottleneck geometries of width 256, the same file and struct
+_BOTTLENECK_FAMILIES = (_BOTTLENECK, _BOTTLENECK256)
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
@@ -1065,10 +1160,10 @@ def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None)
     entry = entry if bn is None or entry in _BN_FAMILIES else _RESBLOCK_BN
     C, _native, lib, ws = _native_workspace(entry + "_workspace_bytes", (*geom, 0), tap.device)
     n, hin, win, cin, width, stride = geom
-    y = torch.empty((n, hin // stride + 2, win // stride + 2, 4 * width if entry == _BOTTLENECK else width), dtype=torch.float16, device=tap.device)
+    y = torch.empty((n, hin // stride + 2, win // stride + 2, 4 * width if entry in _BOTTLENECK_FAMILIES else width), dtype=torch.float16, device=tap.device)
     mode = () if bn is None else (1 if bn[0] else 0, float(bn[1]))
     bstats = () if bn is None else (torch.full((3, 2, width), float("nan"), dtype=torch.float32, device=tap.device),)
-    st = _block_struct(learn, stats, entry == _BOTTLENECK)
+    st = _block_struct(learn, stats, entry in _BOTTLENECK_FAMILIES)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     _native.check(getattr(lib, entry + "_forward")(ptr(tap), *geom, C.byref(st), *mode, eps, ptr(ws), ptr(y), *map(ptr, bstats),
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry + "_forward")
@@ -1084,7 +1179,7 @@ def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx
     grads = [torch.empty_like(p) for p in learn]
     C, _native, lib, scratch = _native_workspace(entry + "_workspace_bytes", (*geom, 1), tap.device)
     n, hin, win, cin, width, stride = geom
-    st, gst = _block_struct(learn, stats, entry == _BOTTLENECK), _block_struct(grads, None, entry == _BOTTLENECK)
+    st, gst = _block_struct(learn, stats, entry in _BOTTLENECK_FAMILIES), _block_struct(grads, None, entry in _BOTTLENECK_FAMILIES)
     dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
     dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
     mode = () if bn is None else (1 if bn[0] else 0,)
@@ -1249,7 +1344,8 @@ class _FPNTrainFn(torch.autograd.Function):
 # BasicBlock from the lowest up (none: the FPN and the head alone) with `beps` their eps,
 # `bn` None or (training, momentum) for blocks on the batch-statistics entries.  _BlockPlan: the block's geometry, its running statistics,
 # its entry family and the count of its learnable tensors (9 with a downsample, 6 without; a Bottleneck's 12 and 9).  `per`: the blocks of
-# each stage of the plan, 2 for ResNet-18's BasicBlock stages and 3 for ResNet-50's res5, the one Bottleneck stage built
+# each stage of the plan, 2 for ResNet-18's BasicBlock stages and 3 for ResNet-50's res5 alone; an int means "every stage", a tuple gives
+# every stage its own count from the lowest up: (6, 3) for ResNet-50's res4 below res5
 _TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn per", defaults=(2,))
 _BlockPlan = namedtuple("_BlockPlan", "geom stats entry nlearn")
 
@@ -1260,15 +1356,23 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
 
     Forward: the stem's launch on the image tap if there is one, then the blocks in order, each on the tap the one before wrote; the last
     tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every stage's last block (every
-    second block; with plan.per = 3, ResNet-50's res5 on the vtd_bottleneck_train_* entries, the third).
+    second block; with plan.per = 3, ResNet-50's res5 on the vtd_bottleneck_train_* entries, the third; with plan.per = (6, 3), res4 on the
+    vtd_bottleneck256_train_* entries below it, the sixth and the ninth).
 
     Backward: head -> FPN -> the blocks from the top down, every gradient handed on as the kernels leave it (NHWC fp32 with its power-of-two
     scale), never through fp16 or an NCHW copy.  The FPN's backward forms dC(k) for the levels the node computes itself (the top
-    len(blocks) / plan.per); dC5 goes into the last block.  Every block but the lowest forms its input gradient (a stage's first block: the strided
+    stages of the plan); dC5 goes into the last block.  Every block but the lowest forms its input gradient (a stage's first block: the strided
     dgrad); where a stage's input is an FPN level too, the first block's dx and the FPN's dC(k) of that level are added at one power-of-two
     scale (vtd_resblock_train_combine) before they go into the stage below.  The lowest block forms a dx only when the stem runs, and that dx
     is the stem's dpool.  The parameter gradients of a block do not depend on whether its dx is formed, so a node gives the bits of the node
     one stage shallower on the taps that stage produces."""
+
+    @staticmethod
+    def _stages(plan):
+        """(the index of every stage's first block, of its last block), from the lowest stage up."""
+        sizes = (plan.per,) * (len(plan.blocks) // plan.per) if isinstance(plan.per, int) else tuple(plan.per)
+        firsts = [sum(sizes[:k]) for k in range(len(sizes))]
+        return firsts, [f + s - 1 for f, s in zip(firsts, sizes)]
 
     @staticmethod
     def _split(plan, params):
@@ -1291,11 +1395,12 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
             x, idx, ctx.sws = _stem_forward_raw(plan.taps[0], sgeom, seps, slearn, sstats, *sbn)
             stem_saved = (x, idx)
         acts, bws = [], []
-        for b, learn in zip(plan.blocks, blearn):      # acts: each block's output; every second one is a C(k)
+        lasts = _TrunkFPNHeadTrainFn._stages(plan)[1]
+        for b, learn in zip(plan.blocks, blearn):      # acts: each block's output; that of every stage's last block is a C(k)
             x, ws = _block_forward_raw(x, b.geom, plan.beps, learn, b.stats, b.entry, plan.bn)[:2]
             acts.append(x)
             bws.append(ws)
-        ftaps = (*plan.taps, *acts[plan.per - 1::plan.per])[-4:]      # C2 .. C5: the last four (an image or pooled tap in front falls out)
+        ftaps = (*plan.taps, *(acts[j] for j in lasts))[-4:]      # C2 .. C5: the last four (an image or pooled tap in front falls out)
         p2p, fws = _fpn_forward_raw(ftaps, plan.geom, fpn_params)
         hws, prob, thresh, stats = _head_forward_raw(p2p, hw, training, momentum, eps, hbuffers, head_params)
         ctx.save_for_backward(p2p, prob, thresh, *stem_saved, *acts, *params)
@@ -1312,8 +1417,9 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
         stem_saved, acts, params = rest[:nstem], rest[nstem:nstem + nb], rest[nstem + nb:]
         slearn, blearn, fpn_params, head_params = _TrunkFPNHeadTrainFn._split(plan, params)
         hgrads, dp2, dscale = _head_backward_raw(p2p, ctx.hw, bool(plan.head[0]), ctx.hws, prob, thresh, head_params, grad_prob, grad_thresh, True)
-        ftaps = (*plan.taps, *acts[plan.per - 1::plan.per])[-4:]
-        stages = nb // plan.per
+        firsts, lasts = _TrunkFPNHeadTrainFn._stages(plan)
+        ftaps = (*plan.taps, *(acts[j] for j in lasts))[-4:]
+        stages = len(firsts)
         fout = _fpn_backward_raw(ftaps, plan.geom, fpn_params, ctx.fws, dp2, dscale, sum(8 >> j for j in range(stages)))      # dC5 down
         if not plan.blocks:
             return (None, *fout, *hgrads)
@@ -1323,9 +1429,10 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
         for i in reversed(range(nb)):
             b, want_dx = plan.blocks[i], i > 0 or plan.stem is not None
             bgrads[i], d, ds = _block_backward_raw(ins[i], b.geom, plan.beps, blearn[i], b.stats, ctx.bws[i], acts[i], d, ds, want_dx, b.entry, plan.bn)
-            level = 3 - stages + i // plan.per      # the FPN level of this block's stage's input: C(2 + level), none below C2
-            if want_dx and i % plan.per == 0 and level >= 0:
-                d, ds = _combine_scaled(d, ds, dtaps[level], scales[level])      # the stage's share of dC(k) + the FPN's
+            if want_dx and i in firsts:
+                level = 3 - stages + firsts.index(i)      # the FPN level of this block's stage's input: C(2 + level), none below C2
+                if level >= 0:
+                    d, ds = _combine_scaled(d, ds, dtaps[level], scales[level])      # the stage's share of dC(k) + the FPN's
         sgrads = ()
         if plan.stem is not None:      # layer1.0's input gradient is the stem's dpool
             sgeom, seps, sstats, *sbn = plan.stem
@@ -1491,6 +1598,9 @@ _STAGE_MODES = ("head+fpn+layer4", "head+fpn+layer4+layer3", "head+fpn+layer4+la
 _BACKBONE_MODE = "head+fpn+backbone"
 # ResNet-50's last stage, res5 (backbone.7: three Bottlenecks), with the FPN and the head; frozen-statistics BatchNorm (ResNet-50 only)
 _RES5_MODE = "head+fpn+res5"
+# one stage further down: res4 (backbone.6: six Bottlenecks of width 256) too, the upper two stages of ResNet-50 with the FPN and the head
+_RES4_MODE = "head+fpn+res5+res4"
+_RES_MODES = (_RES5_MODE, _RES4_MODE)
 
 
 class DBNet(_EngineOwner, nn.Module):
@@ -1550,6 +1660,12 @@ class DBNet(_EngineOwner, nn.Module):
         res5 (csrc/bottleneck_train.hip), the FPN and the head on the HIP training kernels as one autograd node.  res5's BatchNorms normalise
         with their running statistics, which are never written: trunk_bn must be "frozen".
 
+        "head+fpn+res5+res4" (ResNet-50 only; on resnet18 it raises ValueError that names "head+fpn+layer4+layer3"): the usual fine-tuning
+        recipe of a detection trunk on the reference's own backbone -- backbone.0 .. backbone.5 stop requiring grad; backbone.6 (six
+        Bottlenecks of width 256, 57 tensors), backbone.7 (30), fpn (10) and head (20) train: 117 tensors.  A forward in train mode takes C2
+        and C3 from the trunk engine (keyed on the frozen backbone tensors only; its own C4 and C5 are ignored), then runs res4, res5, the
+        FPN and the head on the HIP training kernels as one autograd node.  Frozen statistics only: trunk_bn must be "frozen".
+
         None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
         FPN -- their parameters stop requiring grad, and a forward in train mode runs trunk + FPN on a separate features engine (built
         with fuse_fpn_head=0, rebuilt only when trunk / FPN weights change) and the head on the HIP training kernels, differentiable
@@ -1588,11 +1704,16 @@ class DBNet(_EngineOwner, nn.Module):
             if self.backbone_name != "resnet50":
                 raise ValueError(f"trainable={trainable!r} names ResNet-50's last stage (three Bottlenecks); on {self.backbone_name} the last stage "
                                  "trains with trainable='head+fpn+layer4'")
+        elif trainable == _RES4_MODE:
+            if self.backbone_name != "resnet50":
+                raise ValueError(f"trainable={trainable!r} names ResNet-50's upper two stages (nine Bottlenecks); on {self.backbone_name} the upper "
+                                 "two stages train with trainable='head+fpn+layer4+layer3'")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
-        if trainable == _RES5_MODE and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
-            raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: res5 trains with frozen-statistics BatchNorm only (trunk_bn='frozen'); "
+        if trainable in _RES_MODES and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
+            who = "res5 trains" if trainable == _RES5_MODE else "res4 and res5 train"
+            raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: {who} with frozen-statistics BatchNorm only (trunk_bn='frozen'); "
                              "batch-statistics BatchNorm is not built for Bottleneck blocks")
         if isinstance(bn_mode, (tuple, list)):
             bn_mode = tuple(bn_mode)
@@ -1616,7 +1737,7 @@ class DBNet(_EngineOwner, nn.Module):
         elif trainable == "head+fpn":
             for p in self.backbone.parameters():
                 p.requires_grad_(False)
-        elif trainable in _STAGE_MODES or trainable == _RES5_MODE:
+        elif trainable in _STAGE_MODES or trainable in _RES_MODES:
             first = self._first_trained()
             for i in range(8):
                 for p in self.backbone[i].parameters():
@@ -1632,14 +1753,18 @@ class DBNet(_EngineOwner, nn.Module):
     def _first_trained(self):
         """The first backbone module a stage mode trains: the mode at position k - 1 of _STAGE_MODES trains the top k residual stages,
         backbone.(8 - k) .. backbone.7, over the frozen backbone.0 .. backbone.(7 - k)."""
-        return 7 if self.trainable == _RES5_MODE else 8 - (_STAGE_MODES.index(self.trainable) + 1)
+        if self.trainable in _RES_MODES:      # ResNet-50: res5 alone, or res4 and res5
+            return 7 - _RES_MODES.index(self.trainable)
+        return 8 - (_STAGE_MODES.index(self.trainable) + 1)
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable in (_BACKBONE_MODE, _RES5_MODE):
+        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable in (_BACKBONE_MODE,) + _RES_MODES:
             tensors += list(self.fpn.parameters())
-        if self.trainable == _RES5_MODE:      # backbone.7's 30 parameters and 30 buffers
+        if self.trainable in _RES_MODES:      # backbone.7's 30 parameters and 30 buffers
             tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
+        if self.trainable == _RES4_MODE:      # and backbone.6's 57 and 57
+            tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
         if self.trainable == _BACKBONE_MODE:      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
             for i in (7, 6, 5, 4, 0, 1):
                 tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
@@ -1654,7 +1779,7 @@ class DBNet(_EngineOwner, nn.Module):
         with self._engine_lock:
             # keyed on the backbone tensors' versions only (load_state_dict bumps them): FPN and head updates never rebuild it
             frozen = self.backbone.state_dict()
-            if self.trainable in _STAGE_MODES or self.trainable == _RES5_MODE:
+            if self.trainable in _STAGE_MODES or self.trainable in _RES_MODES:
                 # the frozen tensors only: what the engine computes from the trained stages (stale weights) is never read -- its C5 in the
                 # layer4 mode, C4 and C5 in the layer3 mode, all but C2 in the layer2 mode, all but the pooled stem output in the layer1 mode
                 trained = tuple(f"{i}." for i in range(self._first_trained(), 8))
@@ -1701,12 +1826,14 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE, _RES5_MODE) + _STAGE_MODES:
+        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE) + _RES_MODES + _STAGE_MODES:
             if self.training:
                 if self.trainable == _BACKBONE_MODE:
                     return self._forward_train_backbone(x)
                 if self.trainable == _RES5_MODE:
                     return self._forward_train_res5(x)
+                if self.trainable == _RES4_MODE:
+                    return self._forward_train_res4(x)
                 if self.trainable in _STAGE_MODES:
                     return self._forward_train_trunk(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
@@ -1784,6 +1911,22 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)[:3]   # new tensors per call: autograd may keep them
         out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+    def _forward_train_res4(self, x):
+        """The train-mode forward of "head+fpn+res5+res4": C2 and C3 from the frozen trunk engine (its own C4 and C5 come from the res4 and res5
+        weights it was built with and are ignored), then res4, res5, the FPN and the head as one autograd node."""
+        frozen = [n for i in range(6) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res4 is not implemented; only "
+                               "res4 (backbone.6), res5 (backbone.7), the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. "
+                               "backbone.5)")
+        for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = self.trunk_engine().forward_trunk(x)[:2]   # new tensors per call: autograd may keep them
+        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
