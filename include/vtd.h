@@ -630,7 +630,8 @@ int vtd_recognizer_set_option(vtd_recognizer* r, const char* name, int value);
 int vtd_recognizer_finalize(vtd_recognizer* r, vtd_stream stream);
 /* K6: for every box (frame, x1, y1, x2, y2) take frame[y1:y2, x1:x2] (pipeliine.py:121) out of frames_dev
  * ([n_frames,H,W,3] uint8 BGR) and cv2.resize it to 128x32 (text_recognizer.py:118), then run conv1.  boxes_dev is
- * [ncrops][5] int32 in device memory.  Boxes must lie inside the frame (invalid ones yield a zero crop). */
+ * [ncrops][5] int32 in device memory.  A box must name a frame in [0, n_frames) and lie inside it with x2 > x1, y2 > y1; any
+ * other box yields an all-zero crop and nothing is read for it. */
 int vtd_recognizer_crop_resize(vtd_recognizer* r, const uint8_t* frames_dev, int n_frames, int height, int width,
                                const int32_t* boxes_dev, int ncrops, vtd_stream stream);
 /* Alternative input: the tensor the reference hands to CRNN.forward, [ncrops,3,32,128] float32 (text_recognizer.py:122). */

@@ -36,12 +36,18 @@ def _compare(got, exp):
         assert all(isinstance(v, int) for v in g["bbox"]) and isinstance(g["confidence"], float)
 
 
-@pytest.mark.parametrize("shape,seed", [((720, 1280), 0), ((720, 1280), 101), ((1080, 1920), 1000), ((480, 640), 7)])
+# the last three: portrait 720p (fast pre-process kernel, most LDS rows), portrait 1080p (generic kernel, 7 vertical taps) and a
+# quarter-1080p frame that is shrunk in x and stretched in y; for each the seed is the first from 0 up at which the oracle alone gives a
+# map with margin and at least four boxes (both asserted below)
+@pytest.mark.parametrize("shape,seed", [((720, 1280), 0), ((720, 1280), 101), ((1080, 1920), 1000), ((480, 640), 7),
+                                        ((1280, 720), 0), ((1920, 1080), 0), ((540, 960), 0)])
 def test_detect_single_frame_matches_oracle(det18, shape, seed):
     d, sd = det18
     frame, _ = synth.text_frame(seed, *shape)
+    assert frame.shape == shape + (3,)
     exp, ref_map = opipe.detect(frame, sd, "resnet18", 0.5, return_map=True)
     assert float(np.abs(ref_map - 0.5).min()) > 0.4  # the fixture really has margin
+    assert len(exp) >= 4
     _compare(d.detect(frame, 0.5), exp)
 
 

@@ -1,5 +1,7 @@
 // HBM-bound detector stages for gfx950: fused frame preprocess (K1), NCHW->internal conversion,
 // stem max-pool, and the final ConvTranspose(64->1)+sigmoid of the DB head.
+#include <algorithm>
+
 #include "vtd_common.h"
 
 namespace {
@@ -334,32 +336,60 @@ __global__ void maxpool_kernel(const PoolParams p) {
 
 }  // namespace
 
-int vtd_launch_preprocess(const uint8_t* frames, int n, int H, int W, half_t* out, const int* xb, const int* xk, int ksx,
-                          const int* yb, const int* yk, int ksy, int max_rows, hipStream_t stream) {
-    PreParams p{frames, out, xb, xk, yb, yk, H, W, ksx, ksy, max_rows, 0u};
+// The input rows one workgroup keeps in LDS: the widest span of rows that PRE_TY consecutive output rows touch (yb: [640][2]).
+int vtd_preprocess_max_rows(const int* yb) {
+    int max_rows = 0;
+    for (int oy0 = 0; oy0 < PRE_OUT; oy0 += PRE_TY) {
+        const int last = std::min(oy0 + PRE_TY, PRE_OUT) - 1;
+        max_rows = std::max(max_rows, yb[2 * last] + yb[2 * last + 1] - yb[2 * oy0]);
+    }
+    return max_rows;
+}
+
+// Which kernel serves frames of width W with these tap counts, and the dynamic LDS it is launched with; -1010 where none fits.
+// The one statement of the rule: vtd_launch_preprocess dispatches on it and vtd_preprocess_plan (vtd_api.cpp) reports it.
+//   0  preprocess_fast_kernel<5,5>     720p class: W % 4 == 0, W <= 2048, 5 x 5 taps
+//   1  preprocess_fast_kernel<7,5>     1080p class: the same with 7 horizontal taps
+//   2  preprocess_kernel, 16-byte row loads (W * 3 a multiple of 16)
+//   3  preprocess_kernel, byte loads
+int vtd_preprocess_path(int W, int ksx, int ksy, int max_rows, int* lds_bytes) {
     if ((W & 3) == 0 && W <= 2048 && ksy == 5 && (ksx == 5 || ksx == 7)) {  // 720p / 1080p class sizes: the widened-pixel fast path
         const int lds_fast = (max_rows * PRE_OUT + PRE_CHUNK * (W + ksx) + PRE_TY * (2 + ksy)) * 4 + 3 * 256 * 2;
-        p.quads_magic = (unsigned)(((1ull << 32) + (W / 4) - 1) / (W / 4));
         if (lds_fast <= 160 * 1024) {
-            static bool attr5 = false, attr7 = false;
-            if (ksx == 5) {
-                if (!attr5) {
-                    VTD_HIP_CHECK(hipFuncSetAttribute((const void*)preprocess_fast_kernel<5, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    attr5 = true;
-                }
-                hipLaunchKernelGGL((preprocess_fast_kernel<5, 5>), dim3(PRE_OUT / PRE_TY, n), dim3(PRE_NT), lds_fast, stream, p);
-            } else {
-                if (!attr7) {
-                    VTD_HIP_CHECK(hipFuncSetAttribute((const void*)preprocess_fast_kernel<7, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    attr7 = true;
-                }
-                hipLaunchKernelGGL((preprocess_fast_kernel<7, 5>), dim3(PRE_OUT / PRE_TY, n), dim3(PRE_NT), lds_fast, stream, p);
-            }
-            return -(int)hipGetLastError();
+            *lds_bytes = lds_fast;
+            return ksx == 5 ? 0 : 1;
         }
     }
     const int lds = ((max_rows * PRE_OUT * 3 + 15) & ~15) + PRE_CHUNK * ((W * 3 + 15) & ~15);
     if (lds > 160 * 1024) return -1010;
+    *lds_bytes = lds;
+    return ((W * 3) & 15) == 0 ? 2 : 3;
+}
+
+int vtd_launch_preprocess(const uint8_t* frames, int n, int H, int W, half_t* out, const int* xb, const int* xk, int ksx,
+                          const int* yb, const int* yk, int ksy, int max_rows, hipStream_t stream) {
+    PreParams p{frames, out, xb, xk, yb, yk, H, W, ksx, ksy, max_rows, 0u};
+    int lds = 0;
+    const int path = vtd_preprocess_path(W, ksx, ksy, max_rows, &lds);
+    if (path < 0) return path;
+    if (path <= 1) {
+        p.quads_magic = (unsigned)(((1ull << 32) + (W / 4) - 1) / (W / 4));
+        static bool attr5 = false, attr7 = false;
+        if (path == 0) {
+            if (!attr5) {
+                VTD_HIP_CHECK(hipFuncSetAttribute((const void*)preprocess_fast_kernel<5, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                attr5 = true;
+            }
+            hipLaunchKernelGGL((preprocess_fast_kernel<5, 5>), dim3(PRE_OUT / PRE_TY, n), dim3(PRE_NT), lds, stream, p);
+        } else {
+            if (!attr7) {
+                VTD_HIP_CHECK(hipFuncSetAttribute((const void*)preprocess_fast_kernel<7, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                attr7 = true;
+            }
+            hipLaunchKernelGGL((preprocess_fast_kernel<7, 5>), dim3(PRE_OUT / PRE_TY, n), dim3(PRE_NT), lds, stream, p);
+        }
+        return -(int)hipGetLastError();
+    }
     static bool attr_done = false;
     if (!attr_done) {
         VTD_HIP_CHECK(hipFuncSetAttribute((const void*)preprocess_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -12,12 +12,15 @@ namespace {
 // ------------------------------------------------------------------------------------------------ K6
 // One workgroup per crop.  8-bit bilinear exactly as OpenCV's fixed-point path: 11-bit coefficients,
 // horizontal pass in int, vertical combine ((b0*(h0>>4))>>16 + (b1*(h1>>4))>>16 + 2)>>2; an exact 2x2
-// decimation (256x64 source) takes the area-average route like cv::resize does.
+// decimation (256x64 source) takes the area-average route like cv::resize does.  A box is served only if it names a frame of
+// the batch (0 <= frame < nframes) and lies inside it with a positive extent; any other box gives an all-zero crop and
+// nothing is read for it.  The boxes live on the device, so this is the only check they get.
 struct CropParams {
     const uint8_t* frames;  // [n, H, W, 3] BGR
     const int32_t* boxes;   // [ncrops][5] frame, x1, y1, x2, y2  (crop = frame[y1:y2, x1:x2])
     uint8_t* out;           // [ncrops, 32, 128, 3]
     int H, W, ncrops;
+    int nframes;
 };
 
 __device__ __forceinline__ void linear_coef(int ssize, int dsize, int d, int& ofs, int& c0, int& c1) {
@@ -37,7 +40,7 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropParams p) {
     const int32_t* b = p.boxes + crop * 5;
     const int x1 = b[1], y1 = b[2], sw = b[3] - b[1], sh = b[4] - b[2];
     uint8_t* dst = p.out + (int64_t)crop * 32 * 128 * 3;
-    if (sw <= 0 || sh <= 0 || b[0] < 0 || x1 < 0 || y1 < 0 || b[3] > p.W || b[4] > p.H) {  // never read outside the frame
+    if (sw <= 0 || sh <= 0 || b[0] < 0 || b[0] >= p.nframes || x1 < 0 || y1 < 0 || b[3] > p.W || b[4] > p.H) {  // never read outside the frames
         for (int i = threadIdx.x; i < 32 * 128 * 3; i += 256) dst[i] = 0;
         return;
     }
@@ -333,8 +336,8 @@ __global__ void compact_rows_kernel(const float* __restrict__ in, float* __restr
 
 }  // namespace
 
-int vtd_launch_crop_resize(const uint8_t* frames, int H, int W, const int32_t* boxes, int ncrops, uint8_t* out, hipStream_t s) {
-    CropParams p{frames, boxes, out, H, W, ncrops};
+int vtd_launch_crop_resize(const uint8_t* frames, int nframes, int H, int W, const int32_t* boxes, int ncrops, uint8_t* out, hipStream_t s) {
+    CropParams p{frames, boxes, out, H, W, ncrops, nframes};
     hipLaunchKernelGGL(crop_resize_kernel, dim3(ncrops), dim3(256), 0, s, p);
     return -(int)hipGetLastError();
 }

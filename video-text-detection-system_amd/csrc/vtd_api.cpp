@@ -18,6 +18,8 @@
 // the other kernel launchers (defined in the .hip files)
 int vtd_launch_preprocess(const uint8_t* frames, int n, int H, int W, half_t* out, const int* xb, const int* xk, int ksx,
                           const int* yb, const int* yk, int ksy, int max_rows, hipStream_t stream);
+int vtd_preprocess_max_rows(const int* yb);
+int vtd_preprocess_path(int W, int ksx, int ksy, int max_rows, int* lds_bytes);
 int vtd_launch_nchw_to_input(const float* x, half_t* out, int n, hipStream_t stream);
 int vtd_launch_maxpool(const TensorDesc& in, const TensorDesc& out, int n, int kh, int kw, int sh, int sw, int pad_h, int pad_w,
                        hipStream_t stream);
@@ -28,7 +30,7 @@ void vtd_head_tail_pack_w2(const float* w2, half_t* packed);
 int vtd_launch_head_tail(const TensorDesc& in, const half_t* w1, const float* bias1, const half_t* w2, float b2, float* out, int n,
                          hipStream_t stream);
 
-int vtd_launch_crop_resize(const uint8_t* frames, int H, int W, const int32_t* boxes, int ncrops, uint8_t* out, hipStream_t s);
+int vtd_launch_crop_resize(const uint8_t* frames, int nframes, int H, int W, const int32_t* boxes, int ncrops, uint8_t* out, hipStream_t s);
 int vtd_launch_crnn_conv1(const uint8_t* in_u8, const float* in_f32, const half_t* w, const float* bias, half_t* out, int n, hipStream_t s);
 int vtd_launch_lstm(const half_t* xs, const half_t* whh, half_t* hout, int D, int T, hipStream_t s);
 int vtd_launch_ctc_greedy(const float* logits, int n, int T, int V, int ld, const int32_t* id2char, int blank, int apply_softmax,
@@ -1036,12 +1038,7 @@ static int get_pre_tables(vtd_detector* d, int H, int W, PreTables& out) {
     ResampleAxis ax = pillow_axis(W, 640), ay = pillow_axis(H, 640);
     PreTables t;
     t.ksx = ax.ksize; t.ksy = ay.ksize;
-    int max_rows = 0;
-    for (int oy0 = 0; oy0 < 640; oy0 += 16) {
-        const int last = std::min(oy0 + 16, 640) - 1;
-        max_rows = std::max(max_rows, ay.bounds[2 * last] + ay.bounds[2 * last + 1] - ay.bounds[2 * oy0]);
-    }
-    t.max_rows = max_rows;
+    t.max_rows = vtd_preprocess_max_rows(ay.bounds.data());
     int rc;
     if ((rc = upload(d->arena, ax.bounds.data(), ax.bounds.size() * sizeof(int), (void**)&t.xb))) return rc;
     if ((rc = upload(d->arena, ax.kk.data(), ax.kk.size() * sizeof(int), (void**)&t.xk))) return rc;
@@ -1456,6 +1453,35 @@ int vtd_detector_preprocess(vtd_detector* d, const uint8_t* frames_dev, int n, i
                                  (hipStream_t)stream);
 }
 
+// The frame geometry of the pre-process, readable without a GPU (tests/test_frame_geometry.py; internal, not in include/vtd.h).
+// vtd_preprocess_axis: the tables pillow_axis(in_size, out_size) builds -- *ksize taps per output, bounds [out_size][2] (first input,
+// count), kk [out_size][*ksize] 22-bit coefficients (kk_cap: the ints kk holds).  0, or a negative value on a bad argument or a short
+// buffer.  Sizes up to 65536, many times the largest frame any kernel takes.
+int vtd_preprocess_axis(int in_size, int out_size, int* ksize, int* bounds, int* kk, int kk_cap) {
+    if (in_size <= 0 || out_size <= 0 || in_size > 65536 || out_size > 65536 || !ksize || !bounds || !kk) return ERR_ARG;
+    const ResampleAxis a = pillow_axis(in_size, out_size);
+    if (kk_cap < 0 || (size_t)kk_cap < a.kk.size()) return ERR_CAPACITY;
+    *ksize = a.ksize;
+    std::copy(a.bounds.begin(), a.bounds.end(), bounds);
+    std::copy(a.kk.begin(), a.kk.end(), kk);
+    return 0;
+}
+
+// vtd_preprocess_plan: what vtd_detector_preprocess does with H x W frames -- tap counts, LDS rows per workgroup, the kernel
+// (vtd_preprocess_path's numbering, detector_misc.hip) and its dynamic LDS bytes.  0, -1010 where the launcher refuses the size (the
+// tap counts and rows are still written), or ERR_ARG.
+int vtd_preprocess_plan(int H, int W, int* ksx, int* ksy, int* max_rows, int* path, int* lds_bytes) {
+    if (H <= 0 || W <= 0 || H > 65536 || W > 65536 || !ksx || !ksy || !max_rows || !path || !lds_bytes) return ERR_ARG;
+    const ResampleAxis ax = pillow_axis(W, 640), ay = pillow_axis(H, 640);
+    *ksx = ax.ksize; *ksy = ay.ksize;
+    *max_rows = vtd_preprocess_max_rows(ay.bounds.data());
+    *path = -1; *lds_bytes = 0;
+    const int rc = vtd_preprocess_path(W, *ksx, *ksy, *max_rows, lds_bytes);
+    if (rc < 0) return rc;
+    *path = rc;
+    return 0;
+}
+
 int vtd_detector_set_input_nchw(vtd_detector* d, const float* x_dev, int n, vtd_stream stream) {
     if (!d || !x_dev) return ERR_ARG;
     if (!d->finalized) return ERR_NOT_FINALIZED;
@@ -1831,7 +1857,7 @@ int vtd_recognizer_crop_resize(vtd_recognizer* r, const uint8_t* frames_dev, int
     if (!r || !frames_dev || !boxes_dev || n_frames <= 0 || height <= 0 || width <= 0) return ERR_ARG;
     if (!r->finalized) return ERR_NOT_FINALIZED;
     if (ncrops <= 0 || ncrops > r->max_crops) return ERR_BATCH;
-    int rc = vtd_launch_crop_resize(frames_dev, height, width, boxes_dev, ncrops, r->resized, (hipStream_t)stream);
+    int rc = vtd_launch_crop_resize(frames_dev, n_frames, height, width, boxes_dev, ncrops, r->resized, (hipStream_t)stream);
     if (rc) return rc;
     return vtd_launch_crnn_conv1(r->resized, nullptr, r->w1, r->b1, r->t1.ptr, ncrops, (hipStream_t)stream);
 }
