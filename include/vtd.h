@@ -252,6 +252,10 @@ int vtd_dbhead_unpack_input_grad(const float* dfeats_dev, const float* dscale_de
  * vtd_detector_forward_pool: the detector's ops up to the pooled stem output (what layer1 reads), then a copy of that padded tap,
  * [n][162][162][64] fp16 with a zero ring, into pool_dev (16-byte aligned).  Works on a handle of either "fuse_fpn_head" and either
  * "fuse_stem_pool" setting; -2901 if the tap's ring is not 1, -2903 for a misaligned buffer.
+ * vtd_detector_forward_c2: the detector's ops up to the first residual stage's output (the stem and res2 / layer1; no later stage runs),
+ * then a copy of that padded tap, C2 [n][162][162][c] fp16 (c = 64 for ResNet-18, 256 for ResNet-50), into c2_dev (16-byte aligned): the bits
+ * vtd_detector_forward_trunk writes into its c2_dev.  vtd_detector_forward_trunk's conditions and codes: a handle finalized with
+ * "fuse_fpn_head" = 0 and a C2 tap of ring 1, -2901 otherwise; -2903 for a misaligned buffer.
  * vtd_fpn_train_pack_tap: [n][channels][H][W] NCHW float32 (dtype 0) or fp16 (dtype 1) -> a padded tap, ring included; channels % 64 == 0.
  *
  * Parameters are torch's own tensors as device pointers, float32, contiguous: inner_w[i] / inner_b[i] = fpn.inner_blocks.i
@@ -283,6 +287,7 @@ typedef struct vtd_fpn_params {
 } vtd_fpn_params;
 int vtd_detector_forward_trunk(vtd_detector* d, int n, void* c2_dev, void* c3_dev, void* c4_dev, void* c5_dev, vtd_stream stream);
 int vtd_detector_forward_pool(vtd_detector* d, int n, void* pool_dev, vtd_stream stream);
+int vtd_detector_forward_c2(vtd_detector* d, int n, void* c2_dev, vtd_stream stream);
 int vtd_fpn_train_pack_tap(const void* x_dev, int dtype, int n, int channels, int height, int width, void* tap_dev, vtd_stream stream);
 int64_t vtd_fpn_train_workspace_bytes(int n, int h5, int w5, int c5_channels, int mode);
 int vtd_fpn_train_forward(const void* const* taps, int n, int h5, int w5, int c5_channels, const vtd_fpn_params* params, void* workspace_dev,
@@ -440,6 +445,33 @@ int64_t vtd_bottleneck256_train_workspace_bytes(int n, int h_in, int w_in, int c
 int vtd_bottleneck256_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
                                     float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
 int vtd_bottleneck256_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride,
+                                     const vtd_bottleneck_params* params, float eps, const void* workspace_dev, const void* y_dev,
+                                     const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
+                                     float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
+/* ---- The 128-wide Bottlenecks of ResNet-50's res3 (torchvision's layer2), the same file and host path at W = 128.  Signatures, the
+ * vtd_bottleneck_params struct, tensors, layouts, scales and the "written, not accumulated" rule are those of vtd_bottleneck_train_*:
+ * x_dev [n][h_in+2][w_in+2][cin], y_dev [n][h+2][w+2][512], dy_dev NHWC float32 [n][h][w][512].  Exactly two geometries are accepted,
+ * width 128: (cin 256, stride 2, even h_in and w_in, with downsample: ds_* set) and (cin 512, stride 1, identity: ds_* ignored).  Every
+ * other geometry (widths 256 and 512 included: those are vtd_bottleneck256_train_*'s and vtd_bottleneck_train_*'s), n > 65535, an extent
+ * above 4096 and a tensor of 2^31 elements or more are refused with -3905.
+ * vtd_bottleneck128_train_workspace_bytes: vtd_bottleneck256_train_workspace_bytes's sums at W = 128 (4W = 512), but for the last term of
+ * mode 1, the weight-gradient slabs.  With T(r, w) = min(ceil(512 / w), max(1, ceil(r / 1024))), the slabs of a launch over r rows with w
+ * workgroups per slab (its q-tiles times its 128-column tiles; 512 workgroups when the rows allow slabs of 1024 rows), the term is
+ * a256(4 max(T(M, 9) W 9 W [conv2], T(Min, cin / 128) W cin [conv1], T(M, 4) 4W W [conv3], T(M, 4 cin / 128) 4W cin [the downsample, stride 2
+ * only])): 33.6 MB at n = 32 on a 160 x 160 or 80 x 80 input, where every launch has 512 workgroups.
+ * Fixed orders: the 512-wide gradient g3 = dy (y > 0) is summed per channel by min(256, ceil(M / 32)) workgroups of r = ceil(M / that)
+ * consecutive rows each; in a workgroup threads 0 .. 127 own the 512 channels (four each, one 16-byte load per thread and row) over its first
+ * ceil(r / 2) rows and threads 128 .. 255 over the rest, every half in row order in fp64, then first half + second half, the partials then
+ * in workgroup order; the 128-wide g2 and g1 by min(256, ceil(rows / 256)) workgroups with the same two halves (one channel per thread);
+ * every weight-gradient launch (wgrad_mfma.h MODE 3) cuts ITS rows into T slabs, summed in slab order in fp64.  dx_dev (optional) as
+ * vtd_bottleneck_train_backward's.  No atomics, shape-only grids: bitwise repeatable.  Errors, before any launch: -3905 (a null pointer,
+ * eps <= 0, dx_dev without dxscale_dev, a missing ds_* tensor at stride 2, a mode outside {0, 1}, an unsupported geometry), -3906
+ * (alignment: taps, dy and dx 16 bytes, workspace and scratch 256, scales 8, parameters and gradients 4). */
+int64_t vtd_bottleneck128_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_bottleneck128_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                    float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_bottleneck128_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride,
                                      const vtd_bottleneck_params* params, float eps, const void* workspace_dev, const void* y_dev,
                                      const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
                                      float* dx_dev, float* dxscale_dev, vtd_stream stream);

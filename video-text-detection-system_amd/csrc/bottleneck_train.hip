@@ -1,8 +1,9 @@
 // ResNet Bottleneck (v1.5: the stride sits on the 3x3) training with frozen-statistics BatchNorm (the running statistics normalise and are
-// never written; gamma and beta learn), forward and backward, for the blocks of ResNet-50's upper two stages.  One host path and one set of
-// kernels serve both widths W; each stage has its own C entries and error codes:
+// never written; gamma and beta learn), forward and backward, for the blocks of ResNet-50's upper three stages.  One host path and one set of
+// kernels serve every width W; each stage has its own C entries and error codes:
 //   res5 (torchvision's layer4), W = 512: (1024 -> 512 -> 2048, stride 2, downsample) and (2048 -> 512 -> 2048, stride 1, identity)
 //   res4 (torchvision's layer3), W = 256: (512 -> 256 -> 1024, stride 2, downsample) and (1024 -> 256 -> 1024, stride 1, identity)
+//   res3 (torchvision's layer2), W = 128: (256 -> 128 -> 512, stride 2, downsample) and (512 -> 128 -> 512, stride 1, identity)
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn3(conv3(a2)) + id), a2 = relu(bn2(conv2(a1))), a1 = relu(bn1(conv1(x))),
 // id = x or ds_bn(ds(x)); conv1 1x1 cin -> W, conv2 3x3 at stride s, conv3 1x1 W -> 4 W, ds 1x1 cin = 2 W -> 4 W at stride s.
 //
@@ -17,15 +18,19 @@
 //                    max |.|.  G = min(256, ceil(rows / 32)) workgroups of ceil(rows / G) consecutive rows each, in row order; thread t
 //                    owns channels 1024 j + 4 t .. 1024 j + 4 t + 3 (j < 2 at W = 512, j = 0 at W = 256), so every wave load is 1 KiB of
 //                    one row and a workgroup's loads are the whole row.  rb_finish_kernel adds the partials in workgroup order and gives
-//                    the power-of-two scale
+//                    the power-of-two scale.  W = 128 (4 W = 512 < 1024): bk_mask_reduce512_kernel, the same grid and contract; threads
+//                    0 .. 127 own the row's 512 channels (4 each) over the first ceil(r / 2) of the workgroup's r rows and threads
+//                    128 .. 255 over the rest, so a wave load is still 1 KiB of one row; part = first half + second half (through LDS)
 //   form             rb_form_kernel: the fp16 operands, flat [rows][C] for the weight gradients and ring-padded for the transposed convolutions
 //   g2, g1           the W-wide stages as resblock_train.hip's: rb_mask_kernel, rb_reduce_kernel (min(256, ceil(rows / 256)) workgroups; one
-//                    channel per thread at W = 256, two at 512), finish, form.  g1 lives at the input's extent (conv1 is 1x1 at stride 1
-//                    in front of the strided 3x3)
+//                    channel per thread at W = 256, two at 512; W = 128: rb_reduce128_kernel, two row halves per workgroup), finish, form.
+//                    g1 lives at the input's extent (conv1 is 1x1 at stride 1 in front of the strided 3x3)
 //   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h as it stands: conv3 (lda 4 W: 4 W / 128 column tiles, xc W, 1x1), conv2
 //                    (lda W, xc W, 3x3 at stride s over a1), conv1 (lda W, xc = cin, 1x1, rows = n h_in w_in) and the downsample
 //                    (lda 4 W, xc 2 W, 1x1 at stride 2).  Slabs: min(8, ceil(rows / 4096)) of the LAUNCH's rows -- conv1's are the
-//                    input's, the others' the output's
+//                    input's, the others' the output's.  res3 only (W = 128, where that rule leaves 2 .. 32 workgroups for 256 CUs):
+//                    wg_slabs_tiles, slabs = min(ceil(512 / (q-tiles x column tiles)), ceil(rows / 1024)) -- 512 workgroups when the rows
+//                    allow slabs of 1024 rows; shape-only
 //   param            rb_param_kernel: slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s)
 //   da2              conv3^T(g3): a 1x1 GEMM 4 W -> W on the transposed folded weights (conv_igemm.hip, fp32 output); g2 = da2 (a2 > 0)
 //   da1              conv2^T(g2): the folded weights rotated by 180 degrees and transposed, 3x3 at stride 1.  Stride 2: g2 is written to
@@ -45,7 +50,7 @@ constexpr int BK_MAX_RED = 256;
 
 // an entry family: the Bottleneck width it accepts and its error-code pair
 struct Fam { int width, err_arg, err_align; };
-constexpr Fam BK_RES5 = {512, -3901, -3902}, BK_RES4 = {256, -3903, -3904};
+constexpr Fam BK_RES5 = {512, -3901, -3902}, BK_RES4 = {256, -3903, -3904}, BK_RES3 = {128, -3905, -3906};
 
 struct Geo {
     int n, hin, win, cin, stride, h, w;
@@ -66,6 +71,10 @@ bool make_geo(const Fam& fam, int n, int hin, int win, int cin, int width, int s
     // every tensor the convolutions index: x, a1 and the planes of the input's extent, y and id
     return g.pin * (cin > W ? cin : W) < (1ll << 31) && g.pout * OUT < (1ll << 31);
 }
+
+// the slabs of a weight-gradient launch over `rows` rows with `nqt` q-tiles and lda / 128 column tiles: res5 and res4 by the rows alone, res3
+// (W = 128) by the workgroups the launch would otherwise lack
+int bk_slabs(const Geo& g, int64_t rows, int nqt, int lda) { return g.W == 128 ? wg_slabs_tiles(rows, nqt, lda / 128) : wg_slabs(rows); }
 
 struct FwdLayout { int64_t a1, a2, id, w1, w2, w3, wd, bias, total; };
 struct BwdLayout { int64_t g3, g2, g1, g3h, g2h, g1h, g3p, g2p, g1p, wt, zero, part, pmax, sum3, sum2, sum1, sc, slab, total; };
@@ -100,7 +109,14 @@ BwdLayout bwd_layout(const Geo& g) {
     L.sc = take(3 * 4 * 4);
     // conv2's slab [W][9 W] is the largest of the launches over the output's rows (conv3 [4 W][W], the downsample [4 W][2 W]);
     // conv1's [W][cin] goes with the input's rows
-    const int64_t so = (int64_t)wg_slabs(g.m) * W * 9 * W, si = (int64_t)wg_slabs(g.min) * W * g.cin;
+    int64_t so = (int64_t)wg_slabs(g.m) * W * 9 * W, si = (int64_t)wg_slabs(g.min) * W * g.cin;
+    if (W == 128) {   // per launch: conv2 and conv1, then conv3 and the downsample
+        so = (int64_t)bk_slabs(g, g.m, 9 * W / 128, W) * W * 9 * W;
+        si = (int64_t)bk_slabs(g, g.min, g.cin / 128, W) * W * g.cin;
+        const int64_t s3 = (int64_t)bk_slabs(g, g.m, W / 128, OUT) * OUT * W, sd = g.ds ? (int64_t)bk_slabs(g, g.m, g.cin / 128, OUT) * OUT * g.cin : 0;
+        so = s3 > so ? s3 : so;
+        so = sd > so ? sd : so;
+    }
     L.slab = take((so > si ? so : si) * 4);
     L.total = o;
     return L;
@@ -148,6 +164,54 @@ __global__ __launch_bounds__(RB_THREADS) void bk_mask_reduce_kernel(const float*
     __shared__ float shm[RB_THREADS];
     shm[t] = mx;
     __syncthreads();
+    if (t == 0) {
+        float q = shm[0];
+        for (int k = 1; k < RB_THREADS; ++k) q = shm[k] > q || shm[k] != shm[k] ? shm[k] : q;
+        pmax[blockIdx.x] = q;
+    }
+}
+
+// The 512-wide form (res3, OUT = 512 < 1024): the same contract.  Thread t owns channels 4 (t % 128) .. 4 (t % 128) + 3 over one half of the
+// workgroup's rows m0 .. m1 - 1 in row order, t < 128 the first ceil((m1 - m0) / 2) rows and t >= 128 the rest (rb_reduce128_kernel's split), so
+// a wave's 16-byte loads are still 1 KiB of one row and the two halves stream two rows at a time; part[g][c] = the first half's sum + the second
+// half's (handed over through LDS), fp64; pmax[g] over both halves, NaN kept.
+__global__ __launch_bounds__(RB_THREADS) void bk_mask_reduce512_kernel(const float* v, const half_t* act, int64_t rows, int64_t per, int H, int Wd, float* out,
+                                                                       double* part, float* pmax) {
+    constexpr int OUT = 512;
+    const int t = threadIdx.x, c = 4 * (t & 127), hf = t >> 7;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t mid = m0 + (m1 - m0 + 1) / 2, lo = hf ? mid : m0, hi = hf ? m1 : mid;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    float mx = 0.f;
+    const int HW = H * Wd;
+    int img = (int)(lo / HW), rem = (int)(lo - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    for (int64_t m = lo; m < hi; ++m) {
+        const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * OUT;
+        const floatx4 f = *(const floatx4*)(v + m * OUT + c);
+        const half4 hh = *(const half4*)(a + c);
+        floatx4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o[e] = (float)hh[e] > 0.f ? f[e] : 0.f;
+            s[e] += (double)o[e];
+            const float fa = fabsf(o[e]);
+            mx = fa > mx || fa != fa ? fa : mx;
+        }
+        *(floatx4*)(out + m * OUT + c) = o;
+        if (++x == Wd) { x = 0; if (++y == H) { y = 0; ++img; } }
+    }
+    __shared__ double shs[OUT];
+    __shared__ float shm[RB_THREADS];
+    if (hf) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) shs[c + e] = s[e];
+    }
+    shm[t] = mx;
+    __syncthreads();
+    if (!hf) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[(int64_t)blockIdx.x * OUT + c + e] = s[e] + shs[c + e];
+    }
     if (t == 0) {
         float q = shm[0];
         for (int k = 1; k < RB_THREADS; ++k) q = shm[k] > q || shm[k] != shm[k] ? shm[k] : q;
@@ -306,7 +370,10 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
         int64_t per;
         const int G = red_grid(rows, 256, per);
         hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(rows * (W / 4))), dim3(RB_THREADS), 0, s, v, act, rows, h, w, W, gout);
-        hipLaunchKernelGGL(rb_reduce_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, W, part, pmax);
+        if (W == 128)
+            hipLaunchKernelGGL(rb_reduce128_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, part, pmax);
+        else
+            hipLaunchKernelGGL(rb_reduce_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, W, part, pmax);
         finish_form(gout, rows, h, w, W, G, in_sc, sum, out_sc, flat, padded, dil);
     };
     // a: [rows][lda] gradients of a convolution of ksz x ksz at stride st over the padded input xin (xc channels, hi x wi pixels) whose output
@@ -315,7 +382,7 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
                      const double* sum, const float* w, const float* gam, const float* mean, const float* var, float* dw, float* dgam, float* dbet) {
         WgArgs wa;
         wa.a = a; wa.lda = lda; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = ho; wa.W = wo; wa.rows = rows; wa.slab = slab;
-        const int nqt = ksz * ksz * xc / 128, Sl = wg_slabs(rows);
+        const int nqt = ksz * ksz * xc / 128, Sl = bk_slabs(g, rows, nqt, lda);
         wa.slab_len = slab_rows(rows, Sl); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
         hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, lda / 128), dim3(WG_THREADS), 0, s, wa);
         hipLaunchKernelGGL(rb_param_kernel, dim3(lda), dim3(RB_THREADS), 0, s, (const float*)slab, Sl, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
@@ -338,8 +405,10 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
         const int G = red_grid(M, 32, per);
         if (OUT == 2048)
             hipLaunchKernelGGL(bk_mask_reduce_kernel<2>, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
-        else
+        else if (OUT == 1024)
             hipLaunchKernelGGL(bk_mask_reduce_kernel<1>, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
+        else
+            hipLaunchKernelGGL(bk_mask_reduce512_kernel, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
         hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, OUT)), dim3(RB_THREADS), 0, s, g3p, n, g.h, g.w, OUT);
         finish_form(g3, M, g.h, g.w, OUT, G, dscale, sum3, sc3, g3h, g3p, 1);
     }
@@ -413,4 +482,20 @@ int vtd_launch_bottleneck256_backward(const void* x, int n, int hin, int win, in
                                       const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
                                       float* dx, float* dxscale, hipStream_t s) {
     return launch_backward(BK_RES4, x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+}
+
+// res3 (torchvision's layer2), W = 128: (256 -> 128 -> 512, stride 2, downsample) and (512 -> 128 -> 512, stride 1, identity)
+int64_t vtd_bottleneck128_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(BK_RES3, n, hin, win, cin, width, stride, mode);
+}
+
+int vtd_launch_bottleneck128_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                     void* ws, void* y, hipStream_t s) {
+    return launch_forward(BK_RES3, x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+}
+
+int vtd_launch_bottleneck128_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                      const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
+                                      float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(BK_RES3, x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
 }

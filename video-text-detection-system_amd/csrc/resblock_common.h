@@ -1,7 +1,8 @@
 // What the ResNet block training files share (resblock_train.hip: BasicBlocks with frozen-statistics BatchNorm; resblock_bn_train.hip: batch
 // statistics; bottleneck_train.hip: ResNet-50's Bottlenecks): the padded-tap helpers, the ReLU mask, the identity add, the weight-gradient
 // slab rules, the argument checks and the convolution descriptor; and the kernels of the frozen-statistics path that take every width from
-// their launch: the fold, the reduce's finish, the fp16 operand forming, the dgrad panel and the parameter gradients.
+// their launch: the fold, the reduce's finish, the fp16 operand forming, the dgrad panel and the parameter gradients; and the 128-wide
+// reduce, which ResNet-18's layer2 and ResNet-50's res3 both launch.
 #ifndef VTD_RESBLOCK_COMMON_H
 #define VTD_RESBLOCK_COMMON_H
 #include "vtd_common.h"
@@ -25,6 +26,8 @@ inline int wg_slabs128(int64_t rows, int nqt) {
     const int64_t want = (512 + nqt - 1) / nqt, can = (rows + 1023) / 1024;
     return (int)(want < can ? want : can < 1 ? 1 : can);
 }
+// the same rule with the column tiles counted (ResNet-50's res3, whose 512-wide gradients have four): workgroups = nqt x ctiles x slabs
+inline int wg_slabs_tiles(int64_t rows, int nqt, int ctiles) { return wg_slabs128(rows, nqt * ctiles); }
 inline int wg_nqt(int ksz, int xc) { return (ksz * ksz * xc + 127) / 128; }
 
 // the one-pixel ring of a padded NHWC fp16 tensor of W channels.  One thread = 8 channels of one ring pixel.
@@ -111,6 +114,32 @@ __global__ __launch_bounds__(RB_THREADS) void rb_reduce_kernel(const float* v, i
     __shared__ float shm[RB_THREADS];
     shm[t] = mx;
     __syncthreads();
+    if (t == 0) {
+        float m = shm[0];
+        for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
+        pmax[blockIdx.x] = m;
+    }
+}
+
+// v [rows][128] fp32: thread t owns channel t % 128 over one half of the workgroup's rows m0 .. m1 in row order, t < 128 the first
+// ceil((m1 - m0) / 2) rows and t >= 128 the rest; part[g][c] = the first half's sum + the second half's, fp64; pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce128_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
+    const int t = threadIdx.x, c = t & 127, hf = t >> 7;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t mid = m0 + (m1 - m0 + 1) / 2, lo = hf ? mid : m0, hi = hf ? m1 : mid;
+    double s = 0.0;
+    float mx = 0.f;
+    for (int64_t m = lo; m < hi; ++m) {
+        const float a = v[m * 128 + c], fa = fabsf(a);
+        s += (double)a;
+        mx = fa > mx || fa != fa ? fa : mx;
+    }
+    __shared__ double shs[128];
+    __shared__ float shm[RB_THREADS];
+    if (hf) shs[c] = s;
+    shm[t] = mx;
+    __syncthreads();
+    if (!hf) part[(int64_t)blockIdx.x * 128 + c] = s + shs[c];
     if (t == 0) {
         float m = shm[0];
         for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;

@@ -118,32 +118,6 @@ BwdLayout bwd_layout(const Geo& g, bool strided) {
 }
 
 // ---- backward: what is specific to the BasicBlock's widths -------------------------------------------------------------------------------
-// v [rows][128] fp32: thread t owns channel t % 128 over one half of the workgroup's rows m0 .. m1 in row order, t < 128 the first
-// ceil((m1 - m0) / 2) rows and t >= 128 the rest; part[g][c] = the first half's sum + the second half's, fp64; pmax[g]
-__global__ __launch_bounds__(RB_THREADS) void rb_reduce128_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
-    const int t = threadIdx.x, c = t & 127, hf = t >> 7;
-    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
-    const int64_t mid = m0 + (m1 - m0 + 1) / 2, lo = hf ? mid : m0, hi = hf ? m1 : mid;
-    double s = 0.0;
-    float mx = 0.f;
-    for (int64_t m = lo; m < hi; ++m) {
-        const float a = v[m * 128 + c], fa = fabsf(a);
-        s += (double)a;
-        mx = fa > mx || fa != fa ? fa : mx;
-    }
-    __shared__ double shs[128];
-    __shared__ float shm[RB_THREADS];
-    if (hf) shs[c] = s;
-    shm[t] = mx;
-    __syncthreads();
-    if (!hf) part[(int64_t)blockIdx.x * 128 + c] = s + shs[c];
-    if (t == 0) {
-        float m = shm[0];
-        for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
-        pmax[blockIdx.x] = m;
-    }
-}
-
 // v [rows][64] fp32: thread t owns channel t % 64 over one quarter of the workgroup's rows m0 .. m1 in row order: quarter k = t / 64 takes
 // rows m0 + ceil(k r / 4) .. m0 + ceil((k + 1) r / 4) - 1 of the r = m1 - m0; part[g][c] = (q0 + q1) + (q2 + q3), fp64; pmax[g]
 __global__ __launch_bounds__(RB_THREADS) void rb_reduce64_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {

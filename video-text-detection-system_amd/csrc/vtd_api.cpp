@@ -118,6 +118,12 @@ int vtd_launch_bottleneck256_forward(const void* x, int n, int hin, int win, int
 int vtd_launch_bottleneck256_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
                                       const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
                                       float* dx, float* dxscale, hipStream_t s);
+int64_t vtd_bottleneck128_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_bottleneck128_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                     void* ws, void* y, hipStream_t s);
+int vtd_launch_bottleneck128_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                      const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
+                                      float* dx, float* dxscale, hipStream_t s);
 int vtd_launch_fpn_unpack_tap_grad(const float* g, const float* sc, int n, int channels, int H, int W, float* out, hipStream_t s);
 int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
                                const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
@@ -253,6 +259,7 @@ struct vtd_detector : vtd::ModelBase {
     bool fuse_fpn_head = true;  // compose FPN lateral(C2) + top-down add + P2 smooth + head conv into one classed conv
     bool fuse_downsample = true;  // a downsample block's 1x1 projection rides in the block's last conv as extra K-steps (attach_second_segment)
     size_t pool_ops = 0;  // ops up to and including the one that writes the pooled stem output (vtd_detector_forward_pool)
+    size_t c2_ops = 0;  // ops up to and including the one that writes C2, the first residual stage's output (vtd_detector_forward_c2)
     size_t trunk_ops = 0;  // ops up to and including the last residual stage (vtd_detector_forward_trunk)
     size_t p2_ops = 0;  // unfused graph: ops up to and including the one that writes P2 (vtd_detector_forward_features)
     // optional per-op HIP-event timing (bench / roofline accounting)
@@ -888,6 +895,7 @@ static int build_detector_graph(vtd_detector* d) {
         }
         tapsC[st] = x;
         d->taps["c" + std::to_string(st + 2)] = x;
+        if (st == 0) d->c2_ops = d->ops.size();
     }
     d->trunk_ops = d->ops.size();
 
@@ -1108,6 +1116,9 @@ const char* vtd_strerror(int code) {
         case -3903: return "256-wide Bottleneck training: invalid argument or unsupported geometry (built: width 256 with 512 -> 1024 stride 2, even "
                            "extents and a downsample, or 1024 -> 1024 stride 1: ResNet-50's res4)";
         case -3904: return "256-wide Bottleneck training: misaligned buffer";
+        case -3905: return "128-wide Bottleneck training: invalid argument or unsupported geometry (built: width 128 with 256 -> 512 stride 2, even "
+                           "extents and a downsample, or 512 -> 512 stride 1: ResNet-50's res3)";
+        case -3906: return "128-wide Bottleneck training: misaligned buffer";
         case -3601: return "AdamW step: invalid argument (null or not 4-byte aligned pointer, count < 0, n outside [0, 2^40), non-finite scalar, "
                            "bc2_sqrt <= 0)";
         default: break;
@@ -1270,6 +1281,24 @@ int vtd_bottleneck256_train_backward(const void* x_dev, int n, int h_in, int w_i
                                      const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
                                      float* dx_dev, float* dxscale_dev, vtd_stream stream) {
     return vtd_launch_bottleneck256_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
+                                             scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+// ResNet-50's res3: the two Bottleneck geometries of width 128
+int64_t vtd_bottleneck128_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_bottleneck128_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_bottleneck128_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                    float eps, void* workspace_dev, void* y_dev, vtd_stream stream) {
+    return vtd_launch_bottleneck128_forward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, (hipStream_t)stream);
+}
+
+int vtd_bottleneck128_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride,
+                                     const vtd_bottleneck_params* params, float eps, const void* workspace_dev, const void* y_dev,
+                                     const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
+                                     float* dx_dev, float* dxscale_dev, vtd_stream stream) {
+    return vtd_launch_bottleneck128_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
                                              scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 
@@ -1599,6 +1628,22 @@ int vtd_detector_forward_pool(vtd_detector* d, int n, void* pool_dev, vtd_stream
     if (rc) return rc;
     const TensorDesc& t = it->second;
     VTD_HIP_CHECK(hipMemcpyAsync(pool_dev, t.ptr, (size_t)n * t.hp * t.wp * t.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// the stem and the first residual stage only, then a copy of the n frames' ring-padded C2 ([n][162][162][c] fp16)
+int vtd_detector_forward_c2(vtd_detector* d, int n, void* c2_dev, vtd_stream stream) {
+    if (!d || !c2_dev) return ERR_ARG;
+    if (!d->finalized) return ERR_NOT_FINALIZED;
+    if (n <= 0 || n > d->max_batch) return ERR_BATCH;
+    auto it = d->taps.find("c2");
+    if (d->fuse_fpn_head || !d->c2_ops || it == d->taps.end() || it->second.ring != 1) return -2901;
+    if ((uintptr_t)c2_dev & 15) return -2903;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_detector_ops(d, n, nullptr, nullptr, s, d->c2_ops);
+    if (rc) return rc;
+    const TensorDesc& t = it->second;
+    VTD_HIP_CHECK(hipMemcpyAsync(c2_dev, t.ptr, (size_t)n * t.hp * t.wp * t.c * sizeof(half_t), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

@@ -181,6 +181,10 @@ SIGNATURES = {
     "vtd_bottleneck256_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_bottleneck256_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.POINTER(BottleneckParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck128_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
+    "vtd_bottleneck128_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck128_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.POINTER(BottleneckParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
     "vtd_block64_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -215,6 +219,7 @@ SIGNATURES = {
     "vtd_stem_bn_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StemParams), C.c_void_p, C.c_void_p]),
     "vtd_detector_forward_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtd_detector_forward_c2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_fpn_train_input_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtd_fpn_train_backward_input": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FpnParams), C.c_void_p, C.c_int, C.POINTER(FpnTaps),
                                                C.c_void_p, C.c_void_p]),

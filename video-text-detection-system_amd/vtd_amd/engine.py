@@ -251,6 +251,18 @@ class DetectorEngine(_Tunable):
             del keep
             return tap
 
+    def forward_c2(self, x):
+        """C2 of the input (the first residual stage's output) as a new padded-tap tensor, ring-padded NHWC fp16 [n,162,162,c] with c = 64
+        (ResNet-18) or 256 (ResNet-50): forward_trunk(x)[0]'s bits, but only the stem and that stage run (include/vtd.h
+        vtd_detector_forward_c2).  Needs options fuse_fpn_head=0."""
+        with self.lock:
+            n, keep = self._set_input(x)
+            tap = torch.empty((n, 162, 162, 256 if self.backbone == "resnet50" else 64), dtype=torch.float16, device="cuda")
+            _native.check(self.lib.vtd_detector_forward_c2(self.handle, n, C.c_void_p(tap.data_ptr()), _stream_ptr()),
+                          "vtd_detector_forward_c2")
+            del keep
+            return tap
+
     def read_tap(self, name, n):
         shapes = {"input": (3, 640, 640), "stem": (64, 320, 320), "pool": (64, 160, 160), "p2": (256, 160, 160), "head1": (64, 160, 160),
                   "head2": (64, 320, 320)}

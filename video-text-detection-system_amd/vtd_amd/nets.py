@@ -275,6 +275,14 @@ _RES4_BUILT = ("res4 training is built for ResNet-50's res4: six Bottlenecks of 
                "1024 -> 1024 stride 1, five times) on a C3 tap of 512 channels and even extents, with one BatchNorm eps")
 
 
+# ResNet-50's res3 (torchvision's layer2): the 128-wide Bottlenecks, behind the vtd_bottleneck128_train_* entries of the same file
+_BOTTLENECK128_GEOMETRIES = ((256, 128, 2, True), (512, 128, 1, False))
+_BOTTLENECK128_BUILT = ("bottleneck128_train is built for the Bottlenecks of ResNet-50's res3 (256 -> 128 -> 512 stride 2 with downsample and "
+                        "even extents, 512 -> 128 -> 512 stride 1), with frozen-statistics BatchNorm")
+_RES3_BUILT = ("res3 training is built for ResNet-50's res3: four Bottlenecks of width 128 (256 -> 512 stride 2 with downsample, then "
+               "512 -> 512 stride 1, three times) on a C2 tap of 256 channels and even extents, with one BatchNorm eps")
+
+
 def _bottleneck_pairs(block):
     return ([(block.conv1, block.bn1), (block.conv2, block.bn2), (block.conv3, block.bn3)] +
             ([(block.downsample[0], block.downsample[1])] if hasattr(block, "downsample") else []))
@@ -322,6 +330,13 @@ def bottleneck256_train(block, x):
     downsample, even extents) or 1024 -> 256 -> 1024 at stride 1.  Returns ``[n,1024,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9
     learnable tensors and w.r.t. ``x`` at either stride; frozen statistics, never written; the same refusals before the device is looked at."""
     return _bottleneck_train(block, x, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT, _BOTTLENECK256)
+
+
+def bottleneck128_train(block, x):
+    """bottleneck_train's counterpart for ResNet-50's res3 (the vtd_bottleneck128_train_* entries): 256 -> 128 -> 512 at stride 2 (with
+    downsample, even extents) or 512 -> 128 -> 512 at stride 1.  Returns ``[n,512,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9
+    learnable tensors and w.r.t. ``x`` at either stride; frozen statistics, never written; the same refusals before the device is looked at."""
+    return _bottleneck_train(block, x, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT, _BOTTLENECK128)
 
 
 def _bottleneck_train(block, x, geometries, built, entry):
@@ -396,6 +411,38 @@ def forward_res4_padded(layer, c3_tap):
         x = c3_tap.detach()
         for g, lr, st in zip(geoms, learn, stats):
             x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK256)[0]
+        return x
+
+
+def _res3_operands(layer, tap, device=None):
+    """ResNet-50's res3 on a padded C2 tap, as _res4_operands: (the four blocks, their geometries, eps, their learnable tensors, their running
+    statistics), judged on shapes alone."""
+    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
+    if len(blocks) != 4 or not all(isinstance(b, Bottleneck) for b in blocks):
+        raise RuntimeError(_RES3_BUILT)
+    checks = [_bottleneck_check(b, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT) for b in blocks]
+    if not torch.is_tensor(tap) or tap.dim() != 4:
+        raise RuntimeError(_RES3_BUILT)
+    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
+    if ([c[0] for c in checks] != [(256, 128, 2)] + [(512, 128, 1)] * 3 or tap.shape[3] != 256 or h < 2 or w < 2 or h % 2 or w % 2 or
+            len({c[1] for c in checks}) > 1):
+        raise RuntimeError(_RES3_BUILT)
+    ops = [_bottleneck_operands(b, tap.device if device is None else device, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT) for b in blocks]
+    geoms = [(n, h, w, 256, 128, 2)] + [(n, h // 2, w // 2, 512, 128, 1)] * 3
+    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_res3_padded(layer, c2_tap):
+    """ResNet-50's res3 (four Bottlenecks of width 128) on a padded C2 tap with the HIP training kernels, no gradient: padded C3
+    [n,h3+2,w3+2,512] fp16 with a zero ring."""
+    if not torch.is_tensor(c2_tap) or c2_tap.dim() != 4:
+        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+    _, geoms, eps, learn, stats = _res3_operands(layer, c2_tap)
+    _check_padded_taps([c2_tap])
+    with torch.no_grad():
+        x = c2_tap.detach()
+        for g, lr, st in zip(geoms, learn, stats):
+            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK128)[0]
         return x
 
 
@@ -493,8 +540,17 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False,
-                       stem_batch_stats=False, res5=None, res4=None):
-        """`res4` (ResNet-50's res4, an nn.Sequential of six Bottlenecks of width 256) goes with `res5`, a DBHead and the padded taps [C2, C3] of
+                       stem_batch_stats=False, res5=None, res4=None, res3=None):
+        """`res3` (ResNet-50's res3, an nn.Sequential of four Bottlenecks of width 128) goes with `res4`, `res5`, a DBHead and the padded tap [C2]
+        of 256 channels and extents that are multiples of 8 (further entries are ignored: C3, C4 and C5 are computed here): res3 -> res4 ->
+        res5 -> FPN -> head as ONE autograd node, res3 on the vtd_bottleneck128_train_* entries, differentiable w.r.t. res3's thirty-nine
+        learnable tensors, res4's fifty-seven, res5's thirty, the FPN's ten and the head's twenty.  C3 is the fourth block's output, C4 the
+        tenth's and C5 the thirteenth's; the FPN forms dC5, dC4 and dC3; res5's and res4's first blocks form their strided input gradients,
+        each added to the FPN's gradient of that level once, at one power-of-two scale; res3's blocks 3 .. 1 form their input gradients,
+        block 0 forms none (no dC2).  Without `res4` and `res5`, without a head, or with a ResNet-18 stage argument or batch-statistics flag
+        it raises ValueError.
+
+        `res4` (ResNet-50's res4, an nn.Sequential of six Bottlenecks of width 256) goes with `res5`, a DBHead and the padded taps [C2, C3] of
         256 and 512 channels (further entries are ignored: C4 and C5 are computed here): res4 -> res5 -> FPN -> head as ONE autograd node, res4
         on the vtd_bottleneck256_train_* entries and res5 on vtd_bottleneck_train_* (csrc/bottleneck_train.hip, frozen-statistics BatchNorm),
         differentiable w.r.t. res4's fifty-seven learnable tensors, res5's thirty, the FPN's ten and the head's twenty.  C4 is the sixth
@@ -566,6 +622,17 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
+        if res3 is not None:
+            if res4 is None or res5 is None:
+                raise ValueError("forward_padded(taps, head=head, res3=...) is ResNet-50's res3 -> res4 -> res5 -> FPN -> head node: it needs res4 "
+                                 "and res5 too")
+            if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
+                raise ValueError("forward_padded(taps, head=head, res5=..., res4=..., res3=...) is ResNet-50's res3 -> res4 -> res5 -> FPN -> head "
+                                 "node with frozen-statistics BatchNorm: it takes no layer1 .. layer4, stem, trunk_batch_stats or stem_batch_stats "
+                                 "(those are ResNet-18's)")
+            if head is None:
+                raise ValueError("forward_padded(taps, res5=..., res4=..., res3=...) is the training node: it needs the DBHead too")
+            return self._forward_padded_res3(taps, head, res5, res4, res3)
         if res4 is not None:
             if res5 is None:
                 raise ValueError("forward_padded(taps, head=head, res4=...) is ResNet-50's res4 -> res5 -> FPN -> head node: it needs res5 too")
@@ -655,6 +722,31 @@ class FeaturePyramidNetwork(nn.Module):
                   tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, (6, 3))
         return self._run_node(head, bns, plan, *(t for lr in learn4 + learn5 for t in lr), *params, *hparams)
+
+    def _forward_padded_res3(self, taps, head, res5, res4, res3):
+        """forward_padded(taps, head=head, res5=layer5, res4=layer4, res3=layer3): the plan of thirteen Bottleneck blocks in three stages,
+        (4, 6, 3)."""
+        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
+            raise ValueError("padded taps must be the tensors [C2]")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:1])
+        _check_padded_taps(taps)
+        dev = taps[-1].device
+        _, geoms3, beps, learn3, stats3 = _res3_operands(res3, taps[-1], dev)
+        n, h2, w2 = geoms3[0][:3]
+        # res4 and res5 are judged on the shapes of C3 and C4 (even extents): the tensors themselves are computed in the node
+        _, geoms4, beps4, learn4, stats4 = _res4_operands(res4, _meta_tap(n, h2 // 2, w2 // 2, 512), dev)
+        _, geoms5, beps5, learn5, stats5 = _res5_operands(res5, _meta_tap(n, h2 // 4, w2 // 4, 1024), dev)
+        if beps4 != beps or beps5 != beps:
+            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of res3, res4 and res5")
+        h, w = geoms5[-1][1:3]
+        geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 512, h2 // 2, w2 // 2), (n, 1024, h2 // 4, w2 // 4), (n, 2048, h, w)])
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK128, len(lr)) for g, lr, s in zip(geoms3, learn3, stats3)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, (4, 6, 3))
+        return self._run_node(head, bns, plan, *(t for lr in learn3 + learn4 + learn5 for t in lr), *params, *hparams)
 
     def _forward_padded_batch_stem(self, taps, head, layers, stem, trunk_batch_stats, stem_batch_stats):
         """forward_padded(..., stem_batch_stats=True): the whole-backbone node with batch statistics in the stem too."""
@@ -1142,7 +1234,8 @@ _TRUNK_BN = "vtd_trunk_bn_train"         # layer2's two and layer1's one as well
 _BOTTLENECK = "vtd_bottleneck_train"     # ResNet-50's last stage: the two Bottleneck geometries of width 512 (csrc/bottleneck_train.hip); the
                                          # block's output has 4 width channels and its struct a third convolution + BatchNorm pair
 _BOTTLENECK256 = "vtd_bottleneck256_train"   # ResNet-50's res4: the two Bottleneck geometries of width 256, the same file and struct
-_BOTTLENECK_FAMILIES = (_BOTTLENECK, _BOTTLENECK256)
+_BOTTLENECK128 = "vtd_bottleneck128_train"   # ResNet-50's res3: the two Bottleneck geometries of width 128, the same file and struct
+_BOTTLENECK_FAMILIES = (_BOTTLENECK, _BOTTLENECK256, _BOTTLENECK128)
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
@@ -1345,7 +1438,7 @@ class _FPNTrainFn(torch.autograd.Function):
 # `bn` None or (training, momentum) for blocks on the batch-statistics entries.  _BlockPlan: the block's geometry, its running statistics,
 # its entry family and the count of its learnable tensors (9 with a downsample, 6 without; a Bottleneck's 12 and 9).  `per`: the blocks of
 # each stage of the plan, 2 for ResNet-18's BasicBlock stages and 3 for ResNet-50's res5 alone; an int means "every stage", a tuple gives
-# every stage its own count from the lowest up: (6, 3) for ResNet-50's res4 below res5
+# every stage its own count from the lowest up: (6, 3) for ResNet-50's res4 below res5, (4, 6, 3) with res3 below both
 _TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn per", defaults=(2,))
 _BlockPlan = namedtuple("_BlockPlan", "geom stats entry nlearn")
 
@@ -1357,7 +1450,8 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
     Forward: the stem's launch on the image tap if there is one, then the blocks in order, each on the tap the one before wrote; the last
     tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every stage's last block (every
     second block; with plan.per = 3, ResNet-50's res5 on the vtd_bottleneck_train_* entries, the third; with plan.per = (6, 3), res4 on the
-    vtd_bottleneck256_train_* entries below it, the sixth and the ninth).
+    vtd_bottleneck256_train_* entries below it, the sixth and the ninth; with (4, 6, 3), res3 on the vtd_bottleneck128_train_* entries below
+    both, the fourth, the tenth and the thirteenth).
 
     Backward: head -> FPN -> the blocks from the top down, every gradient handed on as the kernels leave it (NHWC fp32 with its power-of-two
     scale), never through fp16 or an NCHW copy.  The FPN's backward forms dC(k) for the levels the node computes itself (the top
@@ -1600,7 +1694,9 @@ _BACKBONE_MODE = "head+fpn+backbone"
 _RES5_MODE = "head+fpn+res5"
 # one stage further down: res4 (backbone.6: six Bottlenecks of width 256) too, the upper two stages of ResNet-50 with the FPN and the head
 _RES4_MODE = "head+fpn+res5+res4"
-_RES_MODES = (_RES5_MODE, _RES4_MODE)
+# and one more: res3 (backbone.5: four Bottlenecks of width 128); the trunk engine then stops at C2
+_RES3_MODE = "head+fpn+res5+res4+res3"
+_RES_MODES = (_RES5_MODE, _RES4_MODE, _RES3_MODE)
 
 
 class DBNet(_EngineOwner, nn.Module):
@@ -1666,6 +1762,13 @@ class DBNet(_EngineOwner, nn.Module):
         and C3 from the trunk engine (keyed on the frozen backbone tensors only; its own C4 and C5 are ignored), then runs res4, res5, the
         FPN and the head on the HIP training kernels as one autograd node.  Frozen statistics only: trunk_bn must be "frozen".
 
+        "head+fpn+res5+res4+res3" (ResNet-50 only; on resnet18 it raises ValueError that names "head+fpn+layer4+layer3+layer2"): one stage
+        further down -- backbone.0 .. backbone.4 (the stem and res2) stop requiring grad; backbone.5 (four Bottlenecks of width 128, 39
+        tensors), backbone.6 (57), backbone.7 (30), fpn (10) and head (20) train: 156 tensors.  A forward in train mode takes C2 from the
+        trunk engine's forward_c2 (keyed on the frozen backbone tensors only; the engine stops after res2, so no stale C3, C4 or C5 is
+        computed), then runs res3, res4, res5, the FPN and the head on the HIP training kernels as one autograd node.  Frozen statistics only:
+        trunk_bn must be "frozen".
+
         None (default): forward-only on the fused inference engine, as always.  "head": fine-tune the DB head over a frozen trunk and
         FPN -- their parameters stop requiring grad, and a forward in train mode runs trunk + FPN on a separate features engine (built
         with fuse_fpn_head=0, rebuilt only when trunk / FPN weights change) and the head on the HIP training kernels, differentiable
@@ -1708,11 +1811,15 @@ class DBNet(_EngineOwner, nn.Module):
             if self.backbone_name != "resnet50":
                 raise ValueError(f"trainable={trainable!r} names ResNet-50's upper two stages (nine Bottlenecks); on {self.backbone_name} the upper "
                                  "two stages train with trainable='head+fpn+layer4+layer3'")
+        elif trainable == _RES3_MODE:
+            if self.backbone_name != "resnet50":
+                raise ValueError(f"trainable={trainable!r} names ResNet-50's upper three stages (thirteen Bottlenecks); on {self.backbone_name} the "
+                                 "upper three stages train with trainable='head+fpn+layer4+layer3+layer2'")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
         if trainable in _RES_MODES and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
-            who = "res5 trains" if trainable == _RES5_MODE else "res4 and res5 train"
+            who = ("res5 trains", "res4 and res5 train", "res3, res4 and res5 train")[_RES_MODES.index(trainable)]
             raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: {who} with frozen-statistics BatchNorm only (trunk_bn='frozen'); "
                              "batch-statistics BatchNorm is not built for Bottleneck blocks")
         if isinstance(bn_mode, (tuple, list)):
@@ -1753,7 +1860,7 @@ class DBNet(_EngineOwner, nn.Module):
     def _first_trained(self):
         """The first backbone module a stage mode trains: the mode at position k - 1 of _STAGE_MODES trains the top k residual stages,
         backbone.(8 - k) .. backbone.7, over the frozen backbone.0 .. backbone.(7 - k)."""
-        if self.trainable in _RES_MODES:      # ResNet-50: res5 alone, or res4 and res5
+        if self.trainable in _RES_MODES:      # ResNet-50: res5 alone, res4 and res5, or res3, res4 and res5
             return 7 - _RES_MODES.index(self.trainable)
         return 8 - (_STAGE_MODES.index(self.trainable) + 1)
 
@@ -1763,8 +1870,10 @@ class DBNet(_EngineOwner, nn.Module):
             tensors += list(self.fpn.parameters())
         if self.trainable in _RES_MODES:      # backbone.7's 30 parameters and 30 buffers
             tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
-        if self.trainable == _RES4_MODE:      # and backbone.6's 57 and 57
+        if self.trainable in (_RES4_MODE, _RES3_MODE):      # and backbone.6's 57 and 57
             tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
+        if self.trainable == _RES3_MODE:      # and backbone.5's 39 and 39
+            tensors += list(self.backbone[5].parameters()) + list(self.backbone[5].buffers())
         if self.trainable == _BACKBONE_MODE:      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
             for i in (7, 6, 5, 4, 0, 1):
                 tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
@@ -1834,6 +1943,8 @@ class DBNet(_EngineOwner, nn.Module):
                     return self._forward_train_res5(x)
                 if self.trainable == _RES4_MODE:
                     return self._forward_train_res4(x)
+                if self.trainable == _RES3_MODE:
+                    return self._forward_train_res3(x)
                 if self.trainable in _STAGE_MODES:
                     return self._forward_train_trunk(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
@@ -1927,6 +2038,22 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)[:2]   # new tensors per call: autograd may keep them
         out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+    def _forward_train_res3(self, x):
+        """The train-mode forward of "head+fpn+res5+res4+res3": C2 from the frozen trunk engine, which stops there (forward_c2: none of its
+        res3, res4 and res5, built from stale weights, runs), then res3, res4, res5, the FPN and the head as one autograd node."""
+        frozen = [n for i in range(5) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res3 is not implemented; only "
+                               "res3 (backbone.5), res4 (backbone.6), res5 (backbone.7), the FPN and the DB head train (set requires_grad_(False) "
+                               "on backbone.0 .. backbone.4)")
+        for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = [self.trunk_engine().forward_c2(x)]   # a new tensor per call: autograd may keep it
+        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6], res3=self.backbone[5])
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
