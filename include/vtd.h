@@ -476,6 +476,37 @@ int vtd_bottleneck128_train_backward(const void* x_dev, int n, int h_in, int w_i
                                      const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
                                      float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- The 64-wide Bottlenecks of ResNet-50's res2 (torchvision's layer1), the same file and host path at W = 64.  Signatures, the
+ * vtd_bottleneck_params struct, tensors, layouts, scales and the "written, not accumulated" rule are those of vtd_bottleneck_train_*:
+ * x_dev [n][h_in+2][w_in+2][cin], y_dev [n][h+2][w+2][256], dy_dev NHWC float32 [n][h][w][256].  Exactly two geometries are accepted,
+ * width 64, both at stride 1 (h = h_in, w = w_in): (cin 64, with a 1x1 downsample at stride 1: ds_* set) and (cin 256, identity: ds_*
+ * ignored).  Every other geometry (stride 2 and widths 128, 256 and 512 included: those widths are the other three families'), n > 65535,
+ * an extent above 4096 and a tensor of 2^31 elements or more (pin max(cin, W) or pout 4W) are refused with -3907.
+ * vtd_bottleneck64_train_workspace_bytes: vtd_bottleneck256_train_workspace_bytes's sums at W = 64 (4W = 256) with "cin 64" where they say
+ * "stride 2" (id and the downsample's panel exist for the first block), but for the last term of mode 1, the weight-gradient slabs.  With
+ * T(r, w) = min(ceil(512 / w), max(1, ceil(r / 1024))) as vtd_bottleneck128_train_workspace_bytes's, w = the launch's q-tiles (ceil(K / 128))
+ * times its column tiles (one for the 64-wide gradients, two for the 256-wide ones), the term is a256(4 max(T(M, 5) W 9 W [conv2],
+ * T(M, ceil(cin / 128)) W cin [conv1], T(M, 2) 4W W [conv3], T(M, 2) 4W cin [the downsample, cin 64 only])).  At n = 32 on a 160 x 160
+ * input (M = 819 200): workspace 215.1 MB (cin 256) or 645.1 MB (cin 64, with id), scratch 2.55 GB for either, of which the slabs are
+ * 16.8 MB (256 slabs of [64][256] or [256][64], or 512 of [64][64]; conv2 has 103 of [64][576], 15.2 MB): 512 to 515 workgroups a launch.
+ * Fixed orders: the 256-wide gradient g3 = dy (y > 0) is summed per channel by min(256, ceil(M / 32)) workgroups of r = ceil(M / that)
+ * consecutive rows each; in a workgroup threads 64 k .. 64 k + 63 own the 256 channels (four each, one 16-byte load per thread and row) over
+ * quarter k of its rows, rows ceil(k r / 4) .. ceil((k + 1) r / 4) - 1 (15 rows: 4, 4, 4, 3), every quarter in row order in fp64, then
+ * (q0 + q1) + (q2 + q3), the partials then in workgroup order; the 64-wide g2 and g1 by min(256, ceil(rows / 256)) workgroups with the same
+ * four quarters (one channel per thread); conv2 and conv1's weight gradients run on wgrad_mfma.h MODE 5 (the 64-row tile), conv3's and the
+ * downsample's on MODE 4 (64 input channels: half a q-tile), each launch cutting ITS rows into T slabs, summed in slab order in fp64.
+ * dx_dev (optional, with dxscale_dev) is formed for both geometries: conv1^T(g1) plus g3 (cin 256) or the dense ds^T(g3) at every pixel
+ * (cin 64), each summand brought to g1's power-of-two scale before the add.  No atomics, shape-only grids: bitwise repeatable.  Errors,
+ * before any launch: -3907 (a null pointer, eps <= 0, dx_dev without dxscale_dev, a missing ds_* tensor at cin 64, a mode outside {0, 1}, an
+ * unsupported geometry), -3908 (alignment: taps, dy and dx 16 bytes, workspace and scratch 256, scales 8, parameters and gradients 4). */
+int64_t vtd_bottleneck64_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_bottleneck64_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                   float eps, void* workspace_dev, void* y_dev, vtd_stream stream);
+int vtd_bottleneck64_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride,
+                                    const vtd_bottleneck_params* params, float eps, const void* workspace_dev, const void* y_dev,
+                                    const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
+                                    float* dx_dev, float* dxscale_dev, vtd_stream stream);
+
 /* ---- ResNet BasicBlock training with batch-statistics BatchNorm (csrc/resblock_bn_train.hip): the same block as torch's train() mode
  * computes it.  Tensors, layouts, the vtd_basicblock_params struct, the power-of-two gradient scales and the "written, not accumulated" rule
  * are those of vtd_basicblock_train_*.  Two geometries are built, ResNet-18's layer4: (cin 256, width 512, stride 2, even h_in and w_in, with

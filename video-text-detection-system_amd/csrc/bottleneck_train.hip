@@ -1,17 +1,18 @@
 // ResNet Bottleneck (v1.5: the stride sits on the 3x3) training with frozen-statistics BatchNorm (the running statistics normalise and are
-// never written; gamma and beta learn), forward and backward, for the blocks of ResNet-50's upper three stages.  One host path and one set of
+// never written; gamma and beta learn), forward and backward, for the blocks of ResNet-50's four stages.  One host path and one set of
 // kernels serve every width W; each stage has its own C entries and error codes:
 //   res5 (torchvision's layer4), W = 512: (1024 -> 512 -> 2048, stride 2, downsample) and (2048 -> 512 -> 2048, stride 1, identity)
 //   res4 (torchvision's layer3), W = 256: (512 -> 256 -> 1024, stride 2, downsample) and (1024 -> 256 -> 1024, stride 1, identity)
 //   res3 (torchvision's layer2), W = 128: (256 -> 128 -> 512, stride 2, downsample) and (512 -> 128 -> 512, stride 1, identity)
+//   res2 (torchvision's layer1), W = 64: (64 -> 64 -> 256, stride 1, downsample at stride 1) and (256 -> 64 -> 256, stride 1, identity)
 // Tensors are padded taps (ring-padded NHWC fp16, ring 1).  y = relu(bn3(conv3(a2)) + id), a2 = relu(bn2(conv2(a1))), a1 = relu(bn1(conv1(x))),
-// id = x or ds_bn(ds(x)); conv1 1x1 cin -> W, conv2 3x3 at stride s, conv3 1x1 W -> 4 W, ds 1x1 cin = 2 W -> 4 W at stride s.
+// id = x or ds_bn(ds(x)); conv1 1x1 cin -> W, conv2 3x3 at stride s, conv3 1x1 W -> 4 W, ds 1x1 cin = 2 W (res2: W) -> 4 W at stride s.
 //
 // Forward:
 //   fold             per convolution (rb_fold_kernel): w gamma rstd -> fp16 GEMM panel [cout][ksz^2 cin] (k = tap * cin + ci), bias = beta -
 //                    mean gamma rstd; on the device, every call
 //   conv x 3 or 4    conv_igemm.hip: conv1 (ReLU) -> padded a1 at the INPUT's extent; conv2 (stride s, ReLU) -> padded a2; downsample
-//                    (stride 2) -> padded id; conv3 (EPI_RESIDUAL from id or x, ReLU) -> padded y.  a1, a2 and id stay in the workspace
+//                    (the block's stride) -> padded id; conv3 (EPI_RESIDUAL from id or x, ReLU) -> padded y.  a1, a2 and id stay in the workspace
 // Backward from dy (NHWC fp32 [n h w][4 W] times a power of two):
 //   mask + reduce    bk_mask_reduce_kernel<4 W / 1024>, one pass over the 4 W-wide gradient: g3 = dy (y > 0) in fp32 (the gradient at bn3's
 //                    output, of the downsample's BatchNorm output, and of an identity input) with its per-channel fp64 partial sums and
@@ -20,17 +21,23 @@
 //                    one row and a workgroup's loads are the whole row.  rb_finish_kernel adds the partials in workgroup order and gives
 //                    the power-of-two scale.  W = 128 (4 W = 512 < 1024): bk_mask_reduce512_kernel, the same grid and contract; threads
 //                    0 .. 127 own the row's 512 channels (4 each) over the first ceil(r / 2) of the workgroup's r rows and threads
-//                    128 .. 255 over the rest, so a wave load is still 1 KiB of one row; part = first half + second half (through LDS)
+//                    128 .. 255 over the rest, so a wave load is still 1 KiB of one row; part = first half + second half (through LDS).
+//                    W = 64 (4 W = 256): bk_mask_reduce256_kernel, the same again in four row quarters of 64 threads each, split as
+//                    rb_reduce64_kernel splits them (15 rows -> 4, 4, 4, 3); part = (q0 + q1) + (q2 + q3)
 //   form             rb_form_kernel: the fp16 operands, flat [rows][C] for the weight gradients and ring-padded for the transposed convolutions
 //   g2, g1           the W-wide stages as resblock_train.hip's: rb_mask_kernel, rb_reduce_kernel (min(256, ceil(rows / 256)) workgroups; one
-//                    channel per thread at W = 256, two at 512; W = 128: rb_reduce128_kernel, two row halves per workgroup), finish, form.
+//                    channel per thread at W = 256, two at 512; W = 128: rb_reduce128_kernel, two row halves per workgroup; W = 64:
+//                    rb_reduce64_kernel, four row quarters), finish, form.
 //                    g1 lives at the input's extent (conv1 is 1x1 at stride 1 in front of the strided 3x3)
 //   wgrad<3>         G[c][k] = sum_m g[m][c] x[m][k] on wgrad_mfma.h as it stands: conv3 (lda 4 W: 4 W / 128 column tiles, xc W, 1x1), conv2
 //                    (lda W, xc W, 3x3 at stride s over a1), conv1 (lda W, xc = cin, 1x1, rows = n h_in w_in) and the downsample
 //                    (lda 4 W, xc 2 W, 1x1 at stride 2).  Slabs: min(8, ceil(rows / 4096)) of the LAUNCH's rows -- conv1's are the
 //                    input's, the others' the output's.  res3 only (W = 128, where that rule leaves 2 .. 32 workgroups for 256 CUs):
 //                    wg_slabs_tiles, slabs = min(ceil(512 / (q-tiles x column tiles)), ceil(rows / 1024)) -- 512 workgroups when the rows
-//                    allow slabs of 1024 rows; shape-only
+//                    allow slabs of 1024 rows; shape-only.  res2 (W = 64) takes the same rule on the other two modes of wgrad_mfma.h:
+//                    conv2 and conv1 (lda 64) on MODE 5, the 64-row tile with one column tile, slab [64][ksz^2 xc] (conv2: K = 576, 5
+//                    q-tiles; conv1: xc = 256 or 64, 2 or 1); conv3 and the downsample (lda 256, xc 64, 1x1) on MODE 4, two column
+//                    tiles and half a q-tile.  rb_param_kernel's grid is lda, so its slab stride is the launch's either way
 //   param            rb_param_kernel: slabs summed in order in fp64; dW = gamma rstd G, dbeta = s, dgamma = rstd (sum_k w G - mean s)
 //   da2              conv3^T(g3): a 1x1 GEMM 4 W -> W on the transposed folded weights (conv_igemm.hip, fp32 output); g2 = da2 (a2 > 0)
 //   da1              conv2^T(g2): the folded weights rotated by 180 degrees and transposed, 3x3 at stride 1.  Stride 2: g2 is written to
@@ -38,7 +45,8 @@
 //                    path -- the form resblock_train.hip documents.  g1 = da1 (a1 > 0)
 //   dx (optional)    conv1^T(g1), a 1x1 GEMM W -> cin at g1's total scale; plus, stride 1, g3 times the product of the three stages'
 //                    power-of-two multipliers; or, stride 2, ds^T(g3) (a 1x1 GEMM 4 W -> 2 W at g3's scale) times the product of the
-//                    two lower stages' multipliers at the even (row, column) positions
+//                    two lower stages' multipliers at the even (row, column) positions; or, res2.0 (downsample at stride 1), the same
+//                    ds^T(g3) (4 W -> W) times the same product at every pixel (rb_add_identity_kernel's dense sum)
 // No atomics, shape-only grids, fixed summation orders: bitwise repeatable.
 #include "resblock_common.h"
 
@@ -50,31 +58,35 @@ constexpr int BK_MAX_RED = 256;
 
 // an entry family: the Bottleneck width it accepts and its error-code pair
 struct Fam { int width, err_arg, err_align; };
-constexpr Fam BK_RES5 = {512, -3901, -3902}, BK_RES4 = {256, -3903, -3904}, BK_RES3 = {128, -3905, -3906};
+constexpr Fam BK_RES5 = {512, -3901, -3902}, BK_RES4 = {256, -3903, -3904}, BK_RES3 = {128, -3905, -3906}, BK_RES2 = {64, -3907, -3908};
 
 struct Geo {
     int n, hin, win, cin, stride, h, w;
     int W, OUT;                  // the Bottleneck width and 4 W
     int64_t m, min, pin, pout;   // output rows, input rows, padded pixels of the input's and the output's extent
-    bool ds;
+    bool ds;                     // the block has a downsample (1x1 at the block's stride): a stage's first block
 };
 
 bool make_geo(const Fam& fam, int n, int hin, int win, int cin, int width, int stride, Geo& g) {
     const int W = fam.width, OUT = 4 * W;
     if (n <= 0 || hin <= 0 || win <= 0 || n > 65535 || hin > 4096 || win > 4096 || width != W) return false;
-    if (!((cin == 2 * W && stride == 2 && !(hin & 1) && !(win & 1)) || (cin == OUT && stride == 1))) return false;
+    // a stage's first block: res3 .. res5 halve the extent from 2 W channels; res2 (W = 64) follows the max-pool at stride 1 from W channels
+    const bool first = W == 64 ? cin == W && stride == 1 : cin == 2 * W && stride == 2 && !(hin & 1) && !(win & 1);
+    if (!(first || (cin == OUT && stride == 1))) return false;
     g.W = W; g.OUT = OUT;
     g.n = n; g.hin = hin; g.win = win; g.cin = cin; g.stride = stride; g.h = hin / stride; g.w = win / stride;
     g.m = (int64_t)n * g.h * g.w; g.min = (int64_t)n * hin * win;
     g.pin = (int64_t)n * (hin + 2) * (win + 2); g.pout = (int64_t)n * (g.h + 2) * (g.w + 2);
-    g.ds = stride == 2;
+    g.ds = first;
     // every tensor the convolutions index: x, a1 and the planes of the input's extent, y and id
     return g.pin * (cin > W ? cin : W) < (1ll << 31) && g.pout * OUT < (1ll << 31);
 }
 
-// the slabs of a weight-gradient launch over `rows` rows with `nqt` q-tiles and lda / 128 column tiles: res5 and res4 by the rows alone, res3
-// (W = 128) by the workgroups the launch would otherwise lack
-int bk_slabs(const Geo& g, int64_t rows, int nqt, int lda) { return g.W == 128 ? wg_slabs_tiles(rows, nqt, lda / 128) : wg_slabs(rows); }
+// the slabs of a weight-gradient launch over `rows` rows with `nqt` q-tiles and lda / 128 column tiles (one for the 64-row tile of a 64-wide
+// gradient): res5 and res4 by the rows alone, res3 and res2 (W <= 128) by the workgroups the launch would otherwise lack
+int bk_slabs(const Geo& g, int64_t rows, int nqt, int lda) {
+    return g.W <= 128 ? wg_slabs_tiles(rows, nqt, lda < 128 ? 1 : lda / 128) : wg_slabs(rows);
+}
 
 struct FwdLayout { int64_t a1, a2, id, w1, w2, w3, wd, bias, total; };
 struct BwdLayout { int64_t g3, g2, g1, g3h, g2h, g1h, g3p, g2p, g1p, wt, zero, part, pmax, sum3, sum2, sum1, sc, slab, total; };
@@ -110,10 +122,11 @@ BwdLayout bwd_layout(const Geo& g) {
     // conv2's slab [W][9 W] is the largest of the launches over the output's rows (conv3 [4 W][W], the downsample [4 W][2 W]);
     // conv1's [W][cin] goes with the input's rows
     int64_t so = (int64_t)wg_slabs(g.m) * W * 9 * W, si = (int64_t)wg_slabs(g.min) * W * g.cin;
-    if (W == 128) {   // per launch: conv2 and conv1, then conv3 and the downsample
-        so = (int64_t)bk_slabs(g, g.m, 9 * W / 128, W) * W * 9 * W;
-        si = (int64_t)bk_slabs(g, g.min, g.cin / 128, W) * W * g.cin;
-        const int64_t s3 = (int64_t)bk_slabs(g, g.m, W / 128, OUT) * OUT * W, sd = g.ds ? (int64_t)bk_slabs(g, g.m, g.cin / 128, OUT) * OUT * g.cin : 0;
+    if (W <= 128) {   // per launch: conv2 and conv1, then conv3 and the downsample
+        so = (int64_t)bk_slabs(g, g.m, wg_nqt(3, W), W) * W * 9 * W;
+        si = (int64_t)bk_slabs(g, g.min, wg_nqt(1, g.cin), W) * W * g.cin;
+        const int64_t s3 = (int64_t)bk_slabs(g, g.m, wg_nqt(1, W), OUT) * OUT * W,
+                      sd = g.ds ? (int64_t)bk_slabs(g, g.m, wg_nqt(1, g.cin), OUT) * OUT * g.cin : 0;
         so = s3 > so ? s3 : so;
         so = sd > so ? sd : so;
     }
@@ -219,6 +232,52 @@ __global__ __launch_bounds__(RB_THREADS) void bk_mask_reduce512_kernel(const flo
     }
 }
 
+// The 256-wide form (res2, OUT = 256): the same contract.  Thread t owns channels 4 (t % 64) .. 4 (t % 64) + 3 over one quarter of the
+// workgroup's r = m1 - m0 rows in row order: quarter k = t / 64 takes rows m0 + ceil(k r / 4) .. m0 + ceil((k + 1) r / 4) - 1
+// (rb_reduce64_kernel's split: 15 rows -> 4, 4, 4, 3), so a wave's 16-byte loads are still 1 KiB of one row and the four quarters stream four
+// rows at a time; part[g][c] = (q0 + q1) + (q2 + q3) (handed over through LDS), fp64; pmax[g] over all four, NaN kept.
+__global__ __launch_bounds__(RB_THREADS) void bk_mask_reduce256_kernel(const float* v, const half_t* act, int64_t rows, int64_t per, int H, int Wd, float* out,
+                                                                       double* part, float* pmax) {
+    constexpr int OUT = 256;
+    const int t = threadIdx.x, c = 4 * (t & 63), k = t >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t r = m1 - m0, lo = m0 + (k * r + 3) / 4, hi = m0 + ((k + 1) * r + 3) / 4;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    float mx = 0.f;
+    const int HW = H * Wd;
+    int img = (int)(lo / HW), rem = (int)(lo - (int64_t)img * HW), y = rem / Wd, x = rem - y * Wd;
+    for (int64_t m = lo; m < hi; ++m) {
+        const half_t* a = act + (((int64_t)img * (H + 2) + y + 1) * (Wd + 2) + x + 1) * OUT;
+        const floatx4 f = *(const floatx4*)(v + m * OUT + c);
+        const half4 hh = *(const half4*)(a + c);
+        floatx4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o[e] = (float)hh[e] > 0.f ? f[e] : 0.f;
+            s[e] += (double)o[e];
+            const float fa = fabsf(o[e]);
+            mx = fa > mx || fa != fa ? fa : mx;
+        }
+        *(floatx4*)(out + m * OUT + c) = o;
+        if (++x == Wd) { x = 0; if (++y == H) { y = 0; ++img; } }
+    }
+    __shared__ double shs[4][OUT];
+    __shared__ float shm[RB_THREADS];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) shs[k][c + e] = s[e];
+    shm[t] = mx;
+    __syncthreads();
+    if (k == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[(int64_t)blockIdx.x * OUT + c + e] = (shs[0][c + e] + shs[1][c + e]) + (shs[2][c + e] + shs[3][c + e]);
+    }
+    if (t == 0) {
+        float q = shm[0];
+        for (int j = 1; j < RB_THREADS; ++j) q = shm[j] > q || shm[j] != shm[j] ? shm[j] : q;
+        pmax[blockIdx.x] = q;
+    }
+}
+
 // stride 1: dx [items4 x 4] (at g1's total scale) += g3 (at the incoming scale) times the three stages' multipliers, powers of two
 __global__ __launch_bounds__(RB_THREADS) void bk_add_identity_kernel(float* dx, const float* g3, int64_t items4, const float* sc3, const float* sc2,
                                                                      const float* sc1) {
@@ -315,7 +374,7 @@ int launch_forward(const Fam& fam, const void* x, int n, int hin, int win, int c
     padded_out(c2, g.h, g.w, W, a2);
     if ((rc = vtd_launch_conv(c2, -1, s))) return rc;
     if (g.ds) {
-        ConvParams d = conv_of(n, g.h, g.w, OUT, (const half_t*)x, cin, hin, win, 1, 2, wd, bd);
+        ConvParams d = conv_of(n, g.h, g.w, OUT, (const half_t*)x, cin, hin, win, 1, stride, wd, bd);
         padded_out(d, g.h, g.w, OUT, id);
         if ((rc = vtd_launch_conv(d, -1, s))) return rc;
     }
@@ -370,7 +429,9 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
         int64_t per;
         const int G = red_grid(rows, 256, per);
         hipLaunchKernelGGL(rb_mask_kernel, dim3(nblk(rows * (W / 4))), dim3(RB_THREADS), 0, s, v, act, rows, h, w, W, gout);
-        if (W == 128)
+        if (W == 64)
+            hipLaunchKernelGGL(rb_reduce64_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, part, pmax);
+        else if (W == 128)
             hipLaunchKernelGGL(rb_reduce128_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, part, pmax);
         else
             hipLaunchKernelGGL(rb_reduce_kernel, dim3(G), dim3(RB_THREADS), 0, s, (const float*)gout, rows, per, W, part, pmax);
@@ -382,9 +443,14 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
                      const double* sum, const float* w, const float* gam, const float* mean, const float* var, float* dw, float* dgam, float* dbet) {
         WgArgs wa;
         wa.a = a; wa.lda = lda; wa.x = xin; wa.xc = xc; wa.n = n; wa.H = ho; wa.W = wo; wa.rows = rows; wa.slab = slab;
-        const int nqt = ksz * ksz * xc / 128, Sl = bk_slabs(g, rows, nqt, lda);
+        const int nqt = wg_nqt(ksz, xc), Sl = bk_slabs(g, rows, nqt, lda);
         wa.slab_len = slab_rows(rows, Sl); wa.ksz = ksz; wa.stride = st; wa.Hin = hi; wa.Win = wi;
-        hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, lda / 128), dim3(WG_THREADS), 0, s, wa);
+        if (lda == 64)   // res2's conv2 and conv1: the 64-row tile, one column tile, slab [64][ksz^2 xc]
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<5>, dim3(nqt * Sl, 1), dim3(WG_THREADS), 0, s, wa);
+        else if (xc & 127)   // res2's conv3 and downsample over 64 channels: half a q-tile
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<4>, dim3(nqt * Sl, lda / 128), dim3(WG_THREADS), 0, s, wa);
+        else
+            hipLaunchKernelGGL(dbhead_train_wgrad_kernel<3>, dim3(nqt * Sl, lda / 128), dim3(WG_THREADS), 0, s, wa);
         hipLaunchKernelGGL(rb_param_kernel, dim3(lda), dim3(RB_THREADS), 0, s, (const float*)slab, Sl, xc, ksz * ksz, scl, sum, w, gam, mean, var, eps, dw, dgam,
                            dbet);
     };
@@ -407,21 +473,23 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
             hipLaunchKernelGGL(bk_mask_reduce_kernel<2>, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
         else if (OUT == 1024)
             hipLaunchKernelGGL(bk_mask_reduce_kernel<1>, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
-        else
+        else if (OUT == 512)
             hipLaunchKernelGGL(bk_mask_reduce512_kernel, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
+        else
+            hipLaunchKernelGGL(bk_mask_reduce256_kernel, dim3(G), dim3(RB_THREADS), 0, s, dy, (const half_t*)y, M, per, g.h, g.w, g3, part, pmax);
         hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, OUT)), dim3(RB_THREADS), 0, s, g3p, n, g.h, g.w, OUT);
         finish_form(g3, M, g.h, g.w, OUT, G, dscale, sum3, sc3, g3h, g3p, 1);
     }
     VTD_HIP_CHECK(hipGetLastError());
     wgrad(g3h, OUT, M, g.h, g.w, a2, W, g.h, g.w, 1, 1, sc3, sum3, P->conv3_w, P->bn3_w, P->bn3_mean, P->bn3_var, Gp->conv3_w, Gp->bn3_w, Gp->bn3_b);
     if (g.ds)
-        wgrad(g3h, OUT, M, g.h, g.w, (const half_t*)x, cin, hin, win, 1, 2, sc3, sum3, P->ds_w, P->ds_bn_w, P->ds_bn_mean, P->ds_bn_var, Gp->ds_w,
+        wgrad(g3h, OUT, M, g.h, g.w, (const half_t*)x, cin, hin, win, 1, stride, sc3, sum3, P->ds_w, P->ds_bn_w, P->ds_bn_mean, P->ds_bn_var, Gp->ds_w,
               Gp->ds_bn_w, Gp->ds_bn_b);
     VTD_HIP_CHECK(hipGetLastError());
     // da2 = conv3^T(g3) into the g2 buffer, masked in place by a2 > 0.  Its padded operand is of the input's extent: the interior for the
     // stride-1 block, the even positions of a zeroed plane for the stride-2 block
     if ((rc = dgrad(g3p, g.h, g.w, OUT, P->conv3_w, P->bn3_w, P->bn3_var, W, 1, g2))) return rc;
-    if (g.ds)
+    if (stride == 2)
         VTD_HIP_CHECK(hipMemsetAsync(g2p, 0, (size_t)g.pin * W * 2, s));
     else
         hipLaunchKernelGGL(rb_zero_ring_kernel, dim3(ring_blocks(n, g.h, g.w, W)), dim3(RB_THREADS), 0, s, g2p, n, g.h, g.w, W);
@@ -441,10 +509,15 @@ int launch_backward(const Fam& fam, const void* x, int n, int hin, int win, int 
             hipLaunchKernelGGL(bk_add_identity_kernel, dim3(nblk(M * (OUT / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M * (OUT / 4),
                                (const float*)sc3, (const float*)sc2, (const float*)sc1);
         } else {
-            // ds^T(g3) at g3's scale into the g3 buffer (its fp32 values are in the operands by now), then onto the even positions
+            // ds^T(g3) at g3's scale into the g3 buffer (its fp32 values are in the operands by now), then onto the even positions; res2.0's
+            // downsample has stride 1, so its term is dense: every pixel, the same two multipliers (rb_add_identity_kernel's sum)
             if ((rc = dgrad(g3p, g.h, g.w, OUT, P->ds_w, P->ds_bn_w, P->ds_bn_var, cin, 1, g3))) return rc;
-            hipLaunchKernelGGL(bk_add_downsample_kernel, dim3(nblk(M * (cin / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M, g.h, g.w, cin,
-                               (const float*)sc2, (const float*)sc1);
+            if (stride == 2)
+                hipLaunchKernelGGL(bk_add_downsample_kernel, dim3(nblk(M * (cin / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M, g.h, g.w, cin,
+                                   (const float*)sc2, (const float*)sc1);
+            else
+                hipLaunchKernelGGL(rb_add_identity_kernel, dim3(nblk(M * (cin / 4))), dim3(RB_THREADS), 0, s, dx, (const float*)g3, M * (cin / 4),
+                                   (const float*)sc2, (const float*)sc1);
         }
         hipLaunchKernelGGL(rb_copy_scale_kernel, dim3(1), dim3(64), 0, s, (const float*)sc1, dxscale);
     }
@@ -498,4 +571,20 @@ int vtd_launch_bottleneck128_backward(const void* x, int n, int hin, int win, in
                                       const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
                                       float* dx, float* dxscale, hipStream_t s) {
     return launch_backward(BK_RES3, x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
+}
+
+// res2 (torchvision's layer1), W = 64: (64 -> 64 -> 256, stride 1, downsample at stride 1) and (256 -> 64 -> 256, stride 1, identity)
+int64_t vtd_bottleneck64_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode) {
+    return ws_bytes(BK_RES2, n, hin, win, cin, width, stride, mode);
+}
+
+int vtd_launch_bottleneck64_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                    void* ws, void* y, hipStream_t s) {
+    return launch_forward(BK_RES2, x, n, hin, win, cin, width, stride, P, eps, ws, y, s);
+}
+
+int vtd_launch_bottleneck64_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                     const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
+                                     float* dx, float* dxscale, hipStream_t s) {
+    return launch_backward(BK_RES2, x, n, hin, win, cin, width, stride, P, eps, ws, y, dy, dscale, Gp, scratch, dx, dxscale, s);
 }

@@ -2,7 +2,7 @@
 // statistics; bottleneck_train.hip: ResNet-50's Bottlenecks): the padded-tap helpers, the ReLU mask, the identity add, the weight-gradient
 // slab rules, the argument checks and the convolution descriptor; and the kernels of the frozen-statistics path that take every width from
 // their launch: the fold, the reduce's finish, the fp16 operand forming, the dgrad panel and the parameter gradients; and the 128-wide
-// reduce, which ResNet-18's layer2 and ResNet-50's res3 both launch.
+// and 64-wide reduces, which ResNet-18's layer2 and ResNet-50's res3, and ResNet-18's layer1 and ResNet-50's res2, launch.
 #ifndef VTD_RESBLOCK_COMMON_H
 #define VTD_RESBLOCK_COMMON_H
 #include "vtd_common.h"
@@ -143,6 +143,32 @@ __global__ __launch_bounds__(RB_THREADS) void rb_reduce128_kernel(const float* v
     if (t == 0) {
         float m = shm[0];
         for (int k = 1; k < RB_THREADS; ++k) m = shm[k] > m || shm[k] != shm[k] ? shm[k] : m;
+        pmax[blockIdx.x] = m;
+    }
+}
+
+// v [rows][64] fp32: thread t owns channel t % 64 over one quarter of the workgroup's rows m0 .. m1 in row order: quarter k = t / 64 takes
+// rows m0 + ceil(k r / 4) .. m0 + ceil((k + 1) r / 4) - 1 of the r = m1 - m0; part[g][c] = (q0 + q1) + (q2 + q3), fp64; pmax[g]
+__global__ __launch_bounds__(RB_THREADS) void rb_reduce64_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
+    const int t = threadIdx.x, c = t & 63, k = t >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
+    const int64_t r = m1 - m0, lo = m0 + (k * r + 3) / 4, hi = m0 + ((k + 1) * r + 3) / 4;
+    double s = 0.0;
+    float mx = 0.f;
+    for (int64_t m = lo; m < hi; ++m) {
+        const float a = v[m * 64 + c], fa = fabsf(a);
+        s += (double)a;
+        mx = fa > mx || fa != fa ? fa : mx;
+    }
+    __shared__ double shs[RB_THREADS];
+    __shared__ float shm[RB_THREADS];
+    shs[t] = s;
+    shm[t] = mx;
+    __syncthreads();
+    if (k == 0) part[(int64_t)blockIdx.x * 64 + c] = (shs[c] + shs[64 + c]) + (shs[128 + c] + shs[192 + c]);
+    if (t == 0) {
+        float m = shm[0];
+        for (int j = 1; j < RB_THREADS; ++j) m = shm[j] > m || shm[j] != shm[j] ? shm[j] : m;
         pmax[blockIdx.x] = m;
     }
 }

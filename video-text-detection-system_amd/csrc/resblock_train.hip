@@ -118,32 +118,6 @@ BwdLayout bwd_layout(const Geo& g, bool strided) {
 }
 
 // ---- backward: what is specific to the BasicBlock's widths -------------------------------------------------------------------------------
-// v [rows][64] fp32: thread t owns channel t % 64 over one quarter of the workgroup's rows m0 .. m1 in row order: quarter k = t / 64 takes
-// rows m0 + ceil(k r / 4) .. m0 + ceil((k + 1) r / 4) - 1 of the r = m1 - m0; part[g][c] = (q0 + q1) + (q2 + q3), fp64; pmax[g]
-__global__ __launch_bounds__(RB_THREADS) void rb_reduce64_kernel(const float* v, int64_t rows, int64_t per, double* part, float* pmax) {
-    const int t = threadIdx.x, c = t & 63, k = t >> 6;
-    const int64_t m0 = (int64_t)blockIdx.x * per < rows ? (int64_t)blockIdx.x * per : rows, m1 = m0 + per < rows ? m0 + per : rows;
-    const int64_t r = m1 - m0, lo = m0 + (k * r + 3) / 4, hi = m0 + ((k + 1) * r + 3) / 4;
-    double s = 0.0;
-    float mx = 0.f;
-    for (int64_t m = lo; m < hi; ++m) {
-        const float a = v[m * 64 + c], fa = fabsf(a);
-        s += (double)a;
-        mx = fa > mx || fa != fa ? fa : mx;
-    }
-    __shared__ double shs[RB_THREADS];
-    __shared__ float shm[RB_THREADS];
-    shs[t] = s;
-    shm[t] = mx;
-    __syncthreads();
-    if (k == 0) part[(int64_t)blockIdx.x * 64 + c] = (shs[c] + shs[64 + c]) + (shs[128 + c] + shs[192 + c]);
-    if (t == 0) {
-        float m = shm[0];
-        for (int j = 1; j < RB_THREADS; ++j) m = shm[j] > m || shm[j] != shm[j] ? shm[j] : m;
-        pmax[blockIdx.x] = m;
-    }
-}
-
 // the stride-2 block: dx [n][2H][2Wd][cin] (at g1's total scale) += ds^T(g2) [n][H][Wd][cin] (at g2's total scale) times g1's own
 // multiplier, a power of two, at the even (row, column) positions: the 1x1 stride-2 convolution reads no other.  One thread = 4 channels.
 __global__ __launch_bounds__(RB_THREADS) void rb_add_downsample_kernel(float* dx, const float* t, int64_t rows, int H, int Wd, int cin, const float* sc1) {

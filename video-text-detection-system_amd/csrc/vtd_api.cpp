@@ -124,6 +124,12 @@ int vtd_launch_bottleneck128_forward(const void* x, int n, int hin, int win, int
 int vtd_launch_bottleneck128_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
                                       const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
                                       float* dx, float* dxscale, hipStream_t s);
+int64_t vtd_bottleneck64_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_bottleneck64_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                    void* ws, void* y, hipStream_t s);
+int vtd_launch_bottleneck64_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
+                                     const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
+                                     float* dx, float* dxscale, hipStream_t s);
 int vtd_launch_fpn_unpack_tap_grad(const float* g, const float* sc, int n, int channels, int H, int W, float* out, hipStream_t s);
 int vtd_launch_dbhead_backward(const void* feats, int n, int H, int W, const vtd_dbhead_params* params, int training, const void* ws,
                                const float* prob, const float* thresh, const float* gprob, const float* gthresh, const vtd_dbhead_params* grads,
@@ -1119,6 +1125,9 @@ const char* vtd_strerror(int code) {
         case -3905: return "128-wide Bottleneck training: invalid argument or unsupported geometry (built: width 128 with 256 -> 512 stride 2, even "
                            "extents and a downsample, or 512 -> 512 stride 1: ResNet-50's res3)";
         case -3906: return "128-wide Bottleneck training: misaligned buffer";
+        case -3907: return "64-wide Bottleneck training: invalid argument or unsupported geometry (built: width 64 at stride 1 with 64 -> 256 and a "
+                           "downsample, or 256 -> 256: ResNet-50's res2)";
+        case -3908: return "64-wide Bottleneck training: misaligned buffer";
         case -3601: return "AdamW step: invalid argument (null or not 4-byte aligned pointer, count < 0, n outside [0, 2^40), non-finite scalar, "
                            "bc2_sqrt <= 0)";
         default: break;
@@ -1300,6 +1309,24 @@ int vtd_bottleneck128_train_backward(const void* x_dev, int n, int h_in, int w_i
                                      float* dx_dev, float* dxscale_dev, vtd_stream stream) {
     return vtd_launch_bottleneck128_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
                                              scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+// ResNet-50's res2: the two Bottleneck geometries of width 64, both at stride 1
+int64_t vtd_bottleneck64_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_bottleneck64_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_bottleneck64_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                   float eps, void* workspace_dev, void* y_dev, vtd_stream stream) {
+    return vtd_launch_bottleneck64_forward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, (hipStream_t)stream);
+}
+
+int vtd_bottleneck64_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride,
+                                    const vtd_bottleneck_params* params, float eps, const void* workspace_dev, const void* y_dev,
+                                    const float* dy_dev, const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev,
+                                    float* dx_dev, float* dxscale_dev, vtd_stream stream) {
+    return vtd_launch_bottleneck64_backward(x_dev, n, h_in, w_in, cin, width, stride, params, eps, workspace_dev, y_dev, dy_dev, dscale_dev, grads,
+                                            scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 
 int64_t vtd_block64_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {

@@ -185,6 +185,10 @@ SIGNATURES = {
     "vtd_bottleneck128_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_bottleneck128_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.POINTER(BottleneckParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck64_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
+    "vtd_bottleneck64_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck64_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(BottleneckParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
     "vtd_block64_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtd_block64_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -283,6 +283,15 @@ _RES3_BUILT = ("res3 training is built for ResNet-50's res3: four Bottlenecks of
                "512 -> 512 stride 1, three times) on a C2 tap of 256 channels and even extents, with one BatchNorm eps")
 
 
+# ResNet-50's res2 (torchvision's layer1): the 64-wide Bottlenecks, behind the vtd_bottleneck64_train_* entries of the same file.  Both
+# geometries run at stride 1; the first block's downsample is a 1x1 convolution at stride 1 over the pooled stem output's 64 channels
+_BOTTLENECK64_GEOMETRIES = ((64, 64, 1, True), (256, 64, 1, False))
+_BOTTLENECK64_BUILT = ("bottleneck64_train is built for the Bottlenecks of ResNet-50's res2 (64 -> 64 -> 256 stride 1 with downsample, "
+                       "256 -> 64 -> 256 stride 1), with frozen-statistics BatchNorm")
+_RES2_BUILT = ("res2 training is built for ResNet-50's res2: three Bottlenecks of width 64 (64 -> 256 stride 1 with downsample, then "
+               "256 -> 256 stride 1, twice) on a pooled tap of 64 channels, with one BatchNorm eps")
+
+
 def _bottleneck_pairs(block):
     return ([(block.conv1, block.bn1), (block.conv2, block.bn2), (block.conv3, block.bn3)] +
             ([(block.downsample[0], block.downsample[1])] if hasattr(block, "downsample") else []))
@@ -337,6 +346,13 @@ def bottleneck128_train(block, x):
     downsample, even extents) or 512 -> 128 -> 512 at stride 1.  Returns ``[n,512,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9
     learnable tensors and w.r.t. ``x`` at either stride; frozen statistics, never written; the same refusals before the device is looked at."""
     return _bottleneck_train(block, x, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT, _BOTTLENECK128)
+
+
+def bottleneck64_train(block, x):
+    """bottleneck_train's counterpart for ResNet-50's res2 (the vtd_bottleneck64_train_* entries): 64 -> 64 -> 256 (with a 1x1 downsample at
+    stride 1) or 256 -> 64 -> 256, both at stride 1.  Returns ``[n,256,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9 learnable
+    tensors and w.r.t. ``x`` for either geometry; frozen statistics, never written; the same refusals before the device is looked at."""
+    return _bottleneck_train(block, x, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT, _BOTTLENECK64)
 
 
 def _bottleneck_train(block, x, geometries, built, entry):
@@ -446,6 +462,37 @@ def forward_res3_padded(layer, c2_tap):
         return x
 
 
+def _res2_operands(layer, tap, device=None):
+    """ResNet-50's res2 on a padded pooled tap of 64 channels, as _res3_operands: (the three blocks, their geometries, eps, their learnable
+    tensors, their running statistics), judged on shapes alone.  Every block runs at the tap's extent."""
+    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
+    if len(blocks) != 3 or not all(isinstance(b, Bottleneck) for b in blocks):
+        raise RuntimeError(_RES2_BUILT)
+    checks = [_bottleneck_check(b, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT) for b in blocks]
+    if not torch.is_tensor(tap) or tap.dim() != 4:
+        raise RuntimeError(_RES2_BUILT)
+    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
+    if ([c[0] for c in checks] != [(64, 64, 1)] + [(256, 64, 1)] * 2 or tap.shape[3] != 64 or h < 1 or w < 1 or len({c[1] for c in checks}) > 1):
+        raise RuntimeError(_RES2_BUILT)
+    ops = [_bottleneck_operands(b, tap.device if device is None else device, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT) for b in blocks]
+    geoms = [(n, h, w, 64, 64, 1)] + [(n, h, w, 256, 64, 1)] * 2
+    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def forward_res2_padded(layer, pool_tap):
+    """ResNet-50's res2 (three Bottlenecks of width 64) on a padded pooled tap [n,h+2,w+2,64] (the stem's output, e.g.
+    DetectorEngine.forward_pool) with the HIP training kernels, no gradient: padded C2 [n,h+2,w+2,256] fp16 with a zero ring."""
+    if not torch.is_tensor(pool_tap) or pool_tap.dim() != 4:
+        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+    _, geoms, eps, learn, stats = _res2_operands(layer, pool_tap)
+    _check_padded_taps([pool_tap])
+    with torch.no_grad():
+        x = pool_tap.detach()
+        for g, lr, st in zip(geoms, learn, stats):
+            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK64)[0]
+        return x
+
+
 _PLANS = {
     # name: (block class, blocks per stage, C5 channels)
     "resnet18": (BasicBlock, (2, 2, 2, 2), 512),
@@ -540,8 +587,17 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False,
-                       stem_batch_stats=False, res5=None, res4=None, res3=None):
-        """`res3` (ResNet-50's res3, an nn.Sequential of four Bottlenecks of width 128) goes with `res4`, `res5`, a DBHead and the padded tap [C2]
+                       stem_batch_stats=False, res5=None, res4=None, res3=None, res2=None):
+        """`res2` (ResNet-50's res2, an nn.Sequential of three Bottlenecks of width 64) goes with `res3`, `res4`, `res5`, a DBHead and the padded
+        pooled tap [pool] of 64 channels and extents that are multiples of 8 (C2 .. C5 are computed here): res2 -> res3 -> res4 -> res5 -> FPN
+        -> head as ONE autograd node of sixteen blocks, per = (3, 4, 6, 3), res2 on the vtd_bottleneck64_train_* entries, differentiable
+        w.r.t. res2's thirty learnable tensors and the 156 above.  C2 .. C5 are the outputs of blocks 3, 7, 13 and 16; the FPN forms dC2 ..
+        dC5; res3.0's strided input gradient is added to the FPN's dC2 once, at one power-of-two scale; res2.0 forms no input gradient.
+        With `stem=(conv, bn)` too, on the tap [image] (nets.pack_image): stem -> res2 -> .. -> head, the stem on the frozen-statistics
+        vtd_stem_train_* entries, and res2.0's input gradient is the stem's dpool.  Without `res3`, `res4` and `res5`, without a head, or
+        with a ResNet-18 stage argument or batch-statistics flag it raises ValueError.
+
+        `res3` (ResNet-50's res3, an nn.Sequential of four Bottlenecks of width 128) goes with `res4`, `res5`, a DBHead and the padded tap [C2]
         of 256 channels and extents that are multiples of 8 (further entries are ignored: C3, C4 and C5 are computed here): res3 -> res4 ->
         res5 -> FPN -> head as ONE autograd node, res3 on the vtd_bottleneck128_train_* entries, differentiable w.r.t. res3's thirty-nine
         learnable tensors, res4's fifty-seven, res5's thirty, the FPN's ten and the head's twenty.  C3 is the fourth block's output, C4 the
@@ -622,6 +678,17 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
+        if res2 is not None:
+            if res3 is None or res4 is None or res5 is None:
+                raise ValueError("forward_padded(taps, head=head, res2=...) is ResNet-50's res2 -> res3 -> res4 -> res5 -> FPN -> head node: it "
+                                 "needs res3, res4 and res5 too")
+            if any(m is not None for m in layers) or trunk_batch_stats or stem_batch_stats:
+                raise ValueError("forward_padded(taps, head=head, res5=..., res4=..., res3=..., res2=...) is ResNet-50's res2 -> res3 -> res4 -> "
+                                 "res5 -> FPN -> head node with frozen-statistics BatchNorm: it takes no layer1 .. layer4, trunk_batch_stats or "
+                                 "stem_batch_stats (those are ResNet-18's)")
+            if head is None:
+                raise ValueError("forward_padded(taps, res5=..., res4=..., res3=..., res2=...) is the training node: it needs the DBHead too")
+            return self._forward_padded_res2(taps, head, res5, res4, res3, res2, stem)
         if res3 is not None:
             if res4 is None or res5 is None:
                 raise ValueError("forward_padded(taps, head=head, res3=...) is ResNet-50's res3 -> res4 -> res5 -> FPN -> head node: it needs res4 "
@@ -747,6 +814,45 @@ class FeaturePyramidNetwork(nn.Module):
                   tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, (4, 6, 3))
         return self._run_node(head, bns, plan, *(t for lr in learn3 + learn4 + learn5 for t in lr), *params, *hparams)
+
+    def _forward_padded_res2(self, taps, head, res5, res4, res3, res2, stem):
+        """forward_padded(taps, head=head, res5=, res4=, res3=, res2=[, stem=]): the plan of sixteen Bottleneck blocks in four stages,
+        (3, 4, 6, 3), on the pooled tap; with `stem`, on the image tap with the stem's launch in front."""
+        name = "image" if stem is not None else "pool"
+        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
+            raise ValueError(f"padded taps must be the tensors [{name}]")
+        if stem is not None and (not isinstance(stem, (list, tuple)) or len(stem) != 2):
+            raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:1])
+        slearn, splan = [], None
+        if stem is None:
+            _check_padded_taps(taps)
+            pool = taps[0]
+        else:
+            sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], taps[0])
+            splan = (sgeom, seps, tuple(sstats))
+            pool = _meta_tap(sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2, 64)
+        dev = taps[0].device
+        _, geoms2, beps, learn2, stats2 = _res2_operands(res2, pool, dev)
+        n, h2, w2 = geoms2[0][:3]
+        if h2 % 8 or w2 % 8:
+            raise RuntimeError(_RES2_BUILT + f"; the node needs a pooled tap whose extents are multiples of 8, got {h2} x {w2}")
+        # res3, res4 and res5 are judged on the shapes of C2, C3 and C4: the tensors themselves are computed in the node
+        _, geoms3, beps3, learn3, stats3 = _res3_operands(res3, _meta_tap(n, h2, w2, 256), dev)
+        _, geoms4, beps4, learn4, stats4 = _res4_operands(res4, _meta_tap(n, h2 // 2, w2 // 2, 512), dev)
+        _, geoms5, beps5, learn5, stats5 = _res5_operands(res5, _meta_tap(n, h2 // 4, w2 // 4, 1024), dev)
+        if beps3 != beps or beps4 != beps or beps5 != beps:
+            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of res2, res3, res4 and res5")
+        h, w = geoms5[-1][1:3]
+        geom = self._geometry([(n, 256, h2, w2), (n, 512, h2 // 2, w2 // 2), (n, 1024, h2 // 4, w2 // 4), (n, 2048, h, w)])
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK64, len(lr)) for g, lr, s in zip(geoms2, learn2, stats2)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK128, len(lr)) for g, lr, s in zip(geoms3, learn3, stats3)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, blocks, beps, None, (3, 4, 6, 3))
+        return self._run_node(head, bns, plan, *slearn, *(t for lr in learn2 + learn3 + learn4 + learn5 for t in lr), *params, *hparams)
 
     def _forward_padded_batch_stem(self, taps, head, layers, stem, trunk_batch_stats, stem_batch_stats):
         """forward_padded(..., stem_batch_stats=True): the whole-backbone node with batch statistics in the stem too."""
@@ -1235,7 +1341,8 @@ _BOTTLENECK = "vtd_bottleneck_train"     # ResNet-50's last stage: the two Bottl
                                          # block's output has 4 width channels and its struct a third convolution + BatchNorm pair
 _BOTTLENECK256 = "vtd_bottleneck256_train"   # ResNet-50's res4: the two Bottleneck geometries of width 256, the same file and struct
 _BOTTLENECK128 = "vtd_bottleneck128_train"   # ResNet-50's res3: the two Bottleneck geometries of width 128, the same file and struct
-_BOTTLENECK_FAMILIES = (_BOTTLENECK, _BOTTLENECK256, _BOTTLENECK128)
+_BOTTLENECK64 = "vtd_bottleneck64_train"     # ResNet-50's res2: the two Bottleneck geometries of width 64 (both stride 1), the same file and struct
+_BOTTLENECK_FAMILIES = (_BOTTLENECK, _BOTTLENECK256, _BOTTLENECK128, _BOTTLENECK64)
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
 
 
@@ -1696,7 +1803,12 @@ _RES5_MODE = "head+fpn+res5"
 _RES4_MODE = "head+fpn+res5+res4"
 # and one more: res3 (backbone.5: four Bottlenecks of width 128); the trunk engine then stops at C2
 _RES3_MODE = "head+fpn+res5+res4+res3"
-_RES_MODES = (_RES5_MODE, _RES4_MODE, _RES3_MODE)
+# and the last residual stage: res2 (backbone.4: three Bottlenecks of width 64); the trunk engine then runs the stem alone (forward_pool)
+_RES2_MODE = "head+fpn+res5+res4+res3+res2"
+_RES_MODES = (_RES5_MODE, _RES4_MODE, _RES3_MODE, _RES2_MODE)
+# the whole ResNet-50 detector: the four stages and the stem; nothing is frozen and the train-mode forward needs no trunk engine.  ResNet-18's
+# name for the same, "head+fpn+backbone", stays refused on resnet50
+_RES_WHOLE_MODE = "head+fpn+res5+res4+res3+res2+stem"
 
 
 class DBNet(_EngineOwner, nn.Module):
@@ -1762,6 +1874,18 @@ class DBNet(_EngineOwner, nn.Module):
         and C3 from the trunk engine (keyed on the frozen backbone tensors only; its own C4 and C5 are ignored), then runs res4, res5, the
         FPN and the head on the HIP training kernels as one autograd node.  Frozen statistics only: trunk_bn must be "frozen".
 
+        "head+fpn+res5+res4+res3+res2" (ResNet-50 only; on resnet18 it raises ValueError that names
+        "head+fpn+layer4+layer3+layer2+layer1"): every residual stage -- only the stem (backbone.0, backbone.1) stops requiring grad;
+        backbone.4 (three Bottlenecks of width 64, 30 tensors) and the 156 above train: 186 tensors.  A forward in train mode takes the
+        pooled stem output from the trunk engine's forward_pool (keyed on the frozen stem tensors only; the stem alone runs), then runs res2
+        .. res5, the FPN and the head on the HIP training kernels as one autograd node.  Frozen statistics only: trunk_bn must be "frozen".
+
+        "head+fpn+res5+res4+res3+res2+stem" (ResNet-50 only; on resnet18 it raises ValueError that names "head+fpn+backbone", which in turn
+        stays refused on resnet50): the whole ResNet-50 detector -- nothing is frozen, 189 tensors train.  A forward in train mode packs the
+        image (nets.pack_image) and runs the stem (csrc/stem_train.hip, frozen statistics), res2 .. res5, the FPN and the head as one
+        autograd node; no trunk engine is built or read.  res2.0 forms its input gradient, which is the stem's upstream gradient.  Frozen
+        statistics only: trunk_bn must be "frozen".
+
         "head+fpn+res5+res4+res3" (ResNet-50 only; on resnet18 it raises ValueError that names "head+fpn+layer4+layer3+layer2"): one stage
         further down -- backbone.0 .. backbone.4 (the stem and res2) stop requiring grad; backbone.5 (four Bottlenecks of width 128, 39
         tensors), backbone.6 (57), backbone.7 (30), fpn (10) and head (20) train: 156 tensors.  A forward in train mode takes C2 from the
@@ -1815,11 +1939,20 @@ class DBNet(_EngineOwner, nn.Module):
             if self.backbone_name != "resnet50":
                 raise ValueError(f"trainable={trainable!r} names ResNet-50's upper three stages (thirteen Bottlenecks); on {self.backbone_name} the "
                                  "upper three stages train with trainable='head+fpn+layer4+layer3+layer2'")
+        elif trainable == _RES2_MODE:
+            if self.backbone_name != "resnet50":
+                raise ValueError(f"trainable={trainable!r} names ResNet-50's four stages (sixteen Bottlenecks); on {self.backbone_name} the "
+                                 "four stages train with trainable='head+fpn+layer4+layer3+layer2+layer1'")
+        elif trainable == _RES_WHOLE_MODE:
+            if self.backbone_name != "resnet50":
+                raise ValueError(f"trainable={trainable!r} names ResNet-50's four stages and stem; on {self.backbone_name} the whole detector "
+                                 "trains with trainable='head+fpn+backbone'")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
-        if trainable in _RES_MODES and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
-            who = ("res5 trains", "res4 and res5 train", "res3, res4 and res5 train")[_RES_MODES.index(trainable)]
+        if (trainable in _RES_MODES or trainable == _RES_WHOLE_MODE) and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
+            who = ("res5 trains", "res4 and res5 train", "res3, res4 and res5 train", "res2, res3, res4 and res5 train",
+                   "the stem and res2 .. res5 train")[(_RES_MODES + (_RES_WHOLE_MODE,)).index(trainable)]
             raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: {who} with frozen-statistics BatchNorm only (trunk_bn='frozen'); "
                              "batch-statistics BatchNorm is not built for Bottleneck blocks")
         if isinstance(bn_mode, (tuple, list)):
@@ -1851,7 +1984,7 @@ class DBNet(_EngineOwner, nn.Module):
                     p.requires_grad_(i >= first)
             for p in list(self.fpn.parameters()) + list(self.head.parameters()):
                 p.requires_grad_(True)
-        elif trainable == _BACKBONE_MODE:
+        elif trainable in (_BACKBONE_MODE, _RES_WHOLE_MODE):
             for p in self.parameters():
                 p.requires_grad_(True)
         self._head_versions = None
@@ -1860,21 +1993,23 @@ class DBNet(_EngineOwner, nn.Module):
     def _first_trained(self):
         """The first backbone module a stage mode trains: the mode at position k - 1 of _STAGE_MODES trains the top k residual stages,
         backbone.(8 - k) .. backbone.7, over the frozen backbone.0 .. backbone.(7 - k)."""
-        if self.trainable in _RES_MODES:      # ResNet-50: res5 alone, res4 and res5, or res3, res4 and res5
+        if self.trainable in _RES_MODES:      # ResNet-50: res5 alone, res4 and res5, res3, res4 and res5, or all four stages
             return 7 - _RES_MODES.index(self.trainable)
         return 8 - (_STAGE_MODES.index(self.trainable) + 1)
 
     def _head_tensor_versions(self):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
-        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable in (_BACKBONE_MODE,) + _RES_MODES:
+        if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable in (_BACKBONE_MODE, _RES_WHOLE_MODE) + _RES_MODES:
             tensors += list(self.fpn.parameters())
         if self.trainable in _RES_MODES:      # backbone.7's 30 parameters and 30 buffers
             tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
-        if self.trainable in (_RES4_MODE, _RES3_MODE):      # and backbone.6's 57 and 57
+        if self.trainable in (_RES4_MODE, _RES3_MODE, _RES2_MODE):      # and backbone.6's 57 and 57
             tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
-        if self.trainable == _RES3_MODE:      # and backbone.5's 39 and 39
+        if self.trainable in (_RES3_MODE, _RES2_MODE):      # and backbone.5's 39 and 39
             tensors += list(self.backbone[5].parameters()) + list(self.backbone[5].buffers())
-        if self.trainable == _BACKBONE_MODE:      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
+        if self.trainable == _RES2_MODE:      # and backbone.4's 30 and 30
+            tensors += list(self.backbone[4].parameters()) + list(self.backbone[4].buffers())
+        if self.trainable in (_BACKBONE_MODE, _RES_WHOLE_MODE):      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
             for i in (7, 6, 5, 4, 0, 1):
                 tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
         if self.trainable in _STAGE_MODES:      # the stages the mode trains, from layer4 down
@@ -1935,10 +2070,14 @@ class DBNet(_EngineOwner, nn.Module):
             return self._engine
 
     def forward(self, x):
-        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE) + _RES_MODES + _STAGE_MODES:
+        if self.trainable in ("head", "head+fpn", _BACKBONE_MODE, _RES_WHOLE_MODE) + _RES_MODES + _STAGE_MODES:
             if self.training:
                 if self.trainable == _BACKBONE_MODE:
                     return self._forward_train_backbone(x)
+                if self.trainable == _RES_WHOLE_MODE:
+                    return self._forward_train_res_whole(x)
+                if self.trainable == _RES2_MODE:
+                    return self._forward_train_res2(x)
                 if self.trainable == _RES5_MODE:
                     return self._forward_train_res5(x)
                 if self.trainable == _RES4_MODE:
@@ -2054,6 +2193,41 @@ class DBNet(_EngineOwner, nn.Module):
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = [self.trunk_engine().forward_c2(x)]   # a new tensor per call: autograd may keep it
         out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6], res3=self.backbone[5])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+    def _forward_train_res2(self, x):
+        """The train-mode forward of "head+fpn+res5+res4+res3+res2": the pooled stem output from the frozen trunk engine, which stops there
+        (forward_pool: the stem alone runs), then res2 .. res5, the FPN and the head as one autograd node."""
+        frozen = [n for i in range(4) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res2 is not implemented; only "
+                               "res2 .. res5 (backbone.4 .. backbone.7), the FPN and the DB head train (set requires_grad_(False) on backbone.0 "
+                               "and backbone.1, or pick trainable='head+fpn+res5+res4+res3+res2+stem')")
+        for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        taps = [self.trunk_engine().forward_pool(x)]   # a new tensor per call: autograd may keep it
+        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6], res3=self.backbone[5], res2=self.backbone[4])
+        self.mark_dirty()   # the kernels updated the head's running statistics in place
+        return out
+
+    def _forward_train_res_whole(self, x):
+        """The train-mode forward of "head+fpn+res5+res4+res3+res2+stem": the image packed (nets.pack_image), then the stem, res2 .. res5, the
+        FPN and the head as one autograd node; no trunk engine is built or read."""
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"DBNet(trainable={self.trainable!r}): the train-mode forward takes a float [n,3,H,W] tensor")
+        frozen = [n for n, p in self.named_parameters() if not p.requires_grad]
+        if frozen:
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} does not require grad, but this mode trains every tensor "
+                               "(pick a narrower mode with set_trainable to freeze a part)")
+        for m in (self.backbone, self.fpn, self.head):
+            if not next(m.parameters()).is_cuda:
+                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
+        dev = next(self.head.parameters()).device
+        image = pack_image(x if x.is_cuda else x.to(dev))   # no trunk engine: the stem runs on the training kernels too
+        out = self.fpn.forward_padded([image], head=self.head, res5=self.backbone[7], res4=self.backbone[6], res3=self.backbone[5],
+                                      res2=self.backbone[4], stem=(self.backbone[0], self.backbone[1]))
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
