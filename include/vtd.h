@@ -608,6 +608,62 @@ int vtd_trunk_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
                                 int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev, const float* dscale_dev,
                                 const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream);
 
+/* ---- ResNet Bottleneck training with batch-statistics BatchNorm (csrc/bottleneck_bn_train.hip): ResNet-50's res5 and res4 blocks as torch's
+ * train() mode computes them.  vtd_bottleneck_bn_train_* take the arguments of vtd_trunk_bn_train_*, one for one, with the
+ * vtd_bottleneck_params struct; tensors, layouts, the power-of-two gradient scales and the "written, not accumulated" rule are those of
+ * vtd_bottleneck_train_*.  Four geometries are built, W = width, 4W the output's channels: (cin 1024, width 512, stride 2, even h_in and w_in,
+ * with downsample), (cin 2048, width 512, stride 1, identity: ds_* ignored), (cin 512, width 256, stride 2, even extents, with downsample)
+ * and (cin 1024, width 256, stride 1); every other geometry (widths 128 and 64 included: res3, res2 and the stem keep frozen statistics) is
+ * refused with -4001.
+ * training = 0 hands the call to vtd_bottleneck_train_forward / _backward (width 512) or vtd_bottleneck256_train_forward / _backward (width
+ * 256) unchanged: their bits, nothing written (stats_dev included).  The workspace query answers at least theirs, so either value of
+ * `training` runs in one allocation.
+ * training = 1, forward, per convolution + BatchNorm pair (conv1 / bn1, conv2 / bn2, the downsample, conv3 / bn3): the raw weights are
+ * rounded to fp16 on the device in every call (no fold); the convolution writes z in float32, kept in the workspace: z1 [n h_in w_in][W]
+ * (conv1 is 1x1 at the input's extent, and a1 is padded at the input's extent), z2 [n h w][W], z_d and z3 [n h w][4W].  Per-channel statistics
+ * are (count, mean, M2) partials in fp64, combined in workgroup order (Chan) into mu and the biased sigma^2.  The W-wide pairs reduce as
+ * vtd_block_bn_train_* states for widths 512 and 256: min(256, ceil(rows / 256)) workgroups of ceil(rows / workgroups) consecutive rows, two
+ * halves (lower + upper) or four quarters ((q0 + q1) + (q2 + q3)) of them in row order.  The 4W-wide pairs: min(256, ceil(n h w / 32))
+ * workgroups of ceil(n h w / workgroups) consecutive rows; thread t of 256 owns channels 1024 j + 4 t .. 1024 j + 4 t + 3 (j < 4W / 1024) and
+ * sums them over the workgroup's rows in row order: one thread per channel, no join.  The reduce grid is per pair: bn1's rows are the input's.
+ * The running values in `params` are updated in place: mean <- (1 - momentum) mean + momentum mu, var <- (1 - momentum) var + momentum sigma^2
+ * M / (M - 1), M the pair's rows.  stats_dev (optional) receives float32 [4][2][4W]: rows bn1, bn2, bn3 and the downsample's BatchNorm, each
+ * {mu, sigma^2}; rows 0 and 1 use the first W columns; a row (or column) the call does not write is left untouched.  a1, a2, the downsample's
+ * normalised output (no ReLU) and y = relu(((z3 - mu) rstd) gamma + beta + id) are stored as ring-padded fp16 taps.  The caller advances
+ * num_batches_tracked.
+ * training = 1, backward: g3 = dy (y > 0), formed in the same pass that reduces it.  Per pair, with g the gradient at the BatchNorm output (g3
+ * for bn3 and the downsample, conv3^T(dz3) (a2 > 0) for bn2, conv2^T(dz2) (a1 > 0) for bn1) and xh = (z - mu) rstd recomputed from the saved z:
+ * s1 = sum g and s2 = sum g xh in fp64, rows and workgroups in the forward's order; dbeta = s1, dgamma = s2; dz = gamma rstd (g - s1 / M - xh
+ * s2 / M) in float32, then times a power of two taken from the bound max_c |gamma rstd| (max |g| + |s1| / M + max |xh| |s2| / M) and rounded to
+ * fp16; dW = dz^T im2col(input) (MFMA, min(8, ceil(rows / 4096)) slabs of the launch's rows, summed in slab order in fp64): dz carries gamma
+ * rstd, no factor follows.  The transposed convolutions run on the raw weights, rotated and transposed.  Stride 2: dz2 goes to the even
+ * positions of a zeroed ring-padded plane of the input's extent; the downsample pair has its own statistics and its own dz_d, and
+ * ds^T(dz_d) is added to dx at the even (row, column) positions after the power-of-two factor sc3 sc2 sc1 / scd that brings it to dz1's scale
+ * (exact).  Stride 1: dx = conv1^T(dz1) + g3 at one scale.  dx_dev (optional at either stride): NHWC float32 [n][h_in][w_in][cin] times
+ * dxscale_dev[0].  Exact for gamma = 0 and gamma < 0: nothing divides by gamma or sigma.  The statistics are not fused into the convolution's
+ * epilogue: z makes one write and two or three reads through HBM per pair.  No atomics, shape-only grids, fixed summation orders: bitwise
+ * repeatable; a dy scaled by a power of two gives the same gradient bits, scaled.
+ * vtd_bottleneck_bn_train_workspace_bytes: the larger of the frozen family's answer and, with a256(b) = b rounded up to a multiple of 256,
+ * pin = n (h_in+2) (w_in+2), pout = n (h+2) (w+2), M = n h w, Min = n h_in w_in and ds = 1 with a downsample, else 0:
+ *   mode 0: a256(2 pin W) + a256(2 pout W) + ds a256(8 pout W) + a256(4 Min W) + a256(4 M W) + (1 + ds) a256(16 M W) + a256(2 W cin) +
+ *           a256(18 W^2) + a256(8 W^2) + ds a256(8 W cin) + a256(16 W) + a256(256 x 96 W) + 2 a256(16 W) + (1 + ds) a256(64 W) + a256(8 W)
+ *   mode 1: a256(16 M W) + a256(4 M W) + a256(4 Min W) + a256(2 max(4 M W, Min W)) + a256(8 pout W) + 2 a256(2 pin W) + a256(18 W^2) +
+ *           a256(16 W) + a256(256 x 64 W) + a256(256 x 32 W) + a256(48 W) + a256(64) +
+ *           a256(4 max(min(8, ceil(M / 4096)) 9 W^2, min(8, ceil(Min / 4096)) W cin))
+ * At n = 32 a 40 x 40 res5 input (1024 -> 512 -> 2048, stride 2) takes 502624256 bytes of workspace (the frozen family: 149180416; the
+ * difference is the four float32 z) and 579634432 bytes of scratch; an 80 x 80 res4 input (512 -> 256 -> 1024, stride 2) 945600512 bytes of
+ * workspace (frozen: 257697792) and 1065895168 bytes of scratch.  Both scratch figures are the frozen family's, which keeps flat operands
+ * per stage and is the larger sum at these shapes.
+ * Errors, before any launch: -4001 (argument / unsupported geometry / training outside {0, 1} / training = 1 with fewer than two rows in any
+ * pair / momentum outside [0, 1] / dx_dev without dxscale_dev), -4002 (alignment). */
+int64_t vtd_bottleneck_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode);
+int vtd_bottleneck_bn_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                    int training, float momentum, float eps, void* workspace_dev, void* y_dev, float* stats_dev, vtd_stream stream);
+int vtd_bottleneck_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                     int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev,
+                                     const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev,
+                                     vtd_stream stream);
+
 /* ---- ResNet stem training with frozen-statistics BatchNorm (csrc/stem_train.hip): pool = maxpool3x3/s2/p1(relu(bn(conv7x7/s2/p3(x)))) on an
  * image x [n,3,height,width]; height and width are the image's, even and at least 2 (the product's 640 is not built in).  hc x wc = height / 2
  * x width / 2 is the conv map, hp x wp = ceil(hc / 2) x ceil(wc / 2) the pooled map.  The running statistics normalise and are never written;

@@ -112,6 +112,12 @@ int vtd_launch_bottleneck_forward(const void* x, int n, int hin, int win, int ci
 int vtd_launch_bottleneck_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
                                    const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp, void* scratch,
                                    float* dx, float* dxscale, hipStream_t s);
+int64_t vtd_bottleneck_bn_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
+int vtd_launch_bottleneck_bn_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, int training,
+                                     float momentum, float eps, void* ws, void* y, float* stats, hipStream_t s);
+int vtd_launch_bottleneck_bn_backward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, int training,
+                                      float eps, const void* ws, const void* y, const float* dy, const float* dscale, const vtd_bottleneck_params* Gp,
+                                      void* scratch, float* dx, float* dxscale, hipStream_t s);
 int64_t vtd_bottleneck256_ws_bytes(int n, int hin, int win, int cin, int width, int stride, int mode);
 int vtd_launch_bottleneck256_forward(const void* x, int n, int hin, int win, int cin, int width, int stride, const vtd_bottleneck_params* P, float eps,
                                      void* ws, void* y, hipStream_t s);
@@ -1128,6 +1134,10 @@ const char* vtd_strerror(int code) {
         case -3907: return "64-wide Bottleneck training: invalid argument or unsupported geometry (built: width 64 at stride 1 with 64 -> 256 and a "
                            "downsample, or 256 -> 256: ResNet-50's res2)";
         case -3908: return "64-wide Bottleneck training: misaligned buffer";
+        case -4001: return "Bottleneck batch-statistics training: invalid argument or unsupported geometry (built: width 512 with 1024 -> 2048 stride 2 "
+                           "or 2048 -> 2048 stride 1, width 256 with 512 -> 1024 stride 2 or 1024 -> 1024 stride 1, even extents at stride 2: "
+                           "ResNet-50's res5 and res4; training 0 or 1, momentum in [0, 1]; training = 1 needs n h w >= 2)";
+        case -4002: return "Bottleneck batch-statistics training: misaligned buffer";
         case -3601: return "AdamW step: invalid argument (null or not 4-byte aligned pointer, count < 0, n outside [0, 2^40), non-finite scalar, "
                            "bc2_sqrt <= 0)";
         default: break;
@@ -1397,6 +1407,25 @@ int vtd_trunk_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, in
                                 const vtd_basicblock_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev, vtd_stream stream) {
     return vtd_launch_trunk_bn_backward(x_dev, n, h_in, w_in, cin, width, stride, params, training, eps, workspace_dev, y_dev, dy_dev, dscale_dev,
                                         grads, scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
+}
+
+// ResNet-50's res5 and res4 Bottlenecks with batch-statistics BatchNorm (csrc/bottleneck_bn_train.hip)
+int64_t vtd_bottleneck_bn_train_workspace_bytes(int n, int h_in, int w_in, int cin, int width, int stride, int mode) {
+    return vtd_bottleneck_bn_ws_bytes(n, h_in, w_in, cin, width, stride, mode);
+}
+
+int vtd_bottleneck_bn_train_forward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                    int training, float momentum, float eps, void* workspace_dev, void* y_dev, float* stats_dev, vtd_stream stream) {
+    return vtd_launch_bottleneck_bn_forward(x_dev, n, h_in, w_in, cin, width, stride, params, training, momentum, eps, workspace_dev, y_dev, stats_dev,
+                                            (hipStream_t)stream);
+}
+
+int vtd_bottleneck_bn_train_backward(const void* x_dev, int n, int h_in, int w_in, int cin, int width, int stride, const vtd_bottleneck_params* params,
+                                     int training, float eps, const void* workspace_dev, const void* y_dev, const float* dy_dev,
+                                     const float* dscale_dev, const vtd_bottleneck_params* grads, void* scratch_dev, float* dx_dev, float* dxscale_dev,
+                                     vtd_stream stream) {
+    return vtd_launch_bottleneck_bn_backward(x_dev, n, h_in, w_in, cin, width, stride, params, training, eps, workspace_dev, y_dev, dy_dev, dscale_dev,
+                                             grads, scratch_dev, dx_dev, dxscale_dev, (hipStream_t)stream);
 }
 
 int vtd_stem_train_pack_input(const void* x_dev, int dtype, int n, int height, int width, void* tap_dev, vtd_stream stream) {

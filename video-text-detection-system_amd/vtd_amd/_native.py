@@ -211,6 +211,12 @@ SIGNATURES = {
     "vtd_trunk_bn_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BasicBlockParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                                                              C.c_void_p, C.c_void_p, C.POINTER(BasicBlockParams), C.c_void_p, C.c_void_p,
                                                                              C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck_bn_train_workspace_bytes": (C.c_int64, [C.c_int] * 7),
+    "vtd_bottleneck_bn_train_forward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtd_bottleneck_bn_train_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(BottleneckParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                                                                  C.c_void_p, C.c_void_p, C.POINTER(BottleneckParams), C.c_void_p, C.c_void_p,
+                                                                                  C.c_void_p, C.c_void_p]),
     "vtd_stem_train_pack_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vtd_stem_train_workspace_bytes": (C.c_int64, [C.c_int] * 4),
     "vtd_stem_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(StemParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -355,6 +355,58 @@ def bottleneck64_train(block, x):
     return _bottleneck_train(block, x, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT, _BOTTLENECK64)
 
 
+# the Bottleneck geometries with train-mode (batch-statistics) BatchNorm built (csrc/bottleneck_bn_train.hip): ResNet-50's res5 and res4
+_BOTTLENECK_BN_GEOMETRIES = _BOTTLENECK_GEOMETRIES + _BOTTLENECK256_GEOMETRIES
+_BOTTLENECK_BN_BUILT = ("bottleneck_bn_train (train-mode, batch-statistics BatchNorm) is built for the Bottlenecks of ResNet-50's res5 and res4 "
+                        "(1024 -> 512 -> 2048 and 512 -> 256 -> 1024 stride 2 with downsample and even extents, 2048 -> 512 -> 2048 and "
+                        "1024 -> 256 -> 1024 stride 1); res3, res2 and the stem keep frozen statistics")
+_RES_BN_BUILT = ("batch-statistics BatchNorm in Bottleneck stages is built for ResNet-50's res5 and res4: forward_padded(..., res5=, "
+                 "res_batch_stats=True) on the taps [C2, C3, C4] and forward_padded(..., res5=, res4=, res_batch_stats=True) on [C2, C3], and "
+                 "DBNet('resnet50', trainable='head+fpn+res5' or 'head+fpn+res5+res4', trunk_bn='bottleneck'); res3, res2 and the stem keep "
+                 "frozen statistics")
+_BOTTLENECK_BN_MOMENTUM = ("the HIP batch-statistics Bottleneck kernels need one fixed momentum on all of the block's BatchNorms "
+                           "(momentum=None, the cumulative average, is not built)")
+
+
+def _bottleneck_bn_check(block):
+    """((cin, width, stride), eps, the block's BatchNorms, their momentum) of a Bottleneck that vtd_bottleneck_bn_train_* can run in train
+    mode, judged without looking at any device."""
+    geom, eps = _bottleneck_check(block, _BOTTLENECK_BN_GEOMETRIES, _BOTTLENECK_BN_BUILT)
+    bns = [bn for _, bn in _bottleneck_pairs(block)]
+    if any(bn.momentum is None or bn.momentum != bns[0].momentum for bn in bns):
+        raise ValueError(_BOTTLENECK_BN_MOMENTUM)
+    return geom, eps, bns, float(bns[0].momentum)
+
+
+def bottleneck_bn_train(block, x):
+    """One Bottleneck of ResNet-50's res5 or res4 (1024 -> 512 -> 2048 and 512 -> 256 -> 1024 at stride 2 with downsample and even extents,
+    2048 -> 512 -> 2048 and 1024 -> 256 -> 1024 at stride 1) on the vtd_bottleneck_bn_train_* entries (csrc/bottleneck_bn_train.hip) with
+    torch's module semantics: in ``block.training`` mode the statistics of the batch normalise, the running statistics are updated in place
+    and ``num_batches_tracked`` advances on each of the block's three or four BatchNorms; in ``eval()`` mode it gives the bits of
+    ``bottleneck_train`` / ``bottleneck256_train`` and writes no buffer.  The block's BatchNorms need one eps and one fixed momentum.
+    Returns ``[n,4 width,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9 learnable tensors and w.r.t. ``x`` at either stride.
+    Everything else is refused before the device is looked at."""
+    (cin, width, stride), eps, bns, momentum = _bottleneck_bn_check(block)
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != cin:
+        raise ValueError(f"Bottleneck input must be a [n,{cin},H,W] tensor")
+    n, _, hin, win = x.shape
+    if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
+        raise RuntimeError(f"Bottleneck(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+    if block.training and n * (hin // stride) * (win // stride) < 2:
+        raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got an output of {n} x {hin // stride} x {win // stride}")
+    if not x.is_cuda:
+        raise ValueError("Bottleneck runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    _, _, learn, stats = _bottleneck_operands(block, x.device, _BOTTLENECK_BN_GEOMETRIES, _BOTTLENECK_BN_BUILT)
+    src = x if x.requires_grad and torch.is_grad_enabled() else None
+    out = _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _BOTTLENECK_BN,
+                              (bool(block.training), momentum), *learn)
+    if block.training:
+        with torch.no_grad():
+            for bn in bns:
+                bn.num_batches_tracked.add_(1)
+    return out
+
+
 def _bottleneck_train(block, x, geometries, built, entry):
     (cin, width, stride), eps = _bottleneck_check(block, geometries, built)
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != cin:
@@ -587,8 +639,18 @@ class FeaturePyramidNetwork(nn.Module):
         return _FPNTrainFn.apply(tuple(pack_tap(t) for t in features), geom, *srcs, *params)
 
     def forward_padded(self, taps, head=None, layer4=None, layer3=None, layer2=None, layer1=None, stem=None, trunk_batch_stats=False,
-                       stem_batch_stats=False, res5=None, res4=None, res3=None, res2=None):
-        """`res2` (ResNet-50's res2, an nn.Sequential of three Bottlenecks of width 64) goes with `res3`, `res4`, `res5`, a DBHead and the padded
+                       stem_batch_stats=False, res5=None, res4=None, res3=None, res2=None, res_batch_stats=False):
+        """`res_batch_stats` (True, or the tuple of exactly the res stages given: ("res5",) or ("res4", "res5")) goes with `res5`, a DBHead and
+        the taps [C2, C3, C4], or with `res4`, `res5`, a DBHead and the taps [C2, C3]: the res5 -> FPN -> head node or the res4 -> res5 -> FPN ->
+        head node described below with every Bottleneck on the vtd_bottleneck_bn_train_* entries (csrc/bottleneck_bn_train.hip), so the
+        stages' BatchNorms behave as torch's do in the mode they are in: in train() mode the statistics of the batch normalise, the running
+        statistics are updated in place and num_batches_tracked advances (10 BatchNorms for res5, 29 with res4); in eval() mode the frozen
+        path runs, the same bits as without the keyword.  The three or nine blocks must be in one mode with one fixed momentum and one eps.
+        The parameter gradients of a block do not depend on whether its input gradient is formed, so the res5 node gives the bits of the
+        deeper node's res5 gradients when fed the taps that node produced.  With `res3`, `res2`, `stem`, any ResNet-18 argument, without
+        `res5` or without a head it raises ValueError before a device is looked at: res3, res2 and the stem keep frozen statistics.
+
+        `res2` (ResNet-50's res2, an nn.Sequential of three Bottlenecks of width 64) goes with `res3`, `res4`, `res5`, a DBHead and the padded
         pooled tap [pool] of 64 channels and extents that are multiples of 8 (C2 .. C5 are computed here): res2 -> res3 -> res4 -> res5 -> FPN
         -> head as ONE autograd node of sixteen blocks, per = (3, 4, 6, 3), res2 on the vtd_bottleneck64_train_* entries, differentiable
         w.r.t. res2's thirty learnable tensors and the 156 above.  C2 .. C5 are the outputs of blocks 3, 7, 13 and 16; the FPN forms dC2 ..
@@ -678,6 +740,19 @@ class FeaturePyramidNetwork(nn.Module):
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
         layers = (layer1, layer2, layer3, layer4)
+        if res_batch_stats:
+            given = tuple(k for k, m in (("res4", res4), ("res5", res5)) if m is not None)
+            if res5 is None or res3 is not None or res2 is not None or stem is not None or any(m is not None for m in layers) or \
+                    trunk_batch_stats or stem_batch_stats or head is None:
+                raise ValueError(f"forward_padded(..., res_batch_stats={res_batch_stats!r}) is the res5 -> FPN -> head node on the taps [C2, C3, C4] "
+                                 "or the res4 -> res5 -> FPN -> head node on the taps [C2, C3]: it needs res5 and the head and takes no res3, "
+                                 "res2, stem, layer1 .. layer4, trunk_batch_stats or stem_batch_stats; " + _RES_BN_BUILT)
+            if res_batch_stats is not True and not (isinstance(res_batch_stats, (tuple, list)) and tuple(res_batch_stats) == given):
+                raise ValueError(f"forward_padded(..., res_batch_stats={res_batch_stats!r}) must be True or the tuple of exactly the res stages "
+                                 f"given, {given!r}; " + _RES_BN_BUILT)
+            if res4 is not None:
+                return self._forward_padded_res4(taps, head, res5, res4, batch=True)
+            return self._forward_padded_res5(taps, head, res5, batch=True)
         if res2 is not None:
             if res3 is None or res4 is None or res5 is None:
                 raise ValueError("forward_padded(taps, head=head, res2=...) is ResNet-50's res2 -> res3 -> res4 -> res5 -> FPN -> head node: it "
@@ -752,8 +827,31 @@ class FeaturePyramidNetwork(nn.Module):
         plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, (), None, None)      # no trunk stage
         return self._run_node(head, bns, plan, *params, *hparams)
 
-    def _forward_padded_res5(self, taps, head, res5):
-        """forward_padded(taps, head=head, res5=layer): the plan of three Bottleneck blocks in one stage."""
+    @staticmethod
+    def _res_bn_plan(layers, c5):
+        """The batch-statistics plan of a res node: (the blocks' BatchNorms, (training, momentum)), judged without looking at any device."""
+        blocks = [b for layer in layers for b in layer]
+        checks = [_bottleneck_bn_check(b) for b in blocks]
+        bbns = [bn for c in checks for bn in c[2]]
+        if any(b.training != blocks[0].training for b in blocks) or any(c[3] != checks[0][3] for c in checks):
+            raise ValueError(f"the {len(blocks)} Bottlenecks of a res_batch_stats node must be in one mode (train() or eval()) with one fixed "
+                             "BatchNorm momentum")
+        n, _, h5, w5 = c5
+        if blocks[0].training and n * h5 * w5 < 2:
+            raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a C5 of {n} x {h5} x {w5}")
+        return bbns, (bool(blocks[0].training), checks[0][3])
+
+    def _run_res_node(self, head, bns, plan, bbns, learn):
+        out = self._run_node(head, bns, plan, *learn)
+        if plan.bn is not None and plan.bn[0]:
+            with torch.no_grad():
+                for b in bbns:
+                    b.num_batches_tracked.add_(1)
+        return out
+
+    def _forward_padded_res5(self, taps, head, res5, batch=False):
+        """forward_padded(taps, head=head, res5=layer): the plan of three Bottleneck blocks in one stage.  `batch`: on the
+        vtd_bottleneck_bn_train_* entries, the blocks' mode deciding between batch and frozen statistics."""
         if not isinstance(taps, (list, tuple)) or len(taps) < 3:
             raise ValueError("padded taps must be the tensors [C2, C3, C4]")
         taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:3])
@@ -764,12 +862,14 @@ class FeaturePyramidNetwork(nn.Module):
         geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 2048, h, w)])
         params = self._live_checked(dev)
         bns, hparams, hbuffers = head._train_operands(dev)
-        blocks = tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms, learn, stats))
-        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, 3)
-        return self._run_node(head, bns, plan, *(t for lr in learn for t in lr), *params, *hparams)
+        bbns, bn = self._res_bn_plan([res5], (n, 2048, h, w)) if batch else ([], None)
+        blocks = tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms, learn, stats))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, bn, 3)
+        return self._run_res_node(head, bns, plan, bbns, (*(t for lr in learn for t in lr), *params, *hparams))
 
-    def _forward_padded_res4(self, taps, head, res5, res4):
-        """forward_padded(taps, head=head, res5=layer5, res4=layer4): the plan of nine Bottleneck blocks in two stages, (6, 3)."""
+    def _forward_padded_res4(self, taps, head, res5, res4, batch=False):
+        """forward_padded(taps, head=head, res5=layer5, res4=layer4): the plan of nine Bottleneck blocks in two stages, (6, 3).  `batch`: all
+        nine on the vtd_bottleneck_bn_train_* entries, as in _forward_padded_res5."""
         if not isinstance(taps, (list, tuple)) or len(taps) < 2:
             raise ValueError("padded taps must be the tensors [C2, C3]")
         taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:2])
@@ -785,10 +885,11 @@ class FeaturePyramidNetwork(nn.Module):
         geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 1024, h3 // 2, w3 // 2), (n, 2048, h, w)])
         params = self._live_checked(dev)
         bns, hparams, hbuffers = head._train_operands(dev)
-        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
-        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, (6, 3))
-        return self._run_node(head, bns, plan, *(t for lr in learn4 + learn5 for t in lr), *params, *hparams)
+        bbns, bn = self._res_bn_plan([res4, res5], (n, 2048, h, w)) if batch else ([], None)
+        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
+                  tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, bn, (6, 3))
+        return self._run_res_node(head, bns, plan, bbns, (*(t for lr in learn4 + learn5 for t in lr), *params, *hparams))
 
     def _forward_padded_res3(self, taps, head, res5, res4, res3):
         """forward_padded(taps, head=head, res5=layer5, res4=layer4, res3=layer3): the plan of thirteen Bottleneck blocks in three stages,
@@ -1343,7 +1444,11 @@ _BOTTLENECK256 = "vtd_bottleneck256_train"   # ResNet-50's res4: the two Bottlen
 _BOTTLENECK128 = "vtd_bottleneck128_train"   # ResNet-50's res3: the two Bottleneck geometries of width 128, the same file and struct
 _BOTTLENECK64 = "vtd_bottleneck64_train"     # ResNet-50's res2: the two Bottleneck geometries of width 64 (both stride 1), the same file and struct
 _BOTTLENECK_FAMILIES = (_BOTTLENECK, _BOTTLENECK256, _BOTTLENECK128, _BOTTLENECK64)
-_BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN)    # the batch-statistics families a caller names itself; any other entry means vtd_resblock_bn_train
+_BOTTLENECK_BN = "vtd_bottleneck_bn_train"   # res5's and res4's four Bottleneck geometries with batch-statistics BatchNorm
+                                             # (csrc/bottleneck_bn_train.hip): the Bottleneck struct, the 4 width output, statistics [4,2,4 width]
+_BOTTLENECK_STRUCT = _BOTTLENECK_FAMILIES + (_BOTTLENECK_BN,)   # the families on vtd_bottleneck_params
+_BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN, _BOTTLENECK_BN)   # the batch-statistics families a caller names itself; any other entry means
+                                                        # vtd_resblock_bn_train
 
 
 def _block_entry(geom):
@@ -1360,10 +1465,12 @@ def _block_forward_raw(tap, geom, eps, learn, stats, entry=_BASICBLOCK, bn=None)
     entry = entry if bn is None or entry in _BN_FAMILIES else _RESBLOCK_BN
     C, _native, lib, ws = _native_workspace(entry + "_workspace_bytes", (*geom, 0), tap.device)
     n, hin, win, cin, width, stride = geom
-    y = torch.empty((n, hin // stride + 2, win // stride + 2, 4 * width if entry in _BOTTLENECK_FAMILIES else width), dtype=torch.float16, device=tap.device)
+    y = torch.empty((n, hin // stride + 2, win // stride + 2, 4 * width if entry in _BOTTLENECK_STRUCT else width), dtype=torch.float16, device=tap.device)
     mode = () if bn is None else (1 if bn[0] else 0, float(bn[1]))
-    bstats = () if bn is None else (torch.full((3, 2, width), float("nan"), dtype=torch.float32, device=tap.device),)
-    st = _block_struct(learn, stats, entry in _BOTTLENECK_FAMILIES)
+    # vtd_bottleneck_bn_train's statistics are [4,2,4 width]: bn1, bn2, bn3, the downsample's; the first two rows use the first `width` columns
+    bshape = (4, 2, 4 * width) if entry == _BOTTLENECK_BN else (3, 2, width)
+    bstats = () if bn is None else (torch.full(bshape, float("nan"), dtype=torch.float32, device=tap.device),)
+    st = _block_struct(learn, stats, entry in _BOTTLENECK_STRUCT)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     _native.check(getattr(lib, entry + "_forward")(ptr(tap), *geom, C.byref(st), *mode, eps, ptr(ws), ptr(y), *map(ptr, bstats),
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry + "_forward")
@@ -1379,7 +1486,7 @@ def _block_backward_raw(tap, geom, eps, learn, stats, ws, y, dy, dscale, want_dx
     grads = [torch.empty_like(p) for p in learn]
     C, _native, lib, scratch = _native_workspace(entry + "_workspace_bytes", (*geom, 1), tap.device)
     n, hin, win, cin, width, stride = geom
-    st, gst = _block_struct(learn, stats, entry in _BOTTLENECK_FAMILIES), _block_struct(grads, None, entry in _BOTTLENECK_FAMILIES)
+    st, gst = _block_struct(learn, stats, entry in _BOTTLENECK_STRUCT), _block_struct(grads, None, entry in _BOTTLENECK_STRUCT)
     dx = torch.empty((n, hin, win, cin), dtype=torch.float32, device=tap.device) if want_dx else None
     dxs = torch.empty(2, dtype=torch.float32, device=tap.device) if want_dx else None
     mode = () if bn is None else (1 if bn[0] else 0,)
@@ -1847,6 +1954,12 @@ class DBNet(_EngineOwner, nn.Module):
         On the fourth the trunk engine gives the pooled stem output as with "frozen", then layer1 .. layer4 run on the same entries:
         backbone.4 .. backbone.7's nineteen BatchNorms (layer1's blocks have no downsample), 38 running buffers and 19 counters.  The stem keeps
         frozen statistics under "trained": "head+fpn+backbone" with "trained" is refused.
+        "bottleneck" (resnet50 with trainable="head+fpn+res5" or "head+fpn+res5+res4" only; on resnet18, with the other three ResNet-50 modes
+        and with None / "head" / "head+fpn" it raises ValueError and leaves the network as it was): the trained Bottleneck stages run on the
+        vtd_bottleneck_bn_train_* entries (csrc/bottleneck_bn_train.hip) in train mode -- backbone.7's ten BatchNorms normalise with the
+        statistics of the batch and their 20 running buffers and 10 counters move every step; with res4 backbone.6's too, 29 BatchNorms, 58
+        buffers and 29 counters.  The frozen part of the trunk comes from the trunk engine as with "frozen"; a following eval() forward
+        rebuilds the inference engine on the moved statistics.  res3, res2 and the stem under batch statistics are not built: the follow-up.
         "backbone" (resnet18 with trainable="head+fpn+backbone" only; anything else raises ValueError and leaves the network as it was): the
         whole-backbone node with the stem on the vtd_stem_bn_train_* entries and layer1 .. layer4 on vtd_trunk_bn_train_* -- all twenty
         BatchNorms of the trunk normalise with the statistics of the batch, as the reference's model.train() step does, and their 40 running
@@ -1950,18 +2063,21 @@ class DBNet(_EngineOwner, nn.Module):
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
-        if (trainable in _RES_MODES or trainable == _RES_WHOLE_MODE) and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
+        if isinstance(bn_mode, str) and bn_mode == "bottleneck":
+            if self.backbone_name != "resnet50" or trainable not in (_RES5_MODE, _RES4_MODE):
+                raise ValueError(f"trunk_bn='bottleneck' with trainable={trainable!r} on {self.backbone_name}: " + _RES_BN_BUILT)
+        elif (trainable in _RES_MODES or trainable == _RES_WHOLE_MODE) and not (isinstance(bn_mode, str) and bn_mode == "frozen"):
             who = ("res5 trains", "res4 and res5 train", "res3, res4 and res5 train", "res2, res3, res4 and res5 train",
                    "the stem and res2 .. res5 train")[(_RES_MODES + (_RES_WHOLE_MODE,)).index(trainable)]
-            raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: {who} with frozen-statistics BatchNorm only (trunk_bn='frozen'); "
-                             "batch-statistics BatchNorm is not built for Bottleneck blocks")
+            raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r}: {who} with frozen-statistics BatchNorm only (trunk_bn='frozen') "
+                             "under this spelling; " + _RES_BN_BUILT)
         if isinstance(bn_mode, (tuple, list)):
             bn_mode = tuple(bn_mode)
             fits = next((mode for stages, mode in _TRUNK_BN_STAGES.items() if stages == bn_mode), None)      # no hashing: any tuple may come
             if self.backbone_name != "resnet18" or fits is None or fits != trainable:
                 raise ValueError(f"trunk_bn={bn_mode!r} with trainable={trainable!r} on {self.backbone_name}: " + _TRUNK_BN_BUILT)
-        elif not isinstance(bn_mode, str) or bn_mode not in ("frozen", "batch", "trained", "backbone"):
-            raise ValueError(f"trunk_bn must be 'frozen' or 'batch' (or 'trained', 'backbone', or a tuple of stage names), got {bn_mode!r}")
+        elif not isinstance(bn_mode, str) or bn_mode not in ("frozen", "batch", "trained", "backbone", "bottleneck"):
+            raise ValueError(f"trunk_bn must be 'frozen' or 'batch' (or 'trained', 'backbone', 'bottleneck', or a tuple of stage names), got {bn_mode!r}")
         if bn_mode == "backbone" and (self.backbone_name != "resnet18" or trainable != _BACKBONE_MODE):
             raise ValueError(f"trunk_bn='backbone' with trainable={trainable!r} on {self.backbone_name}: " + _BACKBONE_BN_BUILT)
         if bn_mode == "trained" and (self.backbone_name != "resnet18" or trainable not in _TRAINED_BN_MODES):
@@ -2160,7 +2276,8 @@ class DBNet(_EngineOwner, nn.Module):
             if not next(m.parameters()).is_cuda:
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)[:3]   # new tensors per call: autograd may keep them
-        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7])
+        # trunk_bn="bottleneck": res5 on the batch-statistics entries, its 20 running buffers and 10 counters move too; mark_dirty covers them
+        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res_batch_stats=getattr(self, "trunk_bn", "frozen") == "bottleneck")
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
@@ -2176,7 +2293,9 @@ class DBNet(_EngineOwner, nn.Module):
             if not next(m.parameters()).is_cuda:
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
         taps = self.trunk_engine().forward_trunk(x)[:2]   # new tensors per call: autograd may keep them
-        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6])
+        # trunk_bn="bottleneck": res4 and res5 on the batch-statistics entries, their 58 running buffers and 29 counters move too
+        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6],
+                                      res_batch_stats=getattr(self, "trunk_bn", "frozen") == "bottleneck")
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
