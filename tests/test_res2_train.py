@@ -10,7 +10,7 @@ import ctypes as C
 import pytest
 import torch
 
-from test_res5_train import DS_FIELDS, LEARN_FIELDS, _aligned, _struct
+from test_res5_train import DS_FIELDS, LEARN_FIELDS, _aligned, _meta_taps, _struct
 from vtd_amd import _native, nets
 
 GEOMS = {"ds": (64, 64, 1), "id": (256, 64, 1)}      # both at stride 1; "ds" has the 1x1 downsample at stride 1
@@ -219,14 +219,14 @@ def test_forward_padded_res2_refusals():
                        (torch.nn.Sequential(*list(res2), res2[2]), p), (res3, p), (None, p), (res2, _pool(c=256, device="meta")),
                        (res2, _pool(c=128, device="meta")), (res2, torch.empty((1, 10, 2, 64), dtype=torch.float16, device="meta")), (res2, None)):
         with pytest.raises(RuntimeError, match="three Bottlenecks of width 64"):
-            nets._res2_operands(layer, tap, torch.device("cpu"))
+            nets._res_operands(nets._RES_STAGES[0], layer, tap, torch.device("cpu"))
     # shapes alone: any extent passes the stage, odd ones included; what is refused next is the CPU parameters
     with pytest.raises(ValueError, match="CUDA"):
-        nets._res2_operands(res2, _pool(2, 5, 3, device="meta"), torch.device("cpu"))
+        nets._res_operands(nets._RES_STAGES[0], res2, _pool(2, 5, 3, device="meta"), torch.device("cpu"))
     odd = nets.DBNet("resnet50").backbone[4]
     odd[2].bn2.eps = 1e-3
     with pytest.raises(ValueError, match="one eps"):
-        nets._res2_operands(odd, p, torch.device("cpu"))
+        nets._res_operands(nets._RES_STAGES[0], odd, p, torch.device("cpu"))
     with pytest.raises(RuntimeError, match="three Bottlenecks of width 64"):
         nets.forward_res2_padded(r18.backbone[4], _pool())
     with pytest.raises(ValueError, match="CUDA"):
@@ -330,16 +330,66 @@ def test_node_walks_sixteen_blocks_in_four_stages(recorded, stem):
     assert all(p.grad is not None and float(p.grad) == float(i) for i, p in enumerate(params))
 
 
-def test_forward_padded_builds_the_four_stage_plan(monkeypatch):
-    """forward_padded(res2=...) hands the node sixteen blocks in the families' order with per = (3, 4, 6, 3); with `stem=` the plan has the
-    stem too and the tap is the image."""
-    net = nets.DBNet("resnet50")
+def _plans_seen(monkeypatch):
+    """forward_padded without a device: the device checks pass, the parameters' operands are the modules' own tensors, and the node is
+    replaced by a recorder of (plan, learnable tensors)."""
     seen = []
     monkeypatch.setattr(nets, "_check_padded_taps", lambda taps: None)
     monkeypatch.setattr(nets.FeaturePyramidNetwork, "_live_checked", lambda self, dev: self.live_parameters())
     monkeypatch.setattr(nets.DBHead, "_train_operands", lambda self, dev: ([self.probability_head[1]], [p for p in self.parameters()], []))
     monkeypatch.setattr(nets, "_bottleneck_operands", lambda b, dev, *family: (None, None, [p for p in b.parameters()], [x for x in b.buffers()]))
     monkeypatch.setattr(nets.FeaturePyramidNetwork, "_run_node", staticmethod(lambda head, bns, plan, *learn: seen.append((plan, learn))))
+    return seen
+
+
+# the plans of the three shallower nodes at n = 2 and a C5 of 1 x 1 (C4 2 x 2, C3 4 x 4, C2 8 x 8), recorded from the four per-depth
+# builders that the one builder replaced: every block's (n, h, w, cin, width, stride) and the count of its learnable tensors
+G3 = [(2, 8, 8, 256, 128, 2), (2, 4, 4, 512, 128, 1), (2, 4, 4, 512, 128, 1), (2, 4, 4, 512, 128, 1)]
+G4 = [(2, 4, 4, 512, 256, 2), (2, 2, 2, 1024, 256, 1), (2, 2, 2, 1024, 256, 1), (2, 2, 2, 1024, 256, 1), (2, 2, 2, 1024, 256, 1), (2, 2, 2, 1024, 256, 1)]
+G5 = [(2, 2, 2, 1024, 512, 2), (2, 1, 1, 2048, 512, 1), (2, 1, 1, 2048, 512, 1)]
+N3, N4, N5 = [12, 9, 9, 9], [12, 9, 9, 9, 9, 9], [12, 9, 9]
+BN = "vtd_bottleneck_bn_train"
+DEPTHS = {      # node: (the taps it reads, the backbone slots it runs, per, geometries, entries, learnable counts, batch statistics)
+    "res5": (3, (7,), 3, G5, [B5] * 3, N5, False),
+    "res4": (2, (6, 7), (6, 3), G4 + G5, [B4] * 6 + [B5] * 3, N4 + N5, False),
+    "res3": (1, (5, 6, 7), (4, 6, 3), G3 + G4 + G5, [B3] * 4 + [B4] * 6 + [B5] * 3, N3 + N4 + N5, False),
+    "res5 batch": (3, (7,), 3, G5, [BN] * 3, N5, True),
+    "res4 batch": (2, (6, 7), (6, 3), G4 + G5, [BN] * 9, N4 + N5, True),
+}
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("node", list(DEPTHS))
+def test_forward_padded_builds_the_plan_at_every_depth(monkeypatch, node, training):
+    """forward_padded at the three shallower depths and on both batch-statistics nodes: the whole plan, and the learnable tensors by
+    identity -- the stages' in block order, then the FPN's ten, then the head's twenty.  A batch node advances num_batches_tracked on the
+    10 / 29 BatchNorms of its stages in train() and on none in eval()."""
+    ntaps, slots, per, geoms, entries, nlearn, batch = DEPTHS[node]
+    net = nets.DBNet("resnet50").train(training)
+    seen = _plans_seen(monkeypatch)
+    bns = [m for m in net.backbone.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    assert len(bns) == 53 and not any(int(m.num_batches_tracked) for m in bns)
+    kw = {f"res{i - 2}": net.backbone[i] for i in slots}
+    assert net.fpn.forward_padded(_meta_taps(2)[:ntaps], head=net.head, res_batch_stats=batch, **kw) is None and len(seen) == 1
+    plan, learn = seen[0]
+    assert plan.per == per and type(plan.per) is type(per) and plan.geom == (2, 1, 1, 2048) and plan.beps == 1e-5 and plan.stem is None
+    assert plan.bn == ((training, 0.1) if batch else None) and plan.head == (training, 0.1, 1e-5, ())
+    assert [tuple(t.shape) for t in plan.taps] == [(2, 10, 10, 256), (2, 6, 6, 512), (2, 4, 4, 1024)][:ntaps]
+    assert [b.geom for b in plan.blocks] == geoms and [b.entry for b in plan.blocks] == entries and [b.nlearn for b in plan.blocks] == nlearn
+    blocks = [b for i in slots for b in net.backbone[i]]
+    want = [p for b in blocks for p in b.parameters()] + net.fpn.live_parameters() + list(net.head.parameters())
+    assert len(learn) == len(want) == sum(nlearn) + 10 + 20 and all(a is b for a, b in zip(learn, want))
+    assert all(len(b.stats) == len(list(m.buffers())) and all(s is t for s, t in zip(b.stats, m.buffers())) for b, m in zip(plan.blocks, blocks))
+    stage_bns = {id(m) for b in blocks for m in b.modules() if isinstance(m, torch.nn.BatchNorm2d)}
+    assert len(stage_bns) == {(7,): 10, (6, 7): 29, (5, 6, 7): 42}[slots]
+    assert [int(m.num_batches_tracked) for m in bns] == [int(batch and training and id(m) in stage_bns) for m in bns]
+
+
+def test_forward_padded_builds_the_four_stage_plan(monkeypatch):
+    """forward_padded(res2=...) hands the node sixteen blocks in the families' order with per = (3, 4, 6, 3); with `stem=` the plan has the
+    stem too and the tap is the image."""
+    net = nets.DBNet("resnet50")
+    seen = _plans_seen(monkeypatch)
     kw = {"head": net.head, "res5": net.backbone[7], "res4": net.backbone[6], "res3": net.backbone[5], "res2": net.backbone[4]}
     net.fpn.forward_padded([_pool(2, 24, 16)], **kw)
     plan, learn = seen[-1]

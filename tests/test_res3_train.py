@@ -218,11 +218,11 @@ def test_forward_padded_res3_refusals():
                        (res3, torch.empty((1, 10, 2, 256), dtype=torch.float16, device="meta")),
                        (res3, torch.empty((1, 10, 10, 512), dtype=torch.float16, device="meta"))):
         with pytest.raises(RuntimeError, match="four Bottlenecks of width 128"):
-            nets._res3_operands(layer, tap, torch.device("cpu"))
+            nets._res_operands(nets._RES_STAGES[1], layer, tap, torch.device("cpu"))
     odd =nets.DBNet("resnet50").backbone[5]
     odd[2].bn2.eps = 1e-3
     with pytest.raises(ValueError, match="one eps"):
-        nets._res3_operands(odd, c2, torch.device("cpu"))
+        nets._res_operands(nets._RES_STAGES[1], odd, c2, torch.device("cpu"))
     with pytest.raises(RuntimeError, match="four Bottlenecks of width 128"):
         nets.forward_res3_padded(r18.backbone[5], torch.empty((1, 10, 10, 256), dtype=torch.float16))
     with pytest.raises(ValueError, match="CUDA"):

@@ -196,11 +196,11 @@ def test_forward_padded_res4_refusals():
                        (res4, torch.empty((1, 6, 2, 512), dtype=torch.float16, device="meta")),
                        (res4, torch.empty((1, 6, 6, 1024), dtype=torch.float16, device="meta"))):
         with pytest.raises(RuntimeError, match="six Bottlenecks of width 256"):
-            nets._res4_operands(layer, tap, torch.device("cpu"))
+            nets._res_operands(nets._RES_STAGES[2], layer, tap, torch.device("cpu"))
     odd = nets.DBNet("resnet50").backbone[6]
     odd[4].bn2.eps = 1e-3
     with pytest.raises(ValueError, match="one eps"):
-        nets._res4_operands(odd, c3, torch.device("cpu"))
+        nets._res_operands(nets._RES_STAGES[2], odd, c3, torch.device("cpu"))
     with pytest.raises(RuntimeError, match="six Bottlenecks of width 256"):
         nets.forward_res4_padded(r18.backbone[6], torch.empty((1, 6, 6, 512), dtype=torch.float16))
     with pytest.raises(ValueError, match="CUDA"):

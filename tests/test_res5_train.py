@@ -208,7 +208,7 @@ def test_forward_padded_res5_refusals():
                        (res5, torch.empty((1, 5, 4, 1024), dtype=torch.float16, device="meta")),
                        (res5, torch.empty((1, 4, 4, 512), dtype=torch.float16, device="meta"))):
         with pytest.raises(RuntimeError, match="three Bottlenecks of width 512"):
-            nets._res5_operands(layer, tap, torch.device("cpu"))
+            nets._res_operands(nets._RES_STAGES[3], layer, tap, torch.device("cpu"))
     with pytest.raises(RuntimeError, match="three Bottlenecks of width 512"):
         nets.forward_res5_padded(r18.backbone[7], torch.empty((1, 4, 4, 1024), dtype=torch.float16))
     with pytest.raises(ValueError, match="CUDA"):

@@ -386,20 +386,11 @@ def bottleneck_bn_train(block, x):
     ``bottleneck_train`` / ``bottleneck256_train`` and writes no buffer.  The block's BatchNorms need one eps and one fixed momentum.
     Returns ``[n,4 width,h,w]`` fp32, differentiable w.r.t. the block's 12 or 9 learnable tensors and w.r.t. ``x`` at either stride.
     Everything else is refused before the device is looked at."""
-    (cin, width, stride), eps, bns, momentum = _bottleneck_bn_check(block)
-    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != cin:
-        raise ValueError(f"Bottleneck input must be a [n,{cin},H,W] tensor")
-    n, _, hin, win = x.shape
-    if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
-        raise RuntimeError(f"Bottleneck(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
-    if block.training and n * (hin // stride) * (win // stride) < 2:
-        raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got an output of {n} x {hin // stride} x {win // stride}")
-    if not x.is_cuda:
-        raise ValueError("Bottleneck runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    geom, eps, bns, momentum = _bottleneck_bn_check(block)
+    n, hin, win = _bottleneck_input(x, geom, batch=block.training)
     _, _, learn, stats = _bottleneck_operands(block, x.device, _BOTTLENECK_BN_GEOMETRIES, _BOTTLENECK_BN_BUILT)
     src = x if x.requires_grad and torch.is_grad_enabled() else None
-    out = _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), _BOTTLENECK_BN,
-                              (bool(block.training), momentum), *learn)
+    out = _BlockTrainFn.apply(pack_tap(x), src, (n, hin, win, *geom), eps, tuple(stats), _BOTTLENECK_BN, (bool(block.training), momentum), *learn)
     if block.training:
         with torch.no_grad():
             for bn in bns:
@@ -407,142 +398,84 @@ def bottleneck_bn_train(block, x):
     return out
 
 
-def _bottleneck_train(block, x, geometries, built, entry):
-    (cin, width, stride), eps = _bottleneck_check(block, geometries, built)
+def _bottleneck_input(x, geom, batch=False):
+    """(n, H, W) of the input of a single Bottleneck of geometry (cin, width, stride), checked in the wrappers' order; `batch`: the block
+    normalises with the statistics of the batch, which needs more than one value per channel."""
+    cin, _, stride = geom
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != cin:
         raise ValueError(f"Bottleneck input must be a [n,{cin},H,W] tensor")
     n, _, hin, win = x.shape
     if n < 1 or hin < 1 or win < 1 or (stride == 2 and (hin % 2 or win % 2)):
         raise RuntimeError(f"Bottleneck(stride {stride}): the HIP training kernels need a non-empty input with even extents, got {tuple(x.shape)}")
+    if batch and n * (hin // stride) * (win // stride) < 2:
+        raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got an output of {n} x {hin // stride} x {win // stride}")
     if not x.is_cuda:
         raise ValueError("Bottleneck runs on the HIP kernels: the input must be a CUDA (HIP) tensor")
+    return int(n), int(hin), int(win)
+
+
+def _bottleneck_train(block, x, geometries, built, entry):
+    geom, eps = _bottleneck_check(block, geometries, built)
+    n, hin, win = _bottleneck_input(x, geom)
     _, _, learn, stats = _bottleneck_operands(block, x.device, geometries, built)
     src = x if x.requires_grad and torch.is_grad_enabled() else None
-    return _BlockTrainFn.apply(pack_tap(x), src, (int(n), int(hin), int(win), cin, width, stride), eps, tuple(stats), entry, None, *learn)
+    return _BlockTrainFn.apply(pack_tap(x), src, (n, hin, win, *geom), eps, tuple(stats), entry, None, *learn)
 
 
-def _res5_operands(layer, tap, device=None):
-    """ResNet-50's last stage on a padded C4 tap: (the three blocks, their geometries, eps, their learnable tensors, their running
-    statistics).  Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only stand-in."""
+def _res_operands(stage, layer, tap, device=None):
+    """One stage of ResNet-50 (a row of _RES_STAGES) on a padded tap of its input: (the blocks, their geometries, eps, their learnable
+    tensors, their running statistics).  Only the tap's shape is read; `device` names the parameters' device when the tap is a shape-only
+    stand-in.  The first block runs at the tap's extent, the others at that divided by the stride."""
+    cin, width, stride = stage.cin, stage.width, stage.stride
     blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
-    if len(blocks) != 3 or not all(isinstance(b, Bottleneck) for b in blocks):
-        raise RuntimeError(_RES5_BUILT)
-    checks = [_bottleneck_check(b) for b in blocks]
+    if len(blocks) != stage.blocks or not all(isinstance(b, Bottleneck) for b in blocks):
+        raise RuntimeError(stage.built)
+    checks = [_bottleneck_check(b, stage.geometries, stage.family_built) for b in blocks]
+    if not torch.is_tensor(tap) or tap.dim() != 4:
+        raise RuntimeError(stage.built)
     n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
-    if [c[0] for c in checks] != [(1024, 512, 2), (2048, 512, 1), (2048, 512, 1)] or tap.shape[3] != 1024 or h % 2 or w % 2 or len({c[1] for c in checks}) > 1:
-        raise RuntimeError(_RES5_BUILT)
-    ops = [_bottleneck_operands(b, tap.device if device is None else device) for b in blocks]
-    geoms = [(n, h, w, 1024, 512, 2), (n, h // 2, w // 2, 2048, 512, 1), (n, h // 2, w // 2, 2048, 512, 1)]
+    if ([c[0] for c in checks] != [(cin, width, stride)] + [(4 * width, width, 1)] * (stage.blocks - 1) or tap.shape[3] != cin or
+            h < stride or w < stride or h % stride or w % stride or len({c[1] for c in checks}) > 1):
+        raise RuntimeError(stage.built)
+    ops = [_bottleneck_operands(b, tap.device if device is None else device, stage.geometries, stage.family_built) for b in blocks]
+    geoms = [(n, h, w, cin, width, stride)] + [(n, h // stride, w // stride, 4 * width, width, 1)] * (stage.blocks - 1)
     return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+
+
+def _forward_res_padded(stage, layer, tap):
+    if not torch.is_tensor(tap) or tap.dim() != 4:
+        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
+    _, geoms, eps, learn, stats = _res_operands(stage, layer, tap)
+    _check_padded_taps([tap])
+    with torch.no_grad():
+        x = tap.detach()
+        for g, lr, st in zip(geoms, learn, stats):
+            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, stage.entry)[0]
+        return x
 
 
 def forward_res5_padded(layer, c4_tap):
     """ResNet-50's last stage (res5: three Bottlenecks) on a padded C4 tap with the HIP training kernels, no gradient: padded C5
     [n,h5+2,w5+2,2048] fp16 with a zero ring."""
-    if not torch.is_tensor(c4_tap) or c4_tap.dim() != 4:
-        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-    _, geoms, eps, learn, stats = _res5_operands(layer, c4_tap)
-    _check_padded_taps([c4_tap])
-    with torch.no_grad():
-        x = c4_tap.detach()
-        for g, lr, st in zip(geoms, learn, stats):
-            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK)[0]
-        return x
-
-
-def _res4_operands(layer, tap, device=None):
-    """ResNet-50's res4 on a padded C3 tap, as _res5_operands: (the six blocks, their geometries, eps, their learnable tensors, their running
-    statistics), judged on shapes alone."""
-    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
-    if len(blocks) != 6 or not all(isinstance(b, Bottleneck) for b in blocks):
-        raise RuntimeError(_RES4_BUILT)
-    checks = [_bottleneck_check(b, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT) for b in blocks]
-    if not torch.is_tensor(tap) or tap.dim() != 4:
-        raise RuntimeError(_RES4_BUILT)
-    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
-    if ([c[0] for c in checks] != [(512, 256, 2)] + [(1024, 256, 1)] * 5 or tap.shape[3] != 512 or h < 2 or w < 2 or h % 2 or w % 2 or
-            len({c[1] for c in checks}) > 1):
-        raise RuntimeError(_RES4_BUILT)
-    ops = [_bottleneck_operands(b, tap.device if device is None else device, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT) for b in blocks]
-    geoms = [(n, h, w, 512, 256, 2)] + [(n, h // 2, w // 2, 1024, 256, 1)] * 5
-    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+    return _forward_res_padded(_RES_STAGES[3], layer, c4_tap)
 
 
 def forward_res4_padded(layer, c3_tap):
     """ResNet-50's res4 (six Bottlenecks of width 256) on a padded C3 tap with the HIP training kernels, no gradient: padded C4
     [n,h4+2,w4+2,1024] fp16 with a zero ring."""
-    if not torch.is_tensor(c3_tap) or c3_tap.dim() != 4:
-        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-    _, geoms, eps, learn, stats = _res4_operands(layer, c3_tap)
-    _check_padded_taps([c3_tap])
-    with torch.no_grad():
-        x = c3_tap.detach()
-        for g, lr, st in zip(geoms, learn, stats):
-            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK256)[0]
-        return x
-
-
-def _res3_operands(layer, tap, device=None):
-    """ResNet-50's res3 on a padded C2 tap, as _res4_operands: (the four blocks, their geometries, eps, their learnable tensors, their running
-    statistics), judged on shapes alone."""
-    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
-    if len(blocks) != 4 or not all(isinstance(b, Bottleneck) for b in blocks):
-        raise RuntimeError(_RES3_BUILT)
-    checks = [_bottleneck_check(b, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT) for b in blocks]
-    if not torch.is_tensor(tap) or tap.dim() != 4:
-        raise RuntimeError(_RES3_BUILT)
-    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
-    if ([c[0] for c in checks] != [(256, 128, 2)] + [(512, 128, 1)] * 3 or tap.shape[3] != 256 or h < 2 or w < 2 or h % 2 or w % 2 or
-            len({c[1] for c in checks}) > 1):
-        raise RuntimeError(_RES3_BUILT)
-    ops = [_bottleneck_operands(b, tap.device if device is None else device, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT) for b in blocks]
-    geoms = [(n, h, w, 256, 128, 2)] + [(n, h // 2, w // 2, 512, 128, 1)] * 3
-    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+    return _forward_res_padded(_RES_STAGES[2], layer, c3_tap)
 
 
 def forward_res3_padded(layer, c2_tap):
     """ResNet-50's res3 (four Bottlenecks of width 128) on a padded C2 tap with the HIP training kernels, no gradient: padded C3
     [n,h3+2,w3+2,512] fp16 with a zero ring."""
-    if not torch.is_tensor(c2_tap) or c2_tap.dim() != 4:
-        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-    _, geoms, eps, learn, stats = _res3_operands(layer, c2_tap)
-    _check_padded_taps([c2_tap])
-    with torch.no_grad():
-        x = c2_tap.detach()
-        for g, lr, st in zip(geoms, learn, stats):
-            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK128)[0]
-        return x
-
-
-def _res2_operands(layer, tap, device=None):
-    """ResNet-50's res2 on a padded pooled tap of 64 channels, as _res3_operands: (the three blocks, their geometries, eps, their learnable
-    tensors, their running statistics), judged on shapes alone.  Every block runs at the tap's extent."""
-    blocks = list(layer) if isinstance(layer, (nn.Sequential, list, tuple)) else []
-    if len(blocks) != 3 or not all(isinstance(b, Bottleneck) for b in blocks):
-        raise RuntimeError(_RES2_BUILT)
-    checks = [_bottleneck_check(b, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT) for b in blocks]
-    if not torch.is_tensor(tap) or tap.dim() != 4:
-        raise RuntimeError(_RES2_BUILT)
-    n, h, w = int(tap.shape[0]), int(tap.shape[1]) - 2, int(tap.shape[2]) - 2
-    if ([c[0] for c in checks] != [(64, 64, 1)] + [(256, 64, 1)] * 2 or tap.shape[3] != 64 or h < 1 or w < 1 or len({c[1] for c in checks}) > 1):
-        raise RuntimeError(_RES2_BUILT)
-    ops = [_bottleneck_operands(b, tap.device if device is None else device, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT) for b in blocks]
-    geoms = [(n, h, w, 64, 64, 1)] + [(n, h, w, 256, 64, 1)] * 2
-    return blocks, geoms, checks[0][1], [o[2] for o in ops], [tuple(o[3]) for o in ops]
+    return _forward_res_padded(_RES_STAGES[1], layer, c2_tap)
 
 
 def forward_res2_padded(layer, pool_tap):
     """ResNet-50's res2 (three Bottlenecks of width 64) on a padded pooled tap [n,h+2,w+2,64] (the stem's output, e.g.
     DetectorEngine.forward_pool) with the HIP training kernels, no gradient: padded C2 [n,h+2,w+2,256] fp16 with a zero ring."""
-    if not torch.is_tensor(pool_tap) or pool_tap.dim() != 4:
-        raise ValueError("padded taps must be contiguous float16 CUDA tensors [n,h+2,w+2,C]")
-    _, geoms, eps, learn, stats = _res2_operands(layer, pool_tap)
-    _check_padded_taps([pool_tap])
-    with torch.no_grad():
-        x = pool_tap.detach()
-        for g, lr, st in zip(geoms, learn, stats):
-            x = _block_forward_raw(x, g, eps, [t.detach() for t in lr], st, _BOTTLENECK64)[0]
-        return x
+    return _forward_res_padded(_RES_STAGES[0], layer, pool_tap)
 
 
 _PLANS = {
@@ -739,7 +672,7 @@ class FeaturePyramidNetwork(nn.Module):
         P2 as padded features (what DBHead.forward_padded reads), no gradient.  With a DBHead: FPN -> head as ONE autograd node that
         returns the head's maps, differentiable w.r.t. the FPN's ten live tensors and the head's twenty; the head's input gradient goes
         to the FPN's backward as the kernels leave it (NHWC fp32 with its power-of-two scale), never through an fp16 tensor."""
-        layers = (layer1, layer2, layer3, layer4)
+        layers, res = (layer1, layer2, layer3, layer4), (res2, res3, res4, res5)
         if res_batch_stats:
             given = tuple(k for k, m in (("res4", res4), ("res5", res5)) if m is not None)
             if res5 is None or res3 is not None or res2 is not None or stem is not None or any(m is not None for m in layers) or \
@@ -750,48 +683,20 @@ class FeaturePyramidNetwork(nn.Module):
             if res_batch_stats is not True and not (isinstance(res_batch_stats, (tuple, list)) and tuple(res_batch_stats) == given):
                 raise ValueError(f"forward_padded(..., res_batch_stats={res_batch_stats!r}) must be True or the tuple of exactly the res stages "
                                  f"given, {given!r}; " + _RES_BN_BUILT)
-            if res4 is not None:
-                return self._forward_padded_res4(taps, head, res5, res4, batch=True)
-            return self._forward_padded_res5(taps, head, res5, batch=True)
-        if res2 is not None:
-            if res3 is None or res4 is None or res5 is None:
-                raise ValueError("forward_padded(taps, head=head, res2=...) is ResNet-50's res2 -> res3 -> res4 -> res5 -> FPN -> head node: it "
-                                 "needs res3, res4 and res5 too")
-            if any(m is not None for m in layers) or trunk_batch_stats or stem_batch_stats:
-                raise ValueError("forward_padded(taps, head=head, res5=..., res4=..., res3=..., res2=...) is ResNet-50's res2 -> res3 -> res4 -> "
-                                 "res5 -> FPN -> head node with frozen-statistics BatchNorm: it takes no layer1 .. layer4, trunk_batch_stats or "
-                                 "stem_batch_stats (those are ResNet-18's)")
+            return self._forward_padded_res(taps, head, res, None, batch=True)
+        if any(m is not None for m in res):      # ResNet-50's node, from the lowest stage given up
+            low = next(i for i, m in enumerate(res) if m is not None)
+            names = [st.name for st in _RES_STAGES[low:]]
+            node = " -> ".join(names) + " -> FPN -> head node"
+            spelled = ", ".join(f"{name}=..." for name in reversed(names))
+            if any(m is None for m in res[low:]):
+                raise ValueError(f"forward_padded(taps, head=head, {names[0]}=...) is ResNet-50's {node}: it needs {_listed(names[1:])} too")
+            if any(m is not None for m in layers) or (stem is not None and low > 0) or trunk_batch_stats or stem_batch_stats:      # res2 takes the stem
+                raise ValueError(f"forward_padded(taps, head=head, {spelled}) is ResNet-50's {node} with frozen-statistics BatchNorm: it takes no "
+                                 f"layer1 .. layer4, {'stem, ' if low > 0 else ''}trunk_batch_stats or stem_batch_stats (those are ResNet-18's)")
             if head is None:
-                raise ValueError("forward_padded(taps, res5=..., res4=..., res3=..., res2=...) is the training node: it needs the DBHead too")
-            return self._forward_padded_res2(taps, head, res5, res4, res3, res2, stem)
-        if res3 is not None:
-            if res4 is None or res5 is None:
-                raise ValueError("forward_padded(taps, head=head, res3=...) is ResNet-50's res3 -> res4 -> res5 -> FPN -> head node: it needs res4 "
-                                 "and res5 too")
-            if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
-                raise ValueError("forward_padded(taps, head=head, res5=..., res4=..., res3=...) is ResNet-50's res3 -> res4 -> res5 -> FPN -> head "
-                                 "node with frozen-statistics BatchNorm: it takes no layer1 .. layer4, stem, trunk_batch_stats or stem_batch_stats "
-                                 "(those are ResNet-18's)")
-            if head is None:
-                raise ValueError("forward_padded(taps, res5=..., res4=..., res3=...) is the training node: it needs the DBHead too")
-            return self._forward_padded_res3(taps, head, res5, res4, res3)
-        if res4 is not None:
-            if res5 is None:
-                raise ValueError("forward_padded(taps, head=head, res4=...) is ResNet-50's res4 -> res5 -> FPN -> head node: it needs res5 too")
-            if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
-                raise ValueError("forward_padded(taps, head=head, res5=..., res4=...) is ResNet-50's res4 -> res5 -> FPN -> head node with "
-                                 "frozen-statistics BatchNorm: it takes no layer1 .. layer4, stem, trunk_batch_stats or stem_batch_stats (those are "
-                                 "ResNet-18's)")
-            if head is None:
-                raise ValueError("forward_padded(taps, res5=..., res4=...) is the training node: it needs the DBHead too")
-            return self._forward_padded_res4(taps, head, res5, res4)
-        if res5 is not None:
-            if any(m is not None for m in layers) or stem is not None or trunk_batch_stats or stem_batch_stats:
-                raise ValueError("forward_padded(taps, head=head, res5=...) is ResNet-50's res5 -> FPN -> head node with frozen-statistics BatchNorm: it "
-                                 "takes no layer1 .. layer4, stem, trunk_batch_stats or stem_batch_stats (those are ResNet-18's)")
-            if head is None:
-                raise ValueError("forward_padded(taps, res5=...) is the training node: it needs the DBHead too")
-            return self._forward_padded_res5(taps, head, res5)
+                raise ValueError(f"forward_padded(taps, {spelled}) is the training node: it needs the DBHead too")
+            return self._forward_padded_res(taps, head, res, stem)
         if stem_batch_stats:
             return self._forward_padded_batch_stem(taps, head, layers, stem, trunk_batch_stats, stem_batch_stats)
         bn_stages = ()
@@ -841,119 +746,53 @@ class FeaturePyramidNetwork(nn.Module):
             raise ValueError(f"train-mode BatchNorm needs more than one value per channel, got a C5 of {n} x {h5} x {w5}")
         return bbns, (bool(blocks[0].training), checks[0][3])
 
-    def _run_res_node(self, head, bns, plan, bbns, learn):
-        out = self._run_node(head, bns, plan, *learn)
-        if plan.bn is not None and plan.bn[0]:
+    def _forward_padded_res(self, taps, head, layers, stem, batch=False):
+        """forward_padded with ResNet-50 stages: `layers` is (res2, res3, res4, res5) with None below the lowest one given, where the node
+        starts (with `stem`, which goes with res2: at the stem, on the image tap).  `batch`: every block on the vtd_bottleneck_bn_train_*
+        entries, the blocks' mode deciding between batch and frozen statistics."""
+        low = next(i for i, m in enumerate(layers) if m is not None)
+        # the taps the node reads: the FPN levels below the lowest stage's output, the last of them that stage's input; res2 reads the pooled
+        # stem output and the stem the image, neither an FPN level
+        names = ["image"] if stem is not None else [st.tap for st in _RES_STAGES[1:low + 1]] or [_RES_STAGES[0].tap]
+        if not isinstance(taps, (list, tuple)) or len(taps) < len(names):
+            raise ValueError(f"padded taps must be the tensors [{', '.join(names)}]")
+        if stem is not None and (not isinstance(stem, (list, tuple)) or len(stem) != 2):
+            raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
+        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:len(names)])
+        slearn, splan = [], None
+        if stem is None:
+            _check_padded_taps(taps)
+            x = taps[-1]
+        else:
+            sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], taps[0])
+            splan = (sgeom, seps, tuple(sstats))
+            x = _meta_tap(sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2, 64)
+        dev = taps[-1].device
+        stages, ops, outs = _RES_STAGES[low:], [], []      # per stage: _res_operands' result, and its output C(k) as (n, C, h, w)
+        for st, layer in zip(stages, layers[low:]):      # every stage above the lowest is judged on a stand-in of the shape the one below gives
+            ops.append(_res_operands(st, layer, x, dev))
+            n, h, w = ops[-1][1][-1][:3]      # the extent the stage's last block runs at
+            if st.name == "res2" and (h % 8 or w % 8):      # C5 is an eighth of the pooled tap
+                raise RuntimeError(_RES2_BUILT + f"; the node needs a pooled tap whose extents are multiples of 8, got {h} x {w}")
+            outs.append((n, 4 * st.width, h, w))
+            x = _meta_tap(n, h, w, 4 * st.width)
+        beps = ops[0][2]
+        if any(o[2] != beps for o in ops):
+            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of " + _listed([st.name for st in stages]))
+        geom = self._geometry(([_tap_nchw(t) for t in taps] + outs)[-4:])      # C2 .. C5: the last four (the image and the pooled tap fall out)
+        params = self._live_checked(dev)
+        bns, hparams, hbuffers = head._train_operands(dev)
+        bbns, bn = self._res_bn_plan(layers[low:], outs[-1]) if batch else ([], None)
+        blocks = tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else st.entry, len(lr))
+                       for st, (_, geoms, _, learn, stats) in zip(stages, ops) for g, lr, s in zip(geoms, learn, stats))
+        per = 3 if len(stages) == 1 else tuple(st.blocks for st in stages)      # res5 alone: every stage has three
+        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, blocks, beps, bn, per)
+        out = self._run_node(head, bns, plan, *slearn, *(t for o in ops for lr in o[3] for t in lr), *params, *hparams)
+        if bn is not None and bn[0]:
             with torch.no_grad():
                 for b in bbns:
                     b.num_batches_tracked.add_(1)
         return out
-
-    def _forward_padded_res5(self, taps, head, res5, batch=False):
-        """forward_padded(taps, head=head, res5=layer): the plan of three Bottleneck blocks in one stage.  `batch`: on the
-        vtd_bottleneck_bn_train_* entries, the blocks' mode deciding between batch and frozen statistics."""
-        if not isinstance(taps, (list, tuple)) or len(taps) < 3:
-            raise ValueError("padded taps must be the tensors [C2, C3, C4]")
-        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:3])
-        _check_padded_taps(taps)
-        dev = taps[-1].device
-        _, geoms, beps, learn, stats = _res5_operands(res5, taps[-1], dev)
-        n, h, w = geoms[-1][:3]
-        geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 2048, h, w)])
-        params = self._live_checked(dev)
-        bns, hparams, hbuffers = head._train_operands(dev)
-        bbns, bn = self._res_bn_plan([res5], (n, 2048, h, w)) if batch else ([], None)
-        blocks = tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms, learn, stats))
-        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, bn, 3)
-        return self._run_res_node(head, bns, plan, bbns, (*(t for lr in learn for t in lr), *params, *hparams))
-
-    def _forward_padded_res4(self, taps, head, res5, res4, batch=False):
-        """forward_padded(taps, head=head, res5=layer5, res4=layer4): the plan of nine Bottleneck blocks in two stages, (6, 3).  `batch`: all
-        nine on the vtd_bottleneck_bn_train_* entries, as in _forward_padded_res5."""
-        if not isinstance(taps, (list, tuple)) or len(taps) < 2:
-            raise ValueError("padded taps must be the tensors [C2, C3]")
-        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:2])
-        _check_padded_taps(taps)
-        dev = taps[-1].device
-        _, geoms4, beps, learn4, stats4 = _res4_operands(res4, taps[-1], dev)
-        n, h3, w3 = geoms4[0][:3]
-        c4 = _meta_tap(n, h3 // 2, w3 // 2, 1024)      # res5 is judged on C4's shape (even extents): the tensor itself is computed in the node
-        _, geoms5, beps5, learn5, stats5 = _res5_operands(res5, c4, dev)
-        if beps5 != beps:
-            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of res4 and res5")
-        h, w = geoms5[-1][1:3]
-        geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 1024, h3 // 2, w3 // 2), (n, 2048, h, w)])
-        params = self._live_checked(dev)
-        bns, hparams, hbuffers = head._train_operands(dev)
-        bbns, bn = self._res_bn_plan([res4, res5], (n, 2048, h, w)) if batch else ([], None)
-        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK_BN if batch else _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
-        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, bn, (6, 3))
-        return self._run_res_node(head, bns, plan, bbns, (*(t for lr in learn4 + learn5 for t in lr), *params, *hparams))
-
-    def _forward_padded_res3(self, taps, head, res5, res4, res3):
-        """forward_padded(taps, head=head, res5=layer5, res4=layer4, res3=layer3): the plan of thirteen Bottleneck blocks in three stages,
-        (4, 6, 3)."""
-        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
-            raise ValueError("padded taps must be the tensors [C2]")
-        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:1])
-        _check_padded_taps(taps)
-        dev = taps[-1].device
-        _, geoms3, beps, learn3, stats3 = _res3_operands(res3, taps[-1], dev)
-        n, h2, w2 = geoms3[0][:3]
-        # res4 and res5 are judged on the shapes of C3 and C4 (even extents): the tensors themselves are computed in the node
-        _, geoms4, beps4, learn4, stats4 = _res4_operands(res4, _meta_tap(n, h2 // 2, w2 // 2, 512), dev)
-        _, geoms5, beps5, learn5, stats5 = _res5_operands(res5, _meta_tap(n, h2 // 4, w2 // 4, 1024), dev)
-        if beps4 != beps or beps5 != beps:
-            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of res3, res4 and res5")
-        h, w = geoms5[-1][1:3]
-        geom = self._geometry([_tap_nchw(t) for t in taps] + [(n, 512, h2 // 2, w2 // 2), (n, 1024, h2 // 4, w2 // 4), (n, 2048, h, w)])
-        params = self._live_checked(dev)
-        bns, hparams, hbuffers = head._train_operands(dev)
-        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK128, len(lr)) for g, lr, s in zip(geoms3, learn3, stats3)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
-        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), None, blocks, beps, None, (4, 6, 3))
-        return self._run_node(head, bns, plan, *(t for lr in learn3 + learn4 + learn5 for t in lr), *params, *hparams)
-
-    def _forward_padded_res2(self, taps, head, res5, res4, res3, res2, stem):
-        """forward_padded(taps, head=head, res5=, res4=, res3=, res2=[, stem=]): the plan of sixteen Bottleneck blocks in four stages,
-        (3, 4, 6, 3), on the pooled tap; with `stem`, on the image tap with the stem's launch in front."""
-        name = "image" if stem is not None else "pool"
-        if not isinstance(taps, (list, tuple)) or len(taps) < 1:
-            raise ValueError(f"padded taps must be the tensors [{name}]")
-        if stem is not None and (not isinstance(stem, (list, tuple)) or len(stem) != 2):
-            raise ValueError("stem must be the pair (conv, bn) of the trunk's first two modules")
-        taps = tuple(t.detach() if torch.is_tensor(t) else t for t in taps[:1])
-        slearn, splan = [], None
-        if stem is None:
-            _check_padded_taps(taps)
-            pool = taps[0]
-        else:
-            sgeom, seps, slearn, sstats = _stem_operands(stem[0], stem[1], taps[0])
-            splan = (sgeom, seps, tuple(sstats))
-            pool = _meta_tap(sgeom[0], (sgeom[1] // 2 + 1) // 2, (sgeom[2] // 2 + 1) // 2, 64)
-        dev = taps[0].device
-        _, geoms2, beps, learn2, stats2 = _res2_operands(res2, pool, dev)
-        n, h2, w2 = geoms2[0][:3]
-        if h2 % 8 or w2 % 8:
-            raise RuntimeError(_RES2_BUILT + f"; the node needs a pooled tap whose extents are multiples of 8, got {h2} x {w2}")
-        # res3, res4 and res5 are judged on the shapes of C2, C3 and C4: the tensors themselves are computed in the node
-        _, geoms3, beps3, learn3, stats3 = _res3_operands(res3, _meta_tap(n, h2, w2, 256), dev)
-        _, geoms4, beps4, learn4, stats4 = _res4_operands(res4, _meta_tap(n, h2 // 2, w2 // 2, 512), dev)
-        _, geoms5, beps5, learn5, stats5 = _res5_operands(res5, _meta_tap(n, h2 // 4, w2 // 4, 1024), dev)
-        if beps3 != beps or beps4 != beps or beps5 != beps:
-            raise ValueError("the HIP Bottleneck kernels need one eps on all BatchNorms of res2, res3, res4 and res5")
-        h, w = geoms5[-1][1:3]
-        geom = self._geometry([(n, 256, h2, w2), (n, 512, h2 // 2, w2 // 2), (n, 1024, h2 // 4, w2 // 4), (n, 2048, h, w)])
-        params = self._live_checked(dev)
-        bns, hparams, hbuffers = head._train_operands(dev)
-        blocks = (tuple(_BlockPlan(g, s, _BOTTLENECK64, len(lr)) for g, lr, s in zip(geoms2, learn2, stats2)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK128, len(lr)) for g, lr, s in zip(geoms3, learn3, stats3)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK256, len(lr)) for g, lr, s in zip(geoms4, learn4, stats4)) +
-                  tuple(_BlockPlan(g, s, _BOTTLENECK, len(lr)) for g, lr, s in zip(geoms5, learn5, stats5)))
-        plan = _TrunkPlan(taps, geom, (head.training, bns[0].momentum, bns[0].eps, tuple(hbuffers)), splan, blocks, beps, None, (3, 4, 6, 3))
-        return self._run_node(head, bns, plan, *slearn, *(t for lr in learn2 + learn3 + learn4 + learn5 for t in lr), *params, *hparams)
 
     def _forward_padded_batch_stem(self, taps, head, layers, stem, trunk_batch_stats, stem_batch_stats):
         """forward_padded(..., stem_batch_stats=True): the whole-backbone node with batch statistics in the stem too."""
@@ -1450,6 +1289,21 @@ _BOTTLENECK_STRUCT = _BOTTLENECK_FAMILIES + (_BOTTLENECK_BN,)   # the families o
 _BN_FAMILIES = (_BLOCK_BN, _TRUNK_BN, _BOTTLENECK_BN)   # the batch-statistics families a caller names itself; any other entry means
                                                         # vtd_resblock_bn_train
 
+# ResNet-50's four residual stages, lowest first, as _STAGES is ResNet-18's: `slot` is the stage's place in the backbone, `blocks` the count
+# of its Bottlenecks (the first cin -> width -> 4 width at `stride`, the others 4 width -> width -> 4 width at stride 1), `tap` names the
+# stage's input, `entry` is its entry family with frozen-statistics BatchNorm, `geometries` and `family_built` are what that family runs
+# and its refusal, `built` is the stage's own refusal
+_ResStage = namedtuple("_ResStage", "name slot blocks cin width stride tap entry geometries family_built built")
+_RES_STAGES = (_ResStage("res2", 4, 3, 64, 64, 1, "pool", _BOTTLENECK64, _BOTTLENECK64_GEOMETRIES, _BOTTLENECK64_BUILT, _RES2_BUILT),
+               _ResStage("res3", 5, 4, 256, 128, 2, "C2", _BOTTLENECK128, _BOTTLENECK128_GEOMETRIES, _BOTTLENECK128_BUILT, _RES3_BUILT),
+               _ResStage("res4", 6, 6, 512, 256, 2, "C3", _BOTTLENECK256, _BOTTLENECK256_GEOMETRIES, _BOTTLENECK256_BUILT, _RES4_BUILT),
+               _ResStage("res5", 7, 3, 1024, 512, 2, "C4", _BOTTLENECK, _BOTTLENECK_GEOMETRIES, _BOTTLENECK_BUILT, _RES5_BUILT))
+
+
+def _listed(names):
+    """The names as a phrase: 'a', 'a and b', 'a, b and c'."""
+    return " and ".join(filter(None, (", ".join(names[:-1]), names[-1])))
+
 
 def _block_entry(geom):
     """The entry family of a block of basic_block_train's seven, by its width."""
@@ -1652,7 +1506,7 @@ class _FPNTrainFn(torch.autograd.Function):
 # `bn` None or (training, momentum) for blocks on the batch-statistics entries.  _BlockPlan: the block's geometry, its running statistics,
 # its entry family and the count of its learnable tensors (9 with a downsample, 6 without; a Bottleneck's 12 and 9).  `per`: the blocks of
 # each stage of the plan, 2 for ResNet-18's BasicBlock stages and 3 for ResNet-50's res5 alone; an int means "every stage", a tuple gives
-# every stage its own count from the lowest up: (6, 3) for ResNet-50's res4 below res5, (4, 6, 3) with res3 below both
+# every stage its own count from the lowest up (_RES_STAGES' block counts).  A stage's last block is a C(k)
 _TrunkPlan = namedtuple("_TrunkPlan", "taps geom head stem blocks beps bn per", defaults=(2,))
 _BlockPlan = namedtuple("_BlockPlan", "geom stats entry nlearn")
 
@@ -1662,10 +1516,8 @@ class _TrunkFPNHeadTrainFn(torch.autograd.Function):
     Inputs: the plan, then the learnable tensors: the stem's 3 if it runs, those of the blocks from the lowest up, the FPN's 10, the head's 20.
 
     Forward: the stem's launch on the image tap if there is one, then the blocks in order, each on the tap the one before wrote; the last
-    tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every stage's last block (every
-    second block; with plan.per = 3, ResNet-50's res5 on the vtd_bottleneck_train_* entries, the third; with plan.per = (6, 3), res4 on the
-    vtd_bottleneck256_train_* entries below it, the sixth and the ninth; with (4, 6, 3), res3 on the vtd_bottleneck128_train_* entries below
-    both, the fourth, the tenth and the thirteenth).
+    tap of plan.taps is the lowest block's input otherwise.  C2 .. C5 are the taps given and the output of every stage's last block, the
+    stages being plan.per blocks each (ResNet-50's Bottleneck stages: a tuple of their counts from the lowest up).
 
     Backward: head -> FPN -> the blocks from the top down, every gradient handed on as the kernels leave it (NHWC fp32 with its power-of-two
     scale), never through fp16 or an NCHW copy.  The FPN's backward forms dC(k) for the levels the node computes itself (the top
@@ -1916,6 +1768,10 @@ _RES_MODES = (_RES5_MODE, _RES4_MODE, _RES3_MODE, _RES2_MODE)
 # the whole ResNet-50 detector: the four stages and the stem; nothing is frozen and the train-mode forward needs no trunk engine.  ResNet-18's
 # name for the same, "head+fpn+backbone", stays refused on resnet50
 _RES_WHOLE_MODE = "head+fpn+res5+res4+res3+res2+stem"
+# what _RES_MODES and _RES_WHOLE_MODE name, and how ResNet-18's mode of the same depth (_STAGE_MODES, _BACKBONE_MODE) says it
+_RES_MODE_NAMES = (("last stage (three Bottlenecks)", "the last stage trains"), ("upper two stages (nine Bottlenecks)", "the upper two stages train"),
+                   ("upper three stages (thirteen Bottlenecks)", "the upper three stages train"),
+                   ("four stages (sixteen Bottlenecks)", "the four stages train"), ("four stages and stem", "the whole detector trains"))
 
 
 class DBNet(_EngineOwner, nn.Module):
@@ -2040,26 +1896,11 @@ class DBNet(_EngineOwner, nn.Module):
             if self.backbone_name != "resnet18":
                 raise ValueError(f"trainable={trainable!r} is built for resnet18 only: {self.backbone_name} has Bottleneck blocks, and "
                                  "Bottleneck training is not built under this name (resnet50's last stage trains with trainable='head+fpn+res5')")
-        elif trainable == _RES5_MODE:
-            if self.backbone_name != "resnet50":
-                raise ValueError(f"trainable={trainable!r} names ResNet-50's last stage (three Bottlenecks); on {self.backbone_name} the last stage "
-                                 "trains with trainable='head+fpn+layer4'")
-        elif trainable == _RES4_MODE:
-            if self.backbone_name != "resnet50":
-                raise ValueError(f"trainable={trainable!r} names ResNet-50's upper two stages (nine Bottlenecks); on {self.backbone_name} the upper "
-                                 "two stages train with trainable='head+fpn+layer4+layer3'")
-        elif trainable == _RES3_MODE:
-            if self.backbone_name != "resnet50":
-                raise ValueError(f"trainable={trainable!r} names ResNet-50's upper three stages (thirteen Bottlenecks); on {self.backbone_name} the "
-                                 "upper three stages train with trainable='head+fpn+layer4+layer3+layer2'")
-        elif trainable == _RES2_MODE:
-            if self.backbone_name != "resnet50":
-                raise ValueError(f"trainable={trainable!r} names ResNet-50's four stages (sixteen Bottlenecks); on {self.backbone_name} the "
-                                 "four stages train with trainable='head+fpn+layer4+layer3+layer2+layer1'")
-        elif trainable == _RES_WHOLE_MODE:
-            if self.backbone_name != "resnet50":
-                raise ValueError(f"trainable={trainable!r} names ResNet-50's four stages and stem; on {self.backbone_name} the whole detector "
-                                 "trains with trainable='head+fpn+backbone'")
+        elif trainable in _RES_MODES or trainable == _RES_WHOLE_MODE:
+            if self.backbone_name != "resnet50":      # the refusal names ResNet-18's mode of the same depth
+                k = (_RES_MODES + (_RES_WHOLE_MODE,)).index(trainable)
+                raise ValueError(f"trainable={trainable!r} names ResNet-50's {_RES_MODE_NAMES[k][0]}; on {self.backbone_name} {_RES_MODE_NAMES[k][1]} "
+                                 f"with trainable={(_STAGE_MODES + (_BACKBONE_MODE,))[k]!r}")
         elif trainable not in (None, "head", "head+fpn"):
             raise ValueError(f"trainable must be None, 'head' or 'head+fpn', got {trainable!r}")
         bn_mode = getattr(self, "trunk_bn", "frozen") if trunk_bn is None else trunk_bn
@@ -2117,20 +1958,12 @@ class DBNet(_EngineOwner, nn.Module):
         tensors = list(self.head.parameters()) + list(self.head.buffers())
         if self.trainable == "head+fpn" or self.trainable in _STAGE_MODES or self.trainable in (_BACKBONE_MODE, _RES_WHOLE_MODE) + _RES_MODES:
             tensors += list(self.fpn.parameters())
-        if self.trainable in _RES_MODES:      # backbone.7's 30 parameters and 30 buffers
-            tensors += list(self.backbone[7].parameters()) + list(self.backbone[7].buffers())
-        if self.trainable in (_RES4_MODE, _RES3_MODE, _RES2_MODE):      # and backbone.6's 57 and 57
-            tensors += list(self.backbone[6].parameters()) + list(self.backbone[6].buffers())
-        if self.trainable in (_RES3_MODE, _RES2_MODE):      # and backbone.5's 39 and 39
-            tensors += list(self.backbone[5].parameters()) + list(self.backbone[5].buffers())
-        if self.trainable == _RES2_MODE:      # and backbone.4's 30 and 30
-            tensors += list(self.backbone[4].parameters()) + list(self.backbone[4].buffers())
         if self.trainable in (_BACKBONE_MODE, _RES_WHOLE_MODE):      # the four stages as in the layer1 mode, then the stem's three parameters and three buffers
             for i in (7, 6, 5, 4, 0, 1):
                 tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
-        if self.trainable in _STAGE_MODES:      # the stages the mode trains, from layer4 down
-            for i in range(_STAGE_MODES.index(self.trainable) + 1):
-                tensors += list(self.backbone[7 - i].parameters()) + list(self.backbone[7 - i].buffers())
+        if self.trainable in _STAGE_MODES or self.trainable in _RES_MODES:      # the stages the mode trains, from the last one down
+            for i in range(7, self._first_trained() - 1, -1):
+                tensors += list(self.backbone[i].parameters()) + list(self.backbone[i].buffers())
         return tuple(t._version for t in tensors)
 
     def trunk_engine(self):
@@ -2192,14 +2025,8 @@ class DBNet(_EngineOwner, nn.Module):
                     return self._forward_train_backbone(x)
                 if self.trainable == _RES_WHOLE_MODE:
                     return self._forward_train_res_whole(x)
-                if self.trainable == _RES2_MODE:
-                    return self._forward_train_res2(x)
-                if self.trainable == _RES5_MODE:
-                    return self._forward_train_res5(x)
-                if self.trainable == _RES4_MODE:
-                    return self._forward_train_res4(x)
-                if self.trainable == _RES3_MODE:
-                    return self._forward_train_res3(x)
+                if self.trainable in _RES_MODES:
+                    return self._forward_train_res(x)
                 if self.trainable in _STAGE_MODES:
                     return self._forward_train_trunk(x)
                 return self._forward_train_head(x) if self.trainable == "head" else self._forward_train_head_fpn(x)
@@ -2265,69 +2092,28 @@ class DBNet(_EngineOwner, nn.Module):
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
-    def _forward_train_res5(self, x):
-        """The train-mode forward of "head+fpn+res5": C2 .. C4 from the frozen trunk engine (its own C5 comes from the res5 weights it was built
-        with and is ignored), then res5, the FPN and the head as one autograd node."""
-        frozen = [n for i in range(7) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
+    def _forward_train_res(self, x):
+        """The train-mode forward of ResNet-50's stage modes: the input of the lowest trained stage from the frozen trunk engine, then the
+        trained stages, the FPN and the head as one autograd node.  What the engine computes from the trained stages comes from the weights
+        it was built with and is ignored (its C5 in the res5 mode, C4 and C5 in the res4 mode) or never runs (forward_c2 stops at C2 in the
+        res3 mode, forward_pool after the stem in the res2 mode)."""
+        first = self._first_trained()
+        stages = _RES_STAGES[first - 4:]
+        frozen = [n for i in range(first) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
         if frozen:
-            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res5 is not implemented; only "
-                               "res5 (backbone.7), the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. backbone.6)")
-        for m in (self.backbone[7], self.fpn, self.head):
+            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below {stages[0].name} is not "
+                               f"implemented; only {', '.join(f'{st.name} (backbone.{st.slot})' for st in stages)}, the FPN and the DB head train "
+                               f"(set requires_grad_(False) on backbone.0 .. backbone.{first - 1}" +
+                               (f", or pick trainable={_RES_WHOLE_MODE!r})" if first == 4 else ")"))
+        for m in (*(self.backbone[st.slot] for st in stages), self.fpn, self.head):
             if not next(m.parameters()).is_cuda:
                 m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = self.trunk_engine().forward_trunk(x)[:3]   # new tensors per call: autograd may keep them
-        # trunk_bn="bottleneck": res5 on the batch-statistics entries, its 20 running buffers and 10 counters move too; mark_dirty covers them
-        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res_batch_stats=getattr(self, "trunk_bn", "frozen") == "bottleneck")
-        self.mark_dirty()   # the kernels updated the head's running statistics in place
-        return out
-
-    def _forward_train_res4(self, x):
-        """The train-mode forward of "head+fpn+res5+res4": C2 and C3 from the frozen trunk engine (its own C4 and C5 come from the res4 and res5
-        weights it was built with and are ignored), then res4, res5, the FPN and the head as one autograd node."""
-        frozen = [n for i in range(6) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
-        if frozen:
-            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res4 is not implemented; only "
-                               "res4 (backbone.6), res5 (backbone.7), the FPN and the DB head train (set requires_grad_(False) on backbone.0 .. "
-                               "backbone.5)")
-        for m in (self.backbone[6], self.backbone[7], self.fpn, self.head):
-            if not next(m.parameters()).is_cuda:
-                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = self.trunk_engine().forward_trunk(x)[:2]   # new tensors per call: autograd may keep them
-        # trunk_bn="bottleneck": res4 and res5 on the batch-statistics entries, their 58 running buffers and 29 counters move too
-        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6],
-                                      res_batch_stats=getattr(self, "trunk_bn", "frozen") == "bottleneck")
-        self.mark_dirty()   # the kernels updated the head's running statistics in place
-        return out
-
-    def _forward_train_res3(self, x):
-        """The train-mode forward of "head+fpn+res5+res4+res3": C2 from the frozen trunk engine, which stops there (forward_c2: none of its
-        res3, res4 and res5, built from stale weights, runs), then res3, res4, res5, the FPN and the head as one autograd node."""
-        frozen = [n for i in range(5) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
-        if frozen:
-            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res3 is not implemented; only "
-                               "res3 (backbone.5), res4 (backbone.6), res5 (backbone.7), the FPN and the DB head train (set requires_grad_(False) "
-                               "on backbone.0 .. backbone.4)")
-        for m in (self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
-            if not next(m.parameters()).is_cuda:
-                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = [self.trunk_engine().forward_c2(x)]   # a new tensor per call: autograd may keep it
-        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6], res3=self.backbone[5])
-        self.mark_dirty()   # the kernels updated the head's running statistics in place
-        return out
-
-    def _forward_train_res2(self, x):
-        """The train-mode forward of "head+fpn+res5+res4+res3+res2": the pooled stem output from the frozen trunk engine, which stops there
-        (forward_pool: the stem alone runs), then res2 .. res5, the FPN and the head as one autograd node."""
-        frozen = [n for i in range(4) for n, p in self.backbone[i].named_parameters(prefix=f"backbone.{i}") if p.requires_grad]
-        if frozen:
-            raise RuntimeError(f"DBNet(trainable={self.trainable!r}): {frozen[0]} requires grad, but backward below res2 is not implemented; only "
-                               "res2 .. res5 (backbone.4 .. backbone.7), the FPN and the DB head train (set requires_grad_(False) on backbone.0 "
-                               "and backbone.1, or pick trainable='head+fpn+res5+res4+res3+res2+stem')")
-        for m in (self.backbone[4], self.backbone[5], self.backbone[6], self.backbone[7], self.fpn, self.head):
-            if not next(m.parameters()).is_cuda:
-                m.cuda()   # their own tensors are the kernels' operands (the optimizer keeps the same Parameter objects)
-        taps = [self.trunk_engine().forward_pool(x)]   # a new tensor per call: autograd may keep it
-        out = self.fpn.forward_padded(taps, head=self.head, res5=self.backbone[7], res4=self.backbone[6], res3=self.backbone[5], res2=self.backbone[4])
+        engine = self.trunk_engine()      # new tensors per call: autograd may keep them
+        taps = [engine.forward_pool(x)] if first == 4 else [engine.forward_c2(x)] if first == 5 else engine.forward_trunk(x)[:first - 4]
+        # trunk_bn="bottleneck" (set_trainable: res5, or res4 and res5): the stages on the batch-statistics entries, their running buffers and
+        # counters move too; mark_dirty covers them
+        batch = {"res_batch_stats": True} if getattr(self, "trunk_bn", "frozen") == "bottleneck" else {}
+        out = self.fpn.forward_padded(taps, head=self.head, **{st.name: self.backbone[st.slot] for st in stages}, **batch)
         self.mark_dirty()   # the kernels updated the head's running statistics in place
         return out
 
